@@ -18,6 +18,7 @@ One process per GPU; reads are sharded by rank, there is no data-path collective
 rank processes --reads reads per step.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR   # + the last step's results as DIR/*.npy (dump_outputs)
     python bench.py --gpus N ...            # WORLD_SIZE unset: starts N workers itself (child torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -80,6 +81,48 @@ def parity_sample(recs, n_unique, res, cbuf, coff, mdist, k=64, seed=1234):
         got = raw[coff[i]:coff[i + 1]].decode() if res["status"][i] == 0 else ""
         bad += int(res["status"][i] != orr.status or got != oc)
     return {"reads": len(idx), "mismatches": bad, "checker": "oracle/libc3oracle.so (status + consensus bytes), after the timed region"}
+
+
+DUMP_BYTES = 64 << 20
+DUMP_FIELDS = ("status", "n_peaks", "n_sub", "has_front", "has_tail", "front_end", "tail_beg", "cons_len", "draft_len", "n_win")
+
+
+def dump_outputs(path, res, cbuf, coff, lens, seed=2024, budget=DUMP_BYTES):
+    """writes what a caller of the timed path receives for one batch -- the read records and the consensus bytes of
+    c3_batch_results -- for a seeded sample of its reads, as float32 / float64 .npy files of at most `budget` bytes in all:
+      read_index                 float64 [k]        the sampled reads' positions in the batch (ascending)
+      status ... n_win           float32 [k]        one file per scalar field of c3_read_result
+      peaks, sub_beg, sub_end    float32 [k, 256]   entries past n_peaks / n_sub (unspecified in the records) written as -1
+      consensus                  float32 [sum]      consensus bytes (ASCII codes) of the sampled reads, concatenated
+      consensus_offsets          float64 [k + 1]    read i's consensus is consensus[offsets[i]:offsets[i + 1]]
+    The sample depends on the batch size and the read lengths only, never on the results, so two builds dump the same reads; a
+    read's consensus is never longer than the read (k_stitch), which bounds its share of the budget.  Returns a summary."""
+    from c3poa_amd import _lib
+    n = len(res)
+    assert len(lens) == n and int(lens.max()) < 1 << 24            # every record value is then exact in float32
+    # bytes per sampled read: the float32 record, its read_index and consensus_offsets entries, at most len(read) float32 bytes;
+    # 4 KB are kept for the .npy headers and the last offset
+    per_read = 4 * (len(DUMP_FIELDS) + 3 * _lib.MAX_PEAKS) + 8 + 8 + 4 * lens.astype(np.int64)
+    order = np.random.default_rng(seed).permutation(n)
+    k = int(np.searchsorted(np.cumsum(per_read[order]), budget - 4096, side="right"))
+    idx = np.sort(order[:k])
+    sel = res[idx]
+    arrays = {"read_index": idx.astype(np.float64)}
+    for f in DUMP_FIELDS:
+        arrays[f] = sel[f].astype(np.float32)
+    col = np.arange(_lib.MAX_PEAKS)[None, :]
+    for f, cnt in (("peaks", "n_peaks"), ("sub_beg", "n_sub"), ("sub_end", "n_sub")):
+        arrays[f] = np.where(col < sel[cnt][:, None], sel[f], -1).astype(np.float32)
+    beg, end = coff[idx], coff[idx + 1]
+    arrays["consensus"] = np.concatenate([cbuf[b:e] for b, e in zip(beg, end)] + [cbuf[:0]]).astype(np.float32)
+    arrays["consensus_offsets"] = np.concatenate(([0], np.cumsum(end - beg))).astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    nbytes = 0
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+        nbytes += os.path.getsize(os.path.join(path, name + ".npy"))
+    assert nbytes <= budget, nbytes
+    return {"dir": path, "reads": int(k), "of": int(n), "bytes": int(nbytes), "seed": seed}
 
 
 def _gen_shard(args):
@@ -158,7 +201,11 @@ def parse_args(argv=None):
                     help="comma list of further configs run for 3 steps after the headline (rank 0, N=1): 'auto' = cfg3,cfg4,cfgL "
                          "when the headline is cfg2 at full size, 'none' = skip")
     ap.add_argument("--other-unique", type=int, default=0, help="distinct reads generated for each of the other configs (0 = all distinct, no tiling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step delivered (rank 0's records + consensus bytes, seeded sample of reads) as DIR/<name>.npy")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.reads <= 0:
         a.reads = DEFAULT_READS.get(a.cfg, 100000)
     return a
@@ -282,6 +329,7 @@ def main():
         dt = float(t.item())
     tm = h.last_timing
     res, cbuf, coff = res_raw
+    dumped = dump_outputs(a.dump_outputs, res, cbuf, coff, lens) if a.dump_outputs and rank == 0 else None
     ok = res["status"] == 0
     # digest of this rank's shard (status + consensus bytes of the last step): lets a test compare the union of the shards of an
     # N-rank run with single-process results
@@ -354,6 +402,8 @@ def main():
                          "gcups": round(cells / (sum(avg.values()) * 1e-3) / 1e9, 2)},
             "gen_s": round(t_gen, 1),
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
     h.close()
     host.close()
     if rank == 0 and not a.no_cpu:
