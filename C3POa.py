@@ -36,6 +36,10 @@ def parse_args(argv=None):
                         help="Sets the median distance cutoff for consensus sequences. Defaults to 500.")
     parser.add_argument("--zero", "-z", action="store_false", default=True,
                         help="Use to exclude zero repeat reads. Defaults to True (includes zero repeats).")
+    parser.add_argument("--zero-max-cells", dest="zero_max_cells", type=int, default=16777216,
+                        help="Largest product of the two dangling piece lengths for which the zero-repeat rescue is "
+                             "tried (1..2147483647). The reference has no cap; raise this for long-insert libraries, "
+                             "whose zero-repeat reads have pieces of 4-8 kb. Defaults to 16777216.")
     parser.add_argument("--numThreads", "-n", type=int, default=1, help="Number of GPUs (workers) to use. Defaults to 1.")
     parser.add_argument("--groupSize", "-g", type=int, default=1000,
                         help="Number of reads processed by each worker in each iteration. Defaults to 1000.")

@@ -25,13 +25,17 @@ EXPORTS = ["c3_default_config", "c3_version", "c3_device_count", "c3_warm_device
            "c3_host_alloc", "c3_host_free", "c3_writer_reset"]
 
 
+ZERO_MAX_CELLS = 16777216       # c3_default_config's zero_max_cells: largest front * tail the zero-repeat rescue takes
+
+
 class Config(C.Structure):
     _fields_ = ([("device", C.c_int), ("conk_match", C.c_int), ("conk_mismatch", C.c_int), ("conk_penalty", C.c_int),
                  ("sg_iters", C.c_int), ("sg_window", C.c_int), ("sg_order", C.c_int), ("mdistcutoff", C.c_int),
                  ("poa_match", C.c_int), ("poa_mismatch", C.c_int), ("poa_o1", C.c_int), ("poa_e1", C.c_int),
                  ("poa_o2", C.c_int), ("poa_e2", C.c_int), ("poa_band_b", C.c_int), ("poa_band_f", C.c_double),
                  ("pol_match", C.c_int), ("pol_mismatch", C.c_int), ("pol_gap", C.c_int), ("pol_window", C.c_int),
-                 ("pol_q", C.c_int), ("dang_band", C.c_int), ("slots_poa", C.c_int), ("slots_win", C.c_int), ("zero", C.c_int)])
+                 ("pol_q", C.c_int), ("dang_band", C.c_int), ("slots_poa", C.c_int), ("slots_win", C.c_int), ("zero", C.c_int),
+                 ("zero_max_cells", C.c_int64)])
 
 
 class ReadResult(C.Structure):

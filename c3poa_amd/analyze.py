@@ -15,10 +15,11 @@ from .records import consensus_record, subread_records, zero_repeat_records
 _HANDLES = {}
 
 
-def get_handle(device=0, mdistcutoff=500, zero=True):
-    key = (device, mdistcutoff, bool(zero))
+def get_handle(device=0, mdistcutoff=500, zero=True, zero_max_cells=_lib.ZERO_MAX_CELLS):
+    key = (device, mdistcutoff, bool(zero), int(zero_max_cells))
     if key not in _HANDLES:
-        _HANDLES[key] = _lib.Handle(device=device, mdistcutoff=mdistcutoff, zero=1 if zero else 0)
+        _HANDLES[key] = _lib.Handle(device=device, mdistcutoff=mdistcutoff, zero=1 if zero else 0,
+                                    zero_max_cells=int(zero_max_cells))
     return _HANDLES[key]
 
 
@@ -41,7 +42,8 @@ def analyze_reads(args, reads, splint_dict, adapter_dict, adapter_set, iteration
     if not reads:
         return
     splint_names = sorted(splint_dict)
-    h = get_handle(device, args.mdistcutoff, getattr(args, "zero", True))
+    h = get_handle(device, args.mdistcutoff, getattr(args, "zero", True),
+                   getattr(args, "zero_max_cells", _lib.ZERO_MAX_CELLS))
     h.set_splints([splint_dict[n][0] for n in splint_names])
     res, cons = run_batch(h, reads, splint_names, splint_dict, adapter_dict)
     write_group(args, reads, res, cons, adapter_dict, iteration)

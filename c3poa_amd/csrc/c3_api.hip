@@ -21,6 +21,7 @@ extern "C" void c3k_launch_prep(const PrepArgs*, int, hipStream_t);
 extern "C" void c3k_launch_window(const WinArgs*, int, hipStream_t);
 extern "C" void c3k_launch_stitch(const StitchArgs*, int, hipStream_t);
 extern "C" void c3k_launch_zero(const ZeroArgs*, int, hipStream_t);
+extern "C" void c3k_launch_zero_long(const ZeroArgs*, int, hipStream_t);
 extern "C" void c3k_launch_zero_finish(const ZeroArgs*, int, hipStream_t);
 
 // ---- small kernels ----------------------------------------------------------------------
@@ -168,7 +169,8 @@ struct c3_handle {
   int n_poa_redo16 = 0;      // ... of them: because a score left the 16-bit cells
   DBuf s_eH, s_eD, s_lw, d_wrec, d_wlay, d_wbase, d_wout;       // prep / windows
   DBuf s_win_i, s_win_nk, s_win_h, s_win_d, s_win_b, s_win_sc, s_win_desc, s_win_h2, s_win_d2, d_wovf;
-  DBuf s_zero_d, d_zinfo, d_zflag, d_zwork; std::vector<int> zwork;  // window scratch
+  DBuf s_zero_d, d_zinfo, d_zflag, d_zwork; std::vector<int> zwork;  // zero-repeat rescue: k_zero direction bytes, per-read records, work list
+  DBuf s_zero_l;                                                      // k_zero_long slots
   std::vector<Summary> sum; std::vector<int> work;
   int res_prefix = 0;            // entries of peaks[] / sub_beg[] / sub_end[] that any read of the resident batch uses (0: unknown)
   int peaks_grid = 0; bool debug_msa = false; bool injected = false;
@@ -194,7 +196,7 @@ extern "C" void c3_default_config(c3_config* c) {
   c->poa_match = 5; c->poa_mismatch = 4; c->poa_o1 = 4; c->poa_e1 = 2; c->poa_o2 = 24; c->poa_e2 = 1;
   c->poa_band_b = 10; c->poa_band_f = 0.01;
   c->pol_match = 3; c->pol_mismatch = -5; c->pol_gap = -4; c->pol_window = 500; c->pol_q = 5; c->dang_band = 128;
-  c->slots_poa = 0; c->slots_win = 0; c->zero = 1;
+  c->slots_poa = 0; c->slots_win = 0; c->zero = 1; c->zero_max_cells = 16 << 20;
 }
 extern "C" const char* c3_version(void) { return "c3poa_amd 0.1 (gfx950)"; }
 extern "C" int c3_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; } return n; }
@@ -221,6 +223,7 @@ extern "C" int c3_create(const c3_config* cfg, c3_handle** out) {
   }
   if (cfg->sg_order != 2 && cfg->sg_order != 3) { g_create_err = "sg_order must be 2 or 3"; return C3_E_ARG; }
   if (cfg->sg_window < 5 || cfg->sg_window > 127 || !(cfg->sg_window & 1)) { g_create_err = "sg_window must be odd, 5..127"; return C3_E_ARG; }
+  if (cfg->zero_max_cells < 1 || cfg->zero_max_cells > INT32_MAX) { g_create_err = "zero_max_cells must be 1..2147483647"; return C3_E_ARG; }
   c3_handle* h = new c3_handle();
   h->cfg = *cfg;
   if ((e = hipSetDevice(cfg->device)) != hipSuccess) { g_create_err = hipGetErrorString(e); delete h; return C3_E_HIP; }
@@ -255,7 +258,7 @@ extern "C" void c3_destroy(c3_handle* h) {
                  &h->d_info, &h->d_track, &h->d_draft, &h->d_tpos, &h->d_cons, &h->d_counter, &h->d_raw, &h->d_nraw, &h->d_sum,
                  &h->d_work, &h->d_bufA, &h->d_bufB, &h->d_cand, &h->d_cst, &h->d_msa, &h->d_msa_off, &h->d_msa_len,
                  &h->s_poa_i, &h->s_poa_nk, &h->s_poa_cells, &h->s_poa_b, &h->s_poa_sc, &h->s_poa_desc, &h->s_poa_jump, &h->s_poa_path, &h->d_overflow, &h->s_eH, &h->s_eD, &h->s_lw, &h->d_wrec,
-                 &h->d_wlay, &h->d_wbase, &h->d_wout, &h->s_win_i, &h->s_win_nk, &h->s_win_h, &h->s_win_d, &h->s_win_b, &h->s_win_sc, &h->s_win_desc, &h->s_zero_d, &h->d_zinfo, &h->d_zflag, &h->d_zwork, &h->d_gather, &h->d_gather_off};
+                 &h->d_wlay, &h->d_wbase, &h->d_wout, &h->s_win_i, &h->s_win_nk, &h->s_win_h, &h->s_win_d, &h->s_win_b, &h->s_win_sc, &h->s_win_desc, &h->s_zero_d, &h->s_zero_l, &h->d_zinfo, &h->d_zflag, &h->d_zwork, &h->d_gather, &h->d_gather_off};
   for (DBuf* b : all) b->release();
   { DBuf* sh[] = {&h->st.d_ascii, &h->st.d_pk, &h->st.d_woff, &h->st.d_qual, &h->st.d_off, &h->st.d_strand, &h->st.d_sid}; for (DBuf* b : sh) b->release(); }
   if (h->stream_up) { (void)hipStreamSynchronize(h->stream_up); (void)hipStreamDestroy(h->stream_up); }
@@ -308,7 +311,7 @@ static C3Params dev_params(const c3_config& c) {
   p.band_b = c.poa_band_b; p.band_f = c.poa_band_f;
   p.pol_match = c.pol_match; p.pol_mismatch = c.pol_mismatch; p.pol_gap = c.pol_gap; p.pol_window = c.pol_window; p.pol_q = c.pol_q;
   p.dang_band = c.dang_band;
-  p.zero = c.zero; p.zr_match = 2; p.zr_mismatch = 4; p.zr_gapo = 4; p.zr_gape = 2; p.zr_min_score = 80; p.zr_max_cells = 16 << 20;
+  p.zero = c.zero; p.zr_match = 2; p.zr_mismatch = 4; p.zr_gapo = 4; p.zr_gape = 2; p.zr_min_score = 80; p.zr_max_cells = (int)c.zero_max_cells;
   return p;
 }
 
@@ -489,31 +492,62 @@ static void fill_zero_args(c3_handle* h, ZeroArgs& z, int nz) {
 }
 
 // zero-repeat rescue, first half (bin/determine_consensus.py:14-18,106-128): reads whose split kept no
-// subread but has both dangling pieces get their overlap located and become 2-subread POA jobs
+// subread but has both dangling pieces get their overlap located and become 2-subread POA jobs.  k_zero takes the pairs
+// its LDS rows and direction matrix hold; every other pair within zero_max_cells goes to k_zero_long.
+static const long long ZL_BUDGET = 1LL << 30;    // k_zero_long scratch of all slots together (at least one slot)
 static int run_zero(c3_handle* h) {
   h->zwork.clear();
   HIPCHK(h->d_zflag.ensure((size_t)h->n + 16));
   HIPCHK(hipMemsetAsync(h->d_zflag.p, 0, (size_t)h->n, h->stream));
   if (!h->cfg.zero || h->injected) return 0;
-  long long dmax = 0;
+  // test hooks: C3_DEBUG_ZERO_LONG=1 sends every eligible read to k_zero_long, C3_DEBUG_ZERO_K=<n> sets its checkpoint interval
+  const char* ev_long = getenv("C3_DEBUG_ZERO_LONG");
+  const bool force_long = ev_long && atoi(ev_long) != 0;
+  const char* ev_k = getenv("C3_DEBUG_ZERO_K");
+  const int zk = (ev_k && atoi(ev_k) > 0) ? atoi(ev_k) : 256;
+  long long dmax = 0, smax = 0;
+  std::vector<int> zlong;
   for (int i = 0; i < h->n; ++i) {
     const Summary& s = h->sum[i];
-    if (s.status == C3_ST_NO_CONSENSUS && s.n_sub == 0 && s.front > 0 && s.tail > 0 && s.front <= 4096 &&
-        (long long)s.front * s.tail <= (16 << 20)) {
+    if (s.status != C3_ST_NO_CONSENSUS || s.n_sub != 0 || s.front <= 0 || s.tail <= 0) continue;
+    const long long cells = (long long)s.front * s.tail;
+    if (cells > h->cfg.zero_max_cells) continue;
+    if (!force_long && s.front <= 4096 && cells <= (16 << 20)) {
       h->zwork.push_back(i);
       dmax = std::max(dmax, (long long)(s.front + 1) * (s.tail + 1));
+    } else {
+      zlong.push_back(i);
+      smax = std::max(smax, c3_zl_layout(s.front, s.tail, zk).total);
     }
   }
-  const int nz = (int)h->zwork.size();
+  const int ns = (int)h->zwork.size(), nl = (int)zlong.size();
+  h->zwork.insert(h->zwork.end(), zlong.begin(), zlong.end());
+  const int nz = ns + nl;
   if (nz == 0) return 0;
-  const int grid = std::min(nz, 512);
   HIPCHK(h->d_zwork.ensure(sizeof(int) * (size_t)nz)); HIPCHK(h->d_zinfo.ensure(sizeof(int4) * (size_t)h->n));
-  HIPCHK(h->s_zero_d.ensure((size_t)dmax * grid + 64));
+  if (ns) {
+    const int grid = std::min(ns, 512);
+    HIPCHK(h->s_zero_d.ensure((size_t)dmax * grid + 64));
+  }
+  int grid_l = 0;
+  if (nl) {
+    grid_l = (int)std::min<long long>(std::min(nl, 2 * h->n_cus), std::max(1LL, ZL_BUDGET / smax));
+    HIPCHK(h->s_zero_l.ensure((size_t)smax * grid_l));
+  }
   HIPCHK(hipMemcpyAsync(h->d_zwork.p, h->zwork.data(), sizeof(int) * (size_t)nz, hipMemcpyHostToDevice, h->stream));
-  ZeroArgs z; fill_zero_args(h, z, nz); z.dcap = dmax;
-  DBG("zero: nz=%d grid=%d dmax=%lld\n", nz, grid, dmax);
-  c3k_launch_zero(&z, grid, h->stream);
-  HIPCHK(hipGetLastError());
+  if (ns) {
+    ZeroArgs z; fill_zero_args(h, z, ns); z.dcap = dmax;
+    DBG("zero: nz=%d grid=%d dmax=%lld\n", ns, std::min(ns, 512), dmax);
+    c3k_launch_zero(&z, std::min(ns, 512), h->stream);
+    HIPCHK(hipGetLastError());
+  }
+  if (nl) {
+    ZeroArgs z; fill_zero_args(h, z, nl);
+    z.work = h->d_zwork.as<int>() + ns; z.S = h->s_zero_l.as<uint8_t>(); z.scap = smax; z.zk = zk;
+    DBG("zero long: nz=%d grid=%d slot=%lld K=%d\n", nl, grid_l, smax, zk);
+    c3k_launch_zero_long(&z, grid_l, h->stream);
+    HIPCHK(hipGetLastError());
+  }
   { int r_ = copy_summary(h); DBG("zero done\n"); return r_; }              // the rescued reads now carry 2 pseudo-subreads
 }
 

@@ -66,4 +66,17 @@ struct ZeroArgs {
   uint8_t* D; long long dcap;           // [grid][dcap] direction bytes
   int4* zinfo; uint8_t* zflag;          // per read: r_st, r_en, q_st, q_en; rescue in progress / done
   const uint8_t* draft; char* cons;
+  uint8_t* S; long long scap; int zk;   // k_zero_long: [grid][scap] scratch (checkpoint rows, direction block, row carries); checkpoint interval
 };
+
+// k_zero_long scratch of one read (d0 = n0 columns, d1 = n1 rows, checkpoint every K rows), laid out from the slot base:
+// checkpoint rows ceil(n1/K) * (n0+1) * int2 (H, E) | direction block min(K, n1) * (n0+1) bytes | row carries n1 * 3 ints
+struct ZlLayout { long long ck, dir, car, total; };
+__host__ __device__ inline ZlLayout c3_zl_layout(long long n0, long long n1, long long K) {
+  ZlLayout l;
+  l.ck = 0;
+  l.dir = (n1 + K - 1) / K * (n0 + 1) * 8;
+  l.car = (l.dir + (n1 < K ? n1 : K) * (n0 + 1) + 15) & ~15LL;
+  l.total = (l.car + n1 * 12 + 255) & ~255LL;
+  return l;
+}

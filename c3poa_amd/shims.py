@@ -81,7 +81,8 @@ def determine_consensus(args, read, subreads, sub_qual, dangling_subreads, qual_
                 from .records import zero_repeat_records
                 with open(subread_file, "a+") as fh:
                     fh.write(zero_repeat_records(name, dangling_subreads, qual_dangling_subreads))
-            h = _handle(mdistcutoff=getattr(args, "mdistcutoff", 500))
+            h = _handle(mdistcutoff=getattr(args, "mdistcutoff", 500),
+                        zero_max_cells=int(getattr(args, "zero_max_cells", _lib.ZERO_MAX_CELLS)))
             cons = h.zero_repeats(dangling_subreads[0], qual_dangling_subreads[0], dangling_subreads[1],
                                   qual_dangling_subreads[1], getattr(args, "mdistcutoff", 500))
             if cons:

@@ -208,7 +208,8 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
 
         try:
             ts = time.perf_counter()
-            h = _lib.Handle(device=dev, mdistcutoff=args.mdistcutoff, zero=1 if getattr(args, "zero", True) else 0)
+            h = _lib.Handle(device=dev, mdistcutoff=args.mdistcutoff, zero=1 if getattr(args, "zero", True) else 0,
+                            zero_max_cells=int(getattr(args, "zero_max_cells", _lib.ZERO_MAX_CELLS)))
             h.set_splints([splint_dict[n][0] for n in splint_names])
             with lock:
                 t["setup"] += time.perf_counter() - ts

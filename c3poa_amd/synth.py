@@ -72,6 +72,24 @@ def make_read(rng, splint, insert_len, n, k0, k1):
     return seq.decode(), qual.decode(), strand, truth
 
 
+def make_zero_read(rng, splint, insert_len, a, b, err=True, strand=None):
+    """A read with one splint and no full subread: ins[a:] + splint + ins[:b], whose two dangling pieces overlap
+    on ins[a:b] when a < b (the zero-repeat rescue, bin/determine_consensus.py:106-136).  strand None: either,
+    at random.  returns (seq str, qual str, strand '+'/'-', truth str in read orientation)"""
+    ins = _ACGT[rng.integers(0, 4, insert_len)].tobytes().decode()
+    clean = ins[a:] + splint + ins[:b]
+    h = len(splint) // 2
+    truth = splint[h:] + ins + splint[:h]
+    if strand is None:
+        strand = "-" if rng.random() < 0.5 else "+"
+    if strand == "-":
+        clean, truth = revcomp(clean), revcomp(truth)
+    if not err:
+        return clean, "I" * len(clean), strand, truth
+    seq, qual = _mutate(rng, np.frombuffer(clean.encode(), dtype=np.uint8))
+    return seq.decode(), qual.decode(), strand, truth
+
+
 def generate(cfg="cfg2", n_reads=None, seed=None, splint=SPLINT1, start=0):
     """Yield (name, seq, qual, strand, truth).  `start` skips that many reads of the stream
     deterministically (each read has its own child RNG) so shards can be generated independently."""

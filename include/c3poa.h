@@ -58,6 +58,8 @@ typedef struct {
   int dang_band;                                /* half band of the dangling-piece extension, 128 */
   int slots_poa, slots_win;                     /* resident wave slots (0 = auto) */
   int zero;                                     /* args.zero (C3POa.py:48-49): attempt the zero-repeat rescue (default 1) */
+  int64_t zero_max_cells;                       /* zero-repeat rescue only for pieces with front * tail <= this (default 16777216;
+                                                   1 .. 2147483647, else c3_create fails with C3_E_ARG).  The reference has no cap. */
 } c3_config;
 
 typedef struct {
