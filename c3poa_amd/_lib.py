@@ -20,7 +20,7 @@ EXPORTS = ["c3_default_config", "c3_version", "c3_device_count", "c3_warm_device
            "c3_fetch_track", "c3_fetch_smoothed", "c3_fetch_raw_peaks", "c3_fetch_draft", "c3_fetch_msa2",
            "c3_call_peaks", "c3_poa_msa", "c3_pairwise_consensus", "c3_determine_consensus", "c3_zero_repeats", "c3_scan_splints",
            "c3_reader_open", "c3_reader_open_range", "c3_reader_close", "c3_reader_error", "c3_reader_names_only", "c3_reader_next", "c3_reader_next_set", "c3_reader_noqual", "c3_reader_reserved_bytes", "c3_reader_range_lost", "c3_write_group",
-           "c3_scan_adapters", "c3_match_index", "c3_match_index_batch",
+           "c3_scan_adapters", "c3_match_index", "c3_match_index_batch", "c3_demux_indexes", "c3_demux_host",
            "c3_assign_open", "c3_assign_close", "c3_assign_batch", "c3_assign_seen", "c3_write_splint_psl",
            "c3_host_alloc", "c3_host_free", "c3_writer_reset"]
 
@@ -109,6 +109,8 @@ def load():
     lib.c3_scan_adapters.argtypes = [vp, vp]
     lib.c3_match_index.argtypes = [cp, C.c_int, C.c_int, cp, vp]
     lib.c3_match_index_batch.argtypes = [vp, C.c_int, vp, vp, C.c_int, cp, vp, vp]
+    lib.c3_demux_indexes.argtypes = [vp, C.c_int, vp, C.c_int, cp, vp, C.c_int, cp, vp, vp, vp]
+    lib.c3_demux_host.argtypes = [C.c_int, vp, C.c_int, cp, vp, C.c_int, cp, vp, vp, vp]
     lib.c3_assign_open.argtypes = [cp, C.c_int, C.POINTER(cp), C.POINTER(vp)]
     lib.c3_assign_close.argtypes = [vp]
     lib.c3_assign_close.restype = None
@@ -397,6 +399,13 @@ class Handle:
         self._chk(self.lib.c3_match_index_batch(self.h, n, buf.ctypes.data, lens.ctypes.data, len(bs), b"".join(bs), off.ctypes.data, out.ctypes.data))
         return out
 
+    def demux_indexes(self, heads, set_a, set_b, return_dist=False):
+        """c3_demux_indexes (k_demux): winners (n, 2) int32 of index sets A and B (index number or -1) for every head
+        (300 bytes each, see _demux_args), and with return_dist the (n, len(A) + len(B)) uint8 minimum distances"""
+        args, keep, res = _demux_args(heads, set_a, set_b, return_dist)
+        self._chk(self.lib.c3_demux_indexes(self.h, *args))
+        return res
+
     def pairwise_consensus(self, msa_rows, subreads, quals):
         """pairwise_consensus(msa_rows, subreads, quals) of bin/consensus.py:76"""
         ra, rb = _b(msa_rows[0]), _b(msa_rows[1])
@@ -438,6 +447,45 @@ def match_index(seq, index_seqs):
     np.cumsum([len(b) for b in bs], out=off[1:])
     sq = _b(seq)
     return int(load().c3_match_index(sq, len(sq), len(bs), b"".join(bs), off.ctypes.data))
+
+
+DEMUX_HEAD = 300        # C3_DEMUX_HEAD
+
+
+def _demux_args(heads, set_a, set_b, return_dist):
+    """heads: (n, 300) uint8 array or a sequence of 300-byte str / bytes; sets: sequences of str / bytes.
+    Returns the ctypes arguments after the handle, the arrays they point into, and the result."""
+    if isinstance(heads, np.ndarray):
+        h = np.ascontiguousarray(heads, dtype=np.uint8)
+    else:
+        bs = [_b(x) for x in heads]
+        if any(len(x) != DEMUX_HEAD for x in bs):
+            raise ValueError("every head must be %d bytes" % DEMUX_HEAD)
+        h = np.frombuffer(b"".join(bs), dtype=np.uint8)
+    h = h.reshape(-1, DEMUX_HEAD)
+    n = h.shape[0]
+    sets = []
+    for s in (set_a, set_b):
+        bs = [_b(x) for x in s]
+        off = np.zeros(len(bs) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in bs], out=off[1:])
+        sets += [len(bs), b"".join(bs), off]
+    win = np.zeros((n, 2), dtype=np.int32)
+    dist = np.zeros((n, sets[0] + sets[3]), dtype=np.uint8) if return_dist else None
+    res = (win, dist) if return_dist else win
+    args = (n, h.ctypes.data, sets[0], sets[1], sets[2].ctypes.data, sets[3], sets[4], sets[5].ctypes.data, win.ctypes.data,
+            dist.ctypes.data if return_dist else None)
+    return args, (h, sets), res
+
+
+def demux_host(heads, set_a, set_b, return_dist=False):
+    """c3_demux_host: the host statement of Handle.demux_indexes (same arguments and results)"""
+    lib = load()
+    args, keep, res = _demux_args(heads, set_a, set_b, return_dist)
+    rc = lib.c3_demux_host(*args)
+    if rc < 0:
+        raise C3Error("c3 error %d: %s" % (rc, lib.c3_last_error(None).decode()))
+    return res
 
 
 def device_count():

@@ -14,6 +14,7 @@ extern "C" void c3k_launch_conk(const ConkArgs*, int, int, int, hipStream_t);
 extern "C" void c3k_launch_adapter(const AdapterArgs*, int, hipStream_t);
 extern "C" void c3k_launch_pairwise(const uint8_t*, int, const uint8_t*, int, const uint8_t*, int, uint8_t*, uint8_t*, int*, hipStream_t);
 extern "C" void c3k_launch_match_index(const char*, const int*, int, int, const char*, const long long*, int*, hipStream_t);
+extern "C" void c3k_launch_demux(const uint8_t*, int, const uint8_t*, int, int, int, int32_t*, uint8_t*, hipStream_t);
 extern "C" void c3k_launch_peaks(const PeaksArgs*, int, hipStream_t);
 extern "C" int c3k_peaks_blocks_per_cu(void);
 extern "C" void c3k_launch_poa(const PoaArgs*, int, int, int, hipStream_t);
@@ -171,6 +172,7 @@ struct c3_handle {
   DBuf s_win_i, s_win_nk, s_win_h, s_win_d, s_win_b, s_win_sc, s_win_desc, s_win_h2, s_win_d2, d_wovf;
   DBuf s_zero_d, d_zinfo, d_zflag, d_zwork; std::vector<int> zwork;  // zero-repeat rescue: k_zero direction bytes, per-read records, work list
   DBuf s_zero_l;                                                      // k_zero_long slots
+  DBuf d_dmx_heads, d_dmx_meta, d_dmx_out;                            // demultiplexer: heads, Peq / lengths / byte codes, winners + distances
   std::vector<Summary> sum; std::vector<int> work;
   int res_prefix = 0;            // entries of peaks[] / sub_beg[] / sub_end[] that any read of the resident batch uses (0: unknown)
   int peaks_grid = 0; bool debug_msa = false; bool injected = false;
@@ -210,6 +212,7 @@ extern "C" int c3_warm_device(int device) {
 
 static thread_local std::string g_create_err;
 extern "C" const char* c3_last_error(const c3_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
+void c3_set_host_error(const char* msg) { g_create_err = msg; }     // handle-free calls (c3_demux_host) report here
 
 extern "C" int c3_create(const c3_config* cfg, c3_handle** out) {
   if (!cfg || !out) return C3_E_ARG;
@@ -258,7 +261,8 @@ extern "C" void c3_destroy(c3_handle* h) {
                  &h->d_info, &h->d_track, &h->d_draft, &h->d_tpos, &h->d_cons, &h->d_counter, &h->d_raw, &h->d_nraw, &h->d_sum,
                  &h->d_work, &h->d_bufA, &h->d_bufB, &h->d_cand, &h->d_cst, &h->d_msa, &h->d_msa_off, &h->d_msa_len,
                  &h->s_poa_i, &h->s_poa_nk, &h->s_poa_cells, &h->s_poa_b, &h->s_poa_sc, &h->s_poa_desc, &h->s_poa_jump, &h->s_poa_path, &h->d_overflow, &h->s_eH, &h->s_eD, &h->s_lw, &h->d_wrec,
-                 &h->d_wlay, &h->d_wbase, &h->d_wout, &h->s_win_i, &h->s_win_nk, &h->s_win_h, &h->s_win_d, &h->s_win_b, &h->s_win_sc, &h->s_win_desc, &h->s_zero_d, &h->s_zero_l, &h->d_zinfo, &h->d_zflag, &h->d_zwork, &h->d_gather, &h->d_gather_off};
+                 &h->d_wlay, &h->d_wbase, &h->d_wout, &h->s_win_i, &h->s_win_nk, &h->s_win_h, &h->s_win_d, &h->s_win_b, &h->s_win_sc, &h->s_win_desc, &h->s_zero_d, &h->s_zero_l, &h->d_zinfo, &h->d_zflag, &h->d_zwork, &h->d_gather, &h->d_gather_off,
+                 &h->d_dmx_heads, &h->d_dmx_meta, &h->d_dmx_out};
   for (DBuf* b : all) b->release();
   { DBuf* sh[] = {&h->st.d_ascii, &h->st.d_pk, &h->st.d_woff, &h->st.d_qual, &h->st.d_off, &h->st.d_strand, &h->st.d_sid}; for (DBuf* b : sh) b->release(); }
   if (h->stream_up) { (void)hipStreamSynchronize(h->stream_up); (void)hipStreamDestroy(h->stream_up); }
@@ -1182,6 +1186,44 @@ extern "C" int c3_match_index_batch(c3_handle* h, int n, const char* pieces, con
   HIPCHK(hipMemcpyAsync(out, dout.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   dp.release(); dl.release(); di.release(); doff.release(); dout.release();
+  return C3_E_OK;
+}
+
+// sample demultiplexer (paper/Demultiplex_R2C2_reads.py, demultiplex): k_demux over n heads of 300 bytes; the host
+// statement is c3_demux_host (c3_io.cpp), which also holds the checks both share (c3_demux_prepare).
+int c3_demux_prepare(int n_a, const char* a_cat, const int64_t* a_off, int n_b, const char* b_cat, const int64_t* b_off,
+                     uint8_t* tab, int* n_codes, const char** msg);
+extern "C" int c3_demux_indexes(c3_handle* h, int n, const char* heads, int n_a, const char* a_cat, const int64_t* a_off,
+                                int n_b, const char* b_cat, const int64_t* b_off, int32_t* win, uint8_t* dist) {
+  if (!h) return C3_E_ARG;
+  if (n < 0 || (n > 0 && (!heads || !win))) return c3_fail(h, C3_E_ARG, "heads / win missing");
+  uint8_t tab[256]; int K = 0; const char* msg = "";
+  const int rc = c3_demux_prepare(n_a, a_cat, a_off, n_b, b_cat, b_off, tab, &K, &msg);
+  if (rc != C3_E_OK) return c3_fail(h, rc, msg);
+  if (n == 0) return C3_E_OK;
+  // meta = Peq [I][K+1] words (bit j of Peq[k][c]: byte j of index k has code c), lengths [I] words, byte codes [256]
+  const int I = n_a + n_b, K1 = K + 1;
+  std::vector<uint32_t> meta((size_t)I * K1 + I + 64, 0u);
+  for (int k = 0; k < I; ++k) {
+    const char* cat = k < n_a ? a_cat : b_cat;
+    const int64_t* off = k < n_a ? a_off + k : b_off + (k - n_a);
+    const int m = (int)(off[1] - off[0]);
+    for (int j = 0; j < m; ++j) meta[(size_t)k * K1 + tab[(uint8_t)cat[off[0] + j]]] |= 1u << j;
+    meta[(size_t)I * K1 + k] = (uint32_t)m;
+  }
+  memcpy(&meta[(size_t)I * K1 + I], tab, 256);
+  const size_t hb = (size_t)n * C3_DEMUX_HEAD, wb = sizeof(int32_t) * 2 * (size_t)n, db = dist ? (size_t)n * I : 0;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(h->d_dmx_heads.ensure(hb)); HIPCHK(h->d_dmx_meta.ensure(sizeof(uint32_t) * meta.size())); HIPCHK(h->d_dmx_out.ensure(wb + db));
+  HIPCHK(hipMemcpyAsync(h->d_dmx_heads.p, heads, hb, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->d_dmx_meta.p, meta.data(), sizeof(uint32_t) * meta.size(), hipMemcpyHostToDevice, h->stream));
+  uint8_t* d_out = h->d_dmx_out.as<uint8_t>();
+  c3k_launch_demux(h->d_dmx_heads.as<uint8_t>(), n, h->d_dmx_meta.as<uint8_t>(), n_a, n_b, K1, (int32_t*)d_out,
+                   dist ? d_out + wb : nullptr, h->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(win, d_out, wb, hipMemcpyDeviceToHost, h->stream));
+  if (dist) HIPCHK(hipMemcpyAsync(dist, d_out + wb, db, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));      // meta is a host vector of this frame
   return C3_E_OK;
 }
 

@@ -787,6 +787,63 @@ extern "C" int c3_match_index(const char* seq, int n, int n_idx, const char* idx
   return -1;
 }
 
+// ---- sample demultiplexer (paper/Demultiplex_R2C2_reads.py, demultiplex) ------------------------------------------
+// c3_demux_prepare checks the two index sets for both entry points and builds the byte -> code table of k_demux: the
+// distinct bytes of all indexes get codes 1..K in byte order, every other byte 0 (which matches no index position).
+void c3_set_host_error(const char* msg);        // c3_api.hip: the text of c3_last_error(NULL)
+
+int c3_demux_prepare(int n_a, const char* a_cat, const int64_t* a_off, int n_b, const char* b_cat, const int64_t* b_off,
+                     uint8_t* tab, int* n_codes, const char** msg) {
+  const int ns[2] = {n_a, n_b}; const char* cats[2] = {a_cat, b_cat}; const int64_t* offs[2] = {a_off, b_off};
+  bool seen[256] = {};
+  for (int s = 0; s < 2; ++s) {
+    if (ns[s] < 2) { *msg = "an index set needs at least 2 indexes (the reference compares the best with the runner-up)"; return C3_E_ARG; }
+    if (ns[s] > C3_DEMUX_MAX_IDX) { *msg = "more than 128 indexes in one set"; return C3_E_LIMIT; }
+    if (!offs[s] || offs[s][0] != 0) { *msg = "index offsets missing or not starting at 0"; return C3_E_ARG; }
+    for (int k = 0; k < ns[s]; ++k) {
+      const int64_t len = offs[s][k + 1] - offs[s][k];
+      if (len < 0) { *msg = "index offsets decrease"; return C3_E_ARG; }
+      if (len > C3_DEMUX_MAX_LEN) { *msg = "index longer than 32 bytes"; return C3_E_LIMIT; }
+      if (len > 0 && !cats[s]) { *msg = "index bytes missing"; return C3_E_ARG; }
+      for (int64_t j = 0; j < len; ++j) seen[(uint8_t)cats[s][offs[s][k] + j]] = true;
+    }
+  }
+  int K = 0;
+  for (int b = 0; b < 256; ++b) tab[b] = seen[b] ? (uint8_t)++K : 0;
+  if (K > C3_DEMUX_MAX_BYTES) { *msg = "more than 31 distinct bytes over the index sets"; return C3_E_LIMIT; }
+  *n_codes = K;
+  return C3_E_OK;
+}
+
+// Host statement of k_demux: textbook DP for every window (head[i : i+m], i < 300 - m) of every index.
+extern "C" int c3_demux_host(int n, const char* heads, int n_a, const char* a_cat, const int64_t* a_off,
+                             int n_b, const char* b_cat, const int64_t* b_off, int32_t* win, uint8_t* dist) {
+  if (n < 0 || (n > 0 && (!heads || !win))) { c3_set_host_error("heads / win missing"); return C3_E_ARG; }
+  uint8_t tab[256]; int K = 0; const char* msg = "";
+  const int rc = c3_demux_prepare(n_a, a_cat, a_off, n_b, b_cat, b_off, tab, &K, &msg);
+  if (rc != C3_E_OK) { c3_set_host_error(msg); return rc; }
+  const int ns[2] = {n_a, n_b}; const char* cats[2] = {a_cat, b_cat}; const int64_t* offs[2] = {a_off, b_off};
+  std::vector<int> d((size_t)std::max(n_a, n_b));
+  for (int r = 0; r < n; ++r) {
+    const char* head = heads + (size_t)r * C3_DEMUX_HEAD;
+    for (int s = 0; s < 2; ++s) {
+      for (int k = 0; k < ns[s]; ++k) {
+        const int m = (int)(offs[s][k + 1] - offs[s][k]);
+        int best = m;                                           // an empty index: distance 0
+        for (int i = 0; i < C3_DEMUX_HEAD - m; ++i) best = std::min(best, edit_distance(cats[s] + offs[s][k], head + i, m));
+        d[(size_t)k] = best;
+        if (dist) dist[(size_t)r * (n_a + n_b) + (s ? n_a : 0) + k] = (uint8_t)best;
+      }
+      int i0 = 0;                                               // first entry of the stable sort; the runner-up's distance
+      for (int k = 1; k < ns[s]; ++k) if (d[(size_t)k] < d[(size_t)i0]) i0 = k;
+      int d1 = INT32_MAX;
+      for (int k = 0; k < ns[s]; ++k) if (k != i0) d1 = std::min(d1, d[(size_t)k]);
+      win[2 * (size_t)r + s] = (d[(size_t)i0] < 4 && d[(size_t)i0] < d1 - 1) ? i0 : -1;
+    }
+  }
+  return C3_E_OK;
+}
+
 // ---- splint assignment from the PSL (bin/preprocess.py:22-45) without per-read Python objects ---------------------
 // Rows with qBaseInsert (col 5) < 50 and matches (col 0) > 50 count; per read the row with the most matches wins, the
 // earliest row on ties (Python's stable sort with reverse=True keeps the first of equal keys); every splint named by a

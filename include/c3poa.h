@@ -303,6 +303,27 @@ int c3_match_index_batch(c3_handle* h, int n, const char* pieces, const int32_t*
  * -1 for '-'.  Host code. */
 int c3_match_index(const char* seq, int n, int n_idx, const char* idx_cat, const int64_t* idx_off);
 
+/* Sample demultiplexer (paper/Demultiplex_R2C2_reads.py, demultiplex): per read and per index set (A = Nextera,
+ * B = TSO), the minimum Levenshtein distance of every index (length m) to head[i : i+m] for i in 0 .. 299-m (the window
+ * at 300-m is not searched); sets are decided separately: stable sort by distance, the first index wins when its
+ * distance is < 4 and the runner-up's is more than 1 further away.  Byte-exact (case-sensitive, N matches only N).
+ *   heads: n slots of C3_DEMUX_HEAD bytes (the first 300 bases of reads longer than 300; shorter reads are not searched)
+ *   set A: n_a indexes, a_off[n_a+1] into a_cat; set B likewise.  2 .. C3_DEMUX_MAX_IDX indexes per set, each of
+ *          0 .. C3_DEMUX_MAX_LEN bytes (an empty index has distance 0), at most C3_DEMUX_MAX_BYTES distinct bytes over
+ *          both sets; otherwise C3_E_LIMIT / C3_E_ARG with a c3_last_error text
+ *   win[2n]: (A, B) winning index number per read (file order within the set) or -1
+ *   dist[n * (n_a + n_b)]: minimum distances, A's columns then B's, or NULL to skip
+ * c3_demux_indexes runs on the handle's device (k_demux); c3_demux_host is its host statement (textbook DP over every
+ * window) and reports its error text through c3_last_error(NULL). */
+#define C3_DEMUX_HEAD 300
+#define C3_DEMUX_MAX_IDX 128
+#define C3_DEMUX_MAX_LEN 32
+#define C3_DEMUX_MAX_BYTES 31
+int c3_demux_indexes(c3_handle* h, int n, const char* heads, int n_a, const char* a_cat, const int64_t* a_off,
+                     int n_b, const char* b_cat, const int64_t* b_off, int32_t* win, uint8_t* dist);
+int c3_demux_host(int n, const char* heads, int n_a, const char* a_cat, const int64_t* a_off,
+                  int n_b, const char* b_cat, const int64_t* b_off, int32_t* win, uint8_t* dist);
+
 #ifdef __cplusplus
 }
 #endif
