@@ -49,6 +49,9 @@ def parse_args(argv=None):
     parser.add_argument("--blatThreads", "-b", action="store_true", default=False, help="Accepted for compatibility.")
     parser.add_argument("--compress_output", "-co", action="store_true", default=False,
                         help="Use to compress (gzip) both the consensus fasta and subread fastq output files.")
+    parser.add_argument("--consensus-fastq", dest="consensus_fastq", action="store_true", default=False,
+                        help="Also write <splint>/R2C2_Consensus.fastq: every consensus with per-base support QVs computed on "
+                             "the GPU (not calibrated error probabilities; see DESIGN.md). Off by default.")
     parser.add_argument("--version", "-v", action="version", version=VERSION, help="Prints the C3POa version.")
     if argv is None and len(sys.argv) == 1:
         parser.print_help()

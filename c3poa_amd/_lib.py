@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("C3POA_LIB", os.path.join(_HERE, "lib", "libc3poa_hip.
 MAX_PEAKS = 256
 
 STAGE_CONK, STAGE_PEAKS, STAGE_POA, STAGE_POLISH, STAGES_ALL = 1, 2, 4, 8, 15
+STAGE_QV = 16                   # per-base consensus QVs (k_qv), opt-in: c3_batch_run(h, STAGES_ALL | STAGE_QV)
+QV_GLOBAL, QV_ANCHOR_START, QV_ANCHOR_END = 0, 1, 2
 ST_OK, ST_NOT_ASSIGNED, ST_NO_PEAKS, ST_NO_CONSENSUS, ST_TOO_SHORT, ST_LIMIT = range(6)
 
 EXPORTS = ["c3_default_config", "c3_version", "c3_device_count", "c3_warm_device", "c3_create", "c3_destroy", "c3_last_error", "c3_set_splints",
@@ -22,7 +24,9 @@ EXPORTS = ["c3_default_config", "c3_version", "c3_device_count", "c3_warm_device
            "c3_reader_open", "c3_reader_open_range", "c3_reader_close", "c3_reader_error", "c3_reader_names_only", "c3_reader_next", "c3_reader_next_set", "c3_reader_noqual", "c3_reader_reserved_bytes", "c3_reader_range_lost", "c3_write_group",
            "c3_scan_adapters", "c3_match_index", "c3_match_index_batch", "c3_demux_indexes", "c3_demux_host",
            "c3_assign_open", "c3_assign_close", "c3_assign_batch", "c3_assign_seen", "c3_write_splint_psl",
-           "c3_host_alloc", "c3_host_free", "c3_writer_reset"]
+           "c3_host_alloc", "c3_host_free", "c3_writer_reset",
+           "c3_batch_results_fetch_qv", "c3_batch_results_qv", "c3_batch_qv_timing", "c3_consensus_qv", "c3_consensus_qv_host",
+           "c3_write_consensus_fastq"]
 
 
 ZERO_MAX_CELLS = 16777216       # c3_default_config's zero_max_cells: largest front * tail the zero-repeat rescue takes
@@ -58,6 +62,10 @@ class Timing(C.Structure):
                [(n, C.c_int64) for n in ("n_reads", "n_bases", "n_windows", "cells_conk", "cells_poa", "cells_polish", "n_poa_redo")] + \
                [(n, C.c_float) for n in ("ms_wall", "ms_host_worklist", "ms_alloc", "ms_host_gap")] + \
                [(n, C.c_int64) for n in ("cells_polish_computed", "n_band_layers", "n_band_fallback", "n_band_mismatch", "n_win_redo", "n_poa_redo16")]
+
+
+class QvTiming(C.Structure):
+    _fields_ = [("ms_qv", C.c_float)] + [(n, C.c_int64) for n in ("n_reads", "n_pieces", "n_skipped", "band_cells", "edge_hits")]
 
 
 class HostBatchStruct(C.Structure):
@@ -137,6 +145,12 @@ def load():
     lib.c3_write_group.argtypes = [C.POINTER(HostBatchStruct), vp, vp, vp, vp, C.c_int, C.POINTER(cp), C.POINTER(cp), C.c_int]
     lib.c3_determine_consensus.argtypes = [vp, C.c_int, C.POINTER(cp), C.POINTER(cp), ip, cp, cp, C.c_int,
                                            cp, cp, C.c_int, vp, C.c_int, ip, vp, C.c_int, ip]
+    lib.c3_batch_results_fetch_qv.argtypes = [vp, vp, vp, C.c_int64, i64p, vp]
+    lib.c3_batch_results_qv.argtypes = [vp, vp, vp, C.c_int64, i64p, vp]
+    lib.c3_batch_qv_timing.argtypes = [vp, C.POINTER(QvTiming)]
+    lib.c3_consensus_qv.argtypes = [vp, cp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    lib.c3_consensus_qv_host.argtypes = [cp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    lib.c3_write_consensus_fastq.argtypes = [C.POINTER(HostBatchStruct), vp, vp, vp, vp, vp, C.c_int, C.POINTER(cp), C.c_int]
     _lib = lib
     return lib
 
@@ -267,9 +281,18 @@ class Handle:
                                           sid.ctypes.data if sid is not None else None, pb.strand.ctypes.data))
         self._staged = (pb.n, pb.off, pb)
 
-    def run(self, stages=STAGES_ALL):
-        self._chk(self.lib.c3_batch_run(self.h, stages))
+    def run(self, stages=STAGES_ALL, qv=False):
+        """qv=True adds STAGE_QV (per-base consensus QVs after the polish)"""
+        self._chk(self.lib.c3_batch_run(self.h, stages | (STAGE_QV if qv else 0)))
         self.last_timing = self.timing()         # c3_batch_commit clears the library's copy
+        if qv:
+            self.last_qv_timing = self.qv_timing()
+
+    def qv_timing(self):
+        """c3_batch_qv_timing: k_qv figures of the last run with STAGE_QV"""
+        t = QvTiming()
+        self._chk(self.lib.c3_batch_qv_timing(self.h, C.byref(t)))
+        return {f[0]: getattr(t, f[0]) for f in QvTiming._fields_}
 
     def results_raw(self, into=None):
         """(results structured array, consensus byte buffer, cons_off[n+1]) without building Python strings.
@@ -295,9 +318,26 @@ class Handle:
             raise C3Error("c3_batch_results_fetch failed (%d)" % rc)
         return res, buf, coff
 
-    def results(self, with_consensus=True):
+    def results_fetch_qv(self, into, shape):
+        """results_fetch + the QV bytes (c3_batch_results_fetch_qv): (res, cons bytes, cons_off, QV bytes at the same offsets)"""
+        res, buf, coff = into.fit(*shape)
+        qv = into.fit_qv(shape[1])
+        rc = self.lib.c3_batch_results_fetch_qv(self.h, res.ctypes.data, buf.ctypes.data, len(buf), coff.ctypes.data, qv.ctypes.data)
+        if rc != 0:
+            raise C3Error("c3_batch_results_fetch_qv failed (%d)" % rc)
+        return res, buf, coff, qv
+
+    def results(self, with_consensus=True, qv=False):
+        """(records, consensus strings); qv=True: (records, consensus strings, QV strings) via c3_batch_results_qv"""
         res = np.zeros(self.n, dtype=RESULT_DTYPE)
         coff = np.zeros(self.n + 1, dtype=np.int64)
+        if qv:
+            cap = int(self.off[-1]) + 16
+            buf, qbuf = np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype=np.uint8)
+            self._chk(self.lib.c3_batch_results_qv(self.h, res.ctypes.data, buf.ctypes.data, cap, coff.ctypes.data, qbuf.ctypes.data))
+            raw, qraw = buf.tobytes(), qbuf.tobytes()
+            return (res, [raw[coff[i]:coff[i + 1]].decode() for i in range(self.n)],
+                    [qraw[coff[i]:coff[i + 1]].decode() for i in range(self.n)])
         if not with_consensus:
             self._chk(self.lib.c3_batch_results(self.h, res.ctypes.data, None, 0, coff.ctypes.data))
             return res, None
@@ -406,6 +446,13 @@ class Handle:
         self._chk(self.lib.c3_demux_indexes(self.h, *args))
         return res
 
+    def consensus_qv(self, cons, pieces):
+        """c3_consensus_qv (k_qv): Phred+33 QV string of `cons` from pieces = [(seq, qual, mode)], mode QV_GLOBAL /
+        QV_ANCHOR_START / QV_ANCHOR_END"""
+        args, keep = _qv_args(cons, pieces)
+        self._chk(self.lib.c3_consensus_qv(self.h, *args))
+        return keep[-1].raw[:len(keep[0])].decode()
+
     def pairwise_consensus(self, msa_rows, subreads, quals):
         """pairwise_consensus(msa_rows, subreads, quals) of bin/consensus.py:76"""
         ra, rb = _b(msa_rows[0]), _b(msa_rows[1])
@@ -488,6 +535,27 @@ def demux_host(heads, set_a, set_b, return_dist=False):
     return res
 
 
+def _qv_args(cons, pieces):
+    cb = _b(cons)
+    seqs, quals = [_b(p[0]) for p in pieces], [_b(p[1]) for p in pieces]
+    off = np.zeros(len(pieces) + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in seqs], out=off[1:])
+    modes = np.array([int(p[2]) for p in pieces] or [0], dtype=np.int32)
+    sc, qc = b"".join(seqs) + b"\0", b"".join(quals) + b"\0"
+    out = C.create_string_buffer(len(cb) + 1)
+    return (cb, len(cb), len(pieces), sc, qc, off.ctypes.data, modes.ctypes.data, out), (cb, sc, qc, off, modes, out)
+
+
+def consensus_qv_host(cons, pieces):
+    """c3_consensus_qv_host: the host statement of Handle.consensus_qv (same arguments and result)"""
+    lib = load()
+    args, keep = _qv_args(cons, pieces)
+    rc = lib.c3_consensus_qv_host(*args)
+    if rc < 0:
+        raise C3Error("c3 error %d: %s" % (rc, lib.c3_last_error(None).decode()))
+    return keep[-1].raw[:len(keep[0])].decode()
+
+
 def device_count():
     return int(load().c3_device_count())
 
@@ -502,7 +570,7 @@ class ResultBuffers:
     pinned=True takes them from c3_host_alloc (page-locked): what c3_batch_results_begin needs to copy asynchronously"""
 
     def __init__(self, pinned=False):
-        self.res = self.buf = self.coff = None
+        self.res = self.buf = self.coff = self.qv = None
         self.pinned = pinned
         self._p = {}
         self._retired = []
@@ -542,8 +610,14 @@ class ResultBuffers:
             self.coff = self._alloc("coff", n + n // 4 + 2, np.int64)
         return self.res[:n], self.buf, self.coff[:n + 1]
 
+    def fit_qv(self, cons_cap):
+        """the QV buffer (same capacity as the consensus buffer), allocated on first use only"""
+        if self.qv is None or len(self.qv) < cons_cap:
+            self.qv = self._alloc("qv", cons_cap + cons_cap // 4, np.uint8)
+        return self.qv
+
     def close(self):
-        self.res = self.buf = self.coff = None
+        self.res = self.buf = self.coff = self.qv = None
         self._release_retired()
         for p in self._p.values():
             self.lib.c3_host_free(p)
@@ -759,3 +833,17 @@ def write_group(hb, res, cons_buf, cons_off, splint_ids, cons_paths, sub_paths, 
                             coff.ctypes.data, sid.ctypes.data, n_spl, cp, sp, 1 if zero else 0)
     if rc != 0:
         raise OSError("c3_write_group failed (%d)" % rc)
+
+
+def write_consensus_fastq(hb, res, cons_buf, cons_off, qv_buf, splint_ids, fq_paths, zero=True):
+    """c3_write_consensus_fastq: append the consensus FASTQ records (c3_write_group's FASTA records + QV line) of one group"""
+    lib = load()
+    n_spl = len(fq_paths)
+    fp = (C.c_char_p * n_spl)(*[_b(p) for p in fq_paths])
+    sid = np.ascontiguousarray(splint_ids, dtype=np.int16)
+    res = np.ascontiguousarray(res)
+    coff = np.ascontiguousarray(cons_off, dtype=np.int64)
+    rc = lib.c3_write_consensus_fastq(C.byref(hb.c), res.ctypes.data, cons_buf.ctypes.data, coff.ctypes.data, qv_buf.ctypes.data,
+                                      sid.ctypes.data, n_spl, fp, 1 if zero else 0)
+    if rc != 0:
+        raise OSError("c3_write_consensus_fastq failed (%d)" % rc)

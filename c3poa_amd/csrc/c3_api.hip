@@ -24,6 +24,8 @@ extern "C" void c3k_launch_stitch(const StitchArgs*, int, hipStream_t);
 extern "C" void c3k_launch_zero(const ZeroArgs*, int, hipStream_t);
 extern "C" void c3k_launch_zero_long(const ZeroArgs*, int, hipStream_t);
 extern "C" void c3k_launch_zero_finish(const ZeroArgs*, int, hipStream_t);
+extern "C" void c3k_launch_qv(const QvArgs*, int, hipStream_t);
+extern "C" int c3k_qv_lds_max(void);
 
 // ---- small kernels ----------------------------------------------------------------------
 __device__ __forceinline__ uint32_t pack_code(uint32_t b) {
@@ -173,6 +175,8 @@ struct c3_handle {
   DBuf s_zero_d, d_zinfo, d_zflag, d_zwork; std::vector<int> zwork;  // zero-repeat rescue: k_zero direction bytes, per-read records, work list
   DBuf s_zero_l;                                                      // k_zero_long slots
   DBuf d_dmx_heads, d_dmx_meta, d_dmx_out;                            // demultiplexer: heads, Peq / lengths / byte codes, winners + distances
+  DBuf d_qv, s_qv_dirs, s_qv_g, d_qv_cnt, d_gather_qv;                // QV stage: QV arena (like d_cons), direction slots, long-consensus slots, counters, snapshot
+  hipEvent_t ev_qv[2] = {nullptr, nullptr}; c3_qv_timing qtm = {}; bool snap_qv = false;
   std::vector<Summary> sum; std::vector<int> work;
   int res_prefix = 0;            // entries of peaks[] / sub_beg[] / sub_end[] that any read of the resident batch uses (0: unknown)
   int peaks_grid = 0; bool debug_msa = false; bool injected = false;
@@ -262,12 +266,13 @@ extern "C" void c3_destroy(c3_handle* h) {
                  &h->d_work, &h->d_bufA, &h->d_bufB, &h->d_cand, &h->d_cst, &h->d_msa, &h->d_msa_off, &h->d_msa_len,
                  &h->s_poa_i, &h->s_poa_nk, &h->s_poa_cells, &h->s_poa_b, &h->s_poa_sc, &h->s_poa_desc, &h->s_poa_jump, &h->s_poa_path, &h->d_overflow, &h->s_eH, &h->s_eD, &h->s_lw, &h->d_wrec,
                  &h->d_wlay, &h->d_wbase, &h->d_wout, &h->s_win_i, &h->s_win_nk, &h->s_win_h, &h->s_win_d, &h->s_win_b, &h->s_win_sc, &h->s_win_desc, &h->s_zero_d, &h->s_zero_l, &h->d_zinfo, &h->d_zflag, &h->d_zwork, &h->d_gather, &h->d_gather_off,
-                 &h->d_dmx_heads, &h->d_dmx_meta, &h->d_dmx_out};
+                 &h->d_dmx_heads, &h->d_dmx_meta, &h->d_dmx_out, &h->d_qv, &h->s_qv_dirs, &h->s_qv_g, &h->d_qv_cnt, &h->d_gather_qv};
   for (DBuf* b : all) b->release();
   { DBuf* sh[] = {&h->st.d_ascii, &h->st.d_pk, &h->st.d_woff, &h->st.d_qual, &h->st.d_off, &h->st.d_strand, &h->st.d_sid}; for (DBuf* b : sh) b->release(); }
   if (h->stream_up) { (void)hipStreamSynchronize(h->stream_up); (void)hipStreamDestroy(h->stream_up); }
   for (int i = 0; i < 2; ++i) if (h->ev_up[i]) (void)hipEventDestroy(h->ev_up[i]);
   for (int i = 0; i < EV_N; ++i) (void)hipEventDestroy(h->ev[i]);
+  for (int i = 0; i < 2; ++i) if (h->ev_qv[i]) (void)hipEventDestroy(h->ev_qv[i]);
   (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -819,8 +824,58 @@ static int run_polish(c3_handle* h, float* ms_prep, float* ms_win, float* ms_st)
   return 0;
 }
 
+// QV scratch: one direction slot per wave (ceil(longest piece / 8) groups of 256 bytes; a piece is at most a read) and, when
+// the batch has reads longer than the LDS holds, one S + codes slot per workgroup; the slot count is bounded by a fixed budget.
+static const long long QV_BUDGET = 1LL << 30;
+static int qv_scratch(c3_handle* h, long long max_m, long long max_n, int n_items, QvArgs& a, int* grid) {
+  a.dir_words = (max_m + 7) / 8 * 64;
+  a.lds_n = (int)std::min<long long>((max_n + 15) / 16 * 16, c3k_qv_lds_max());
+  a.gcap = max_n > a.lds_n ? (max_n + 15) / 16 * 16 : 0;
+  const long long per_wg = 4 * 4 * a.dir_words + 5 * a.gcap;
+  *grid = (int)std::max(1LL, std::min<long long>(std::min(n_items, h->n_cus * 8), QV_BUDGET / per_wg));
+  HIPCHK(h->s_qv_dirs.ensure(sizeof(uint32_t) * (size_t)a.dir_words * 4 * (size_t)*grid + 256));
+  if (a.gcap) HIPCHK(h->s_qv_g.ensure((size_t)a.gcap * 5 * (size_t)*grid + 256));
+  a.dirs = h->s_qv_dirs.as<uint32_t>();
+  a.gS = a.gcap ? h->s_qv_g.as<int>() : nullptr; a.gcodes = a.gcap ? h->s_qv_g.as<uint8_t>() + (size_t)a.gcap * 4 * (size_t)*grid : nullptr;
+  HIPCHK(h->d_qv_cnt.ensure(64));
+  HIPCHK(hipMemsetAsync(h->d_qv_cnt.p, 0, 64, h->stream));
+  a.cnt = h->d_qv_cnt.as<unsigned long long>();
+  return 0;
+}
+static int qv_counts(c3_handle* h, float ms) {
+  unsigned long long c[8];
+  HIPCHK(hipMemcpyAsync(c, h->d_qv_cnt.p, 64, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->qtm.ms_qv = ms; h->qtm.n_reads = (int64_t)c[0]; h->qtm.n_pieces = (int64_t)c[1]; h->qtm.n_skipped = (int64_t)c[2];
+  h->qtm.band_cells = (int64_t)c[3]; h->qtm.edge_hits = (int64_t)c[4];
+  return 0;
+}
+
+// per-base QVs of every read with a consensus (k_qv after the polish); writes the QV arena at off[i] as d_cons
+static int run_qv(c3_handle* h) {
+  for (int i = 0; i < 2; ++i) if (!h->ev_qv[i]) HIPCHK(hipEventCreate(&h->ev_qv[i]));
+  HIPCHK(h->d_qv.ensure((size_t)h->total + 64));
+  QvArgs a; memset(&a, 0, sizeof(a));
+  int grid = 0;
+  int rc = qv_scratch(h, h->maxL, h->maxL, h->n, a, &grid);
+  if (rc) return rc;
+  a.n_reads = h->n; a.info = h->d_info.as<C3Info>(); a.pk = h->d_pk.as<uint32_t>(); a.woff = h->d_woff.as<int64_t>();
+  a.qual = h->d_qual.as<uint8_t>(); a.off = h->d_off.as<int64_t>(); a.cons = h->d_cons.as<char>(); a.qv = h->d_qv.as<char>();
+  a.sa_np = -1;
+  DBG("qv: grid=%d dir_words=%lld lds_n=%d gcap=%lld\n", grid, a.dir_words, a.lds_n, a.gcap);
+  HIPCHK(hipEventRecord(h->ev_qv[0], h->stream));
+  c3k_launch_qv(&a, grid, h->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->ev_qv[1], h->stream));
+  HIPCHK(hipEventSynchronize(h->ev_qv[1]));
+  float ms = 0; HIPCHK(hipEventElapsedTime(&ms, h->ev_qv[0], h->ev_qv[1]));
+  return qv_counts(h, ms);
+}
+
 extern "C" int c3_batch_run(c3_handle* h, int stages) {
   if (!h || h->n <= 0) return C3_E_STATE;
+  if ((stages & C3_STAGE_QV) && !((stages | h->stages_done) & C3_STAGE_POLISH))
+    return c3_fail(h, C3_E_STATE, "C3_STAGE_QV needs the polish stage (in this call or an earlier one on the resident batch)");
   HIPCHK(hipSetDevice(h->cfg.device));
   int rc;
   float ms;
@@ -859,6 +914,7 @@ extern "C" int c3_batch_run(c3_handle* h, int stages) {
     }
     if (stages & C3_STAGE_POLISH) { if ((rc = run_polish(h, &ms_prep, &ms_win, &ms_st))) return rc; }
   }
+  if (stages & C3_STAGE_QV) { if ((rc = run_qv(h))) return rc; }
   HIPCHK(hipStreamSynchronize(h->stream));
   DBG("run: done\n");
   HIPCHK(hipGetLastError());
@@ -869,7 +925,14 @@ extern "C" int c3_batch_run(c3_handle* h, int stages) {
   h->tm.ms_wall = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - wall0).count();
   h->tm.ms_alloc = (float)(g_alloc_ms - alloc0);
   h->tm.ms_host_gap = h->tm.ms_wall - h->tm.ms_total;
+  if (stages & C3_STAGES_ALL) h->stages_done &= ~C3_STAGE_QV;         // a rerun of any stage without QV leaves stale QVs
   h->stages_done |= stages;
+  return C3_E_OK;
+}
+
+extern "C" int c3_batch_qv_timing(c3_handle* h, c3_qv_timing* t) {
+  if (!h || !t) return C3_E_ARG;
+  *t = h->qtm;
   return C3_E_OK;
 }
 
@@ -928,16 +991,24 @@ extern "C" int c3_batch_results_snapshot(c3_handle* h) {
     hipLaunchKernelGGL(k_gather_cons, dim3((unsigned)std::min((n + 3) / 4, h->n_cus * 32)), dim3(256), 0, h->stream,
                        h->d_cons.as<char>(), h->d_off.as<int64_t>(), d_coff.as<int64_t>(), n, d_out.as<char>());
   }
+  const bool have_qv = have_cons && (h->stages_done & C3_STAGE_QV) != 0;
+  if (have_qv && tot > 0) {                                   // the QV bytes, gathered at the same offsets
+    HIPCHK(h->d_gather_qv.ensure((size_t)tot + 64));
+    hipLaunchKernelGGL(k_gather_cons, dim3((unsigned)std::min((n + 3) / 4, h->n_cus * 32)), dim3(256), 0, h->stream,
+                       h->d_qv.as<char>(), h->d_off.as<int64_t>(), d_coff.as<int64_t>(), n, h->d_gather_qv.as<char>());
+  }
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(h->ev_dn, h->stream));
-  h->snap_n = n; h->snap_kp = prefix ? kp : 0; h->snap_tot = tot; h->snap_cons = have_cons;
+  h->snap_n = n; h->snap_kp = prefix ? kp : 0; h->snap_tot = tot; h->snap_cons = have_cons; h->snap_qv = have_qv;
   h->snap_pending.store(true, std::memory_order_release);
   return C3_E_OK;
 }
 
-extern "C" int c3_batch_results_fetch(c3_handle* h, c3_read_result* res, char* cons, int64_t cons_cap, int64_t* cons_off) {
+// c3_batch_results_fetch and c3_batch_results_fetch_qv (qv != NULL: the QV bytes too, same offsets and cap)
+static int results_fetch(c3_handle* h, c3_read_result* res, char* cons, int64_t cons_cap, int64_t* cons_off, char* qv) {
   if (!h || !res) return C3_E_ARG;
   if (!h->snap_pending.load(std::memory_order_acquire)) return C3_E_STATE;          // (h->err belongs to the owner thread: not touched here)
+  if (qv && !h->snap_qv) return C3_E_STATE;                                          // (the snapshot stays pending for a plain fetch)
   hipError_t e;
 #define DNCHK(x) do { if ((e = (x)) != hipSuccess) { h->snap_pending.store(false, std::memory_order_release); return C3_E_HIP; } } while (0)
   DNCHK(hipSetDevice(h->cfg.device));
@@ -957,10 +1028,30 @@ extern "C" int c3_batch_results_fetch(c3_handle* h, c3_read_result* res, char* c
   if (cons_off) DNCHK(hipMemcpyAsync(cons_off, h->d_gather_off.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, dn));
   const bool fits = !(cons_off && cons) || h->snap_tot <= cons_cap;
   if (cons_off && cons && fits && h->snap_cons && h->snap_tot > 0) DNCHK(hipMemcpyAsync(cons, h->d_gather.p, (size_t)h->snap_tot, hipMemcpyDeviceToHost, dn));
+  if (qv && cons_off && cons && fits && h->snap_tot > 0) DNCHK(hipMemcpyAsync(qv, h->d_gather_qv.p, (size_t)h->snap_tot, hipMemcpyDeviceToHost, dn));
   DNCHK(hipStreamSynchronize(dn));
 #undef DNCHK
   h->snap_pending.store(false, std::memory_order_release);
   return fits ? C3_E_OK : C3_E_LIMIT;                 // too small: the records and the offsets (needed size = cons_off[n]) were still delivered
+}
+
+extern "C" int c3_batch_results_fetch(c3_handle* h, c3_read_result* res, char* cons, int64_t cons_cap, int64_t* cons_off) {
+  return results_fetch(h, res, cons, cons_cap, cons_off, nullptr);
+}
+extern "C" int c3_batch_results_fetch_qv(c3_handle* h, c3_read_result* res, char* cons, int64_t cons_cap, int64_t* cons_off, char* qv) {
+  if (!qv) return C3_E_ARG;
+  return results_fetch(h, res, cons, cons_cap, cons_off, qv);
+}
+
+extern "C" int c3_batch_results_qv(c3_handle* h, c3_read_result* res, char* cons, int64_t cons_cap, int64_t* cons_off, char* qv) {
+  if (!h || h->n <= 0 || !res || !qv) return C3_E_ARG;
+  if (!(h->stages_done & C3_STAGE_QV) || !(h->stages_done & C3_STAGE_POLISH)) return c3_fail(h, C3_E_STATE, "the resident batch did not run C3_STAGE_QV");
+  int rc = c3_batch_results_snapshot(h);
+  if (rc) return rc;
+  rc = c3_batch_results_fetch_qv(h, res, cons, cons_cap, cons_off, qv);
+  if (rc == C3_E_LIMIT) return c3_fail(h, C3_E_LIMIT, "consensus buffer too small");
+  if (rc == C3_E_HIP) return c3_fail(h, C3_E_HIP, "HIP error while copying the results");
+  return rc;
 }
 
 extern "C" int c3_batch_results(c3_handle* h, c3_read_result* res, char* cons, int64_t cons_cap, int64_t* cons_off) {
@@ -1224,6 +1315,57 @@ extern "C" int c3_demux_indexes(c3_handle* h, int n, const char* heads, int n_a,
   HIPCHK(hipMemcpyAsync(win, d_out, wb, hipMemcpyDeviceToHost, h->stream));
   if (dist) HIPCHK(hipMemcpyAsync(dist, d_out + wb, db, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));      // meta is a host vector of this frame
+  return C3_E_OK;
+}
+
+// stand-alone QVs of one consensus (k_qv on one workgroup); the host statement and the shared refusals are in c3_qv.cpp.
+// The pieces are 2-bit packed here the way c3_batch_stage packs reads (every piece starts on a word).
+int c3_qv_check(const char* cons, int n, int n_pieces, const char* seq_cat, const char* qual_cat, const int64_t* piece_off,
+                const int32_t* modes, const char* qv_out, const char** msg);
+extern "C" int c3_consensus_qv(c3_handle* h, const char* cons, int n, int n_pieces, const char* seq_cat, const char* qual_cat,
+                               const int64_t* piece_off, const int32_t* modes, char* qv_out) {
+  if (!h) return C3_E_ARG;
+  const char* msg = "";
+  const int rc0 = c3_qv_check(cons, n, n_pieces, seq_cat, qual_cat, piece_off, modes, qv_out, &msg);
+  if (rc0 != C3_E_OK) return c3_fail(h, rc0, msg);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const int np = n_pieces;
+  std::vector<int64_t> woff((size_t)np + 1, 0);
+  long long max_m = 1;
+  for (int k = 0; k < np; ++k) {
+    const int64_t m = piece_off[k + 1] - piece_off[k];
+    max_m = std::max<long long>(max_m, m);
+    woff[(size_t)k + 1] = woff[(size_t)k] + (m + 15) / 16 + 2;
+  }
+  std::vector<uint32_t> pk((size_t)woff[(size_t)np] + 1, 0u);
+  for (int k = 0; k < np; ++k)
+    for (int64_t x = 0; x < piece_off[k + 1] - piece_off[k]; ++x)
+      pk[(size_t)(woff[(size_t)k] + x / 16)] |= (uint32_t)code_of(seq_cat[piece_off[k] + x]) << ((x & 15) * 2);
+  const size_t qb = np ? (size_t)piece_off[np] : 0;
+  // one device buffer: consensus | QVs | qualities | packed pieces | word offsets | base offsets | modes
+  const size_t o_qv = (size_t)n + 64, o_q = o_qv + (size_t)n + 64, o_pk = (o_q + qb + 64 + 255) / 256 * 256;
+  const size_t o_wo = o_pk + 4 * pk.size() + 64, o_off = o_wo + 8 * woff.size() + 64, o_md = o_off + 8 * ((size_t)np + 1) + 64;
+  DBuf d; HIPCHK(d.ensure(o_md + 4 * (size_t)np + 64));
+  char* b = d.as<char>();
+  HIPCHK(hipMemcpyAsync(b, cons, (size_t)n, hipMemcpyHostToDevice, h->stream));
+  if (np) {
+    HIPCHK(hipMemcpyAsync(b + o_q, qual_cat, qb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(b + o_pk, pk.data(), 4 * pk.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(b + o_wo, woff.data(), 8 * woff.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(b + o_off, piece_off, 8 * ((size_t)np + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(b + o_md, modes, 4 * (size_t)np, hipMemcpyHostToDevice, h->stream));
+  }
+  QvArgs a; memset(&a, 0, sizeof(a));
+  int grid = 0;
+  const int rc = qv_scratch(h, max_m, n, 1, a, &grid);
+  if (rc) { d.release(); return rc; }
+  a.cons = b; a.qv = b + o_qv; a.qual = (const uint8_t*)(b + o_q); a.pk = (const uint32_t*)(b + o_pk);
+  a.sa_np = np; a.sa_n = n; a.sa_woff = (const int64_t*)(b + o_wo); a.sa_off = (const int64_t*)(b + o_off); a.sa_mode = (const int32_t*)(b + o_md);
+  c3k_launch_qv(&a, 1, h->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(qv_out, b + o_qv, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));           // pk / woff are host vectors of this frame
+  d.release();
   return C3_E_OK;
 }
 

@@ -80,3 +80,14 @@ __host__ __device__ inline ZlLayout c3_zl_layout(long long n0, long long n1, lon
   l.total = (l.car + n1 * 12 + 255) & ~255LL;
   return l;
 }
+// k_qv (k_qv.hip): per-base consensus QVs.  Batch form (sa_np < 0): every read of the resident batch with status OK and
+// cons_len > 0; stand-alone form (sa_np >= 0): one consensus cons[0..sa_n) with sa_np pieces packed like reads.
+struct QvArgs {
+  int n_reads; const C3Info* info; const uint32_t* pk; const int64_t* woff; const uint8_t* qual; const int64_t* off;
+  const char* cons; char* qv;                      // consensus / QV bytes at off[r] (batch) or at 0 (stand-alone)
+  int sa_np, sa_n; const int64_t* sa_woff; const int64_t* sa_off; const int32_t* sa_mode;
+  uint32_t* dirs; long long dir_words;             // [grid * 4][dir_words] packed direction dwords, one slot per wave
+  int* gS; uint8_t* gcodes; long long gcap;        // [grid][gcap]: S and codes of a consensus longer than lds_n
+  int lds_n;                                       // consensus columns held in LDS (S int32 + code byte each)
+  unsigned long long* cnt;                         // [0] reads, [1] pieces, [2] skipped, [3] band cells, [4] edge hits
+};

@@ -742,6 +742,49 @@ extern "C" int c3_write_group(const c3_host_batch* b, const c3_read_result* res,
   return ok ? C3_E_OK : C3_E_ARG;
 }
 
+// R2C2_Consensus.fastq beside the FASTA: the consensus records of c3_write_group (emit_of, same header) with the QV line.
+// One formatting pass per splint file (the records are a small share of the group's bytes), then c3_write_group's
+// reservation of the byte range at the end of the file and one pwrite.
+extern "C" int c3_write_consensus_fastq(const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
+                                        const char* qv, const int16_t* splint_id, int n_splints, const char* const* fq_paths, int zero) {
+  if (!b || !res || !cons || !cons_off || !qv || !splint_id || n_splints <= 0 || !fq_paths) return C3_E_ARG;
+  std::vector<size_t> bound((size_t)n_splints, 0);
+  for (int i = 0; i < b->n; ++i) {
+    const int64_t clen = cons_off[i + 1] - cons_off[i];
+    const Emit e = emit_of(res[i], splint_id[i], n_splints, zero, clen);
+    if (e.cons) bound[(size_t)splint_id[i]] += (size_t)(b->name_off[i + 1] - b->name_off[i]) + 2 * (size_t)clen + 96;
+  }
+  bool ok = true;
+  for (int s = 0; s < n_splints && ok; ++s) {
+    if (!bound[(size_t)s] || !fq_paths[s]) continue;
+    std::vector<char> buf(bound[(size_t)s]);
+    Out o{buf.data()};
+    for (int i = 0; i < b->n; ++i) {
+      if (splint_id[i] != s) continue;
+      const int64_t clen = cons_off[i + 1] - cons_off[i];
+      const Emit e = emit_of(res[i], s, n_splints, zero, clen);
+      if (!e.cons) continue;
+      const char* name = b->names + b->name_off[i]; const size_t nl = (size_t)(b->name_off[i + 1] - b->name_off[i]);
+      const int64_t L = b->off[i + 1] - b->off[i];
+      o.put('@'); o.app(name, nl); o.put('_');
+      avg_qual_text(b->quals + b->off[i], L, o);
+      o.put('_'); o.num((long long)L); o.put('_'); o.num(e.ns);
+      o.put('_'); o.num((long long)clen); o.put('\n');
+      o.app(cons + cons_off[i], (size_t)clen); o.app("\n+\n", 3);
+      o.app(qv + cons_off[i], (size_t)clen); o.put('\n');
+    }
+    const size_t total = (size_t)(o.p - buf.data());
+    if (!total) continue;
+    const int fd = open(fq_paths[s], O_WRONLY | O_CREAT, 0644);
+    if (fd < 0) { ok = false; break; }
+    const off_t at = reserve_append(fd, total);
+    if (!pwrite_all(fd, buf.data(), total, at)) ok = false;
+    release_append(fd);
+    if (close(fd) != 0) ok = false;
+  }
+  return ok ? C3_E_OK : C3_E_ARG;
+}
+
 // ---- oligo-dT index matcher of the post-processing step (C3POa_postprocessing.py:266-285, match_index) ----------
 // seq is slid over every index (file order); the Levenshtein distance of seq[p : p+len(idx)] to idx is taken for every
 // position where the slice has the full length (at a position where it is too short for index k the reference breaks

@@ -75,6 +75,9 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
     compress = bool(getattr(args, "compress_output", False))
     cons_paths = [args.out_path + n + "/R2C2_Consensus.fasta" for n in splint_names]
     sub_paths = [args.out_path + n + "/R2C2_Subreads.fastq" for n in splint_names]
+    # --consensus-fastq: per-base QVs on the GPU (STAGE_QV) and R2C2_Consensus.fastq beside the FASTA
+    qv_on = bool(getattr(args, "consensus_fastq", False))
+    fq_paths = [args.out_path + n + "/R2C2_Consensus.fastq" for n in splint_names] if qv_on else []
     fused = assigner is None
     used = set(adapter_set or ())                                             # cat_files runs per adapter_set entry (C3POa.py:259)
     if fused:
@@ -83,10 +86,10 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
         sp_lens = [len(splint_dict[n][0]) for n in splint_names]
     if isinstance(assigner, DictAssigner):
         used |= set(v[0] for v in assigner.d.values())
-    for n, cp, sp in zip(splint_names, cons_paths, sub_paths):
+    for k, (n, cp, sp) in enumerate(zip(splint_names, cons_paths, sub_paths)):
         if n in used:
             os.makedirs(args.out_path + n, exist_ok=True)
-            for p in (cp, sp):                                   # "w+" semantics of cat_files (C3POa.py:88-92)
+            for p in (cp, sp) + ((fq_paths[k],) if qv_on else ()):                                   # "w+" semantics of cat_files (C3POa.py:88-92)
                 open(p, "w").close()
                 if os.path.exists(p + ".gz"):
                     os.remove(p + ".gz")
@@ -249,7 +252,10 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
                 except queue.Empty:
                     pass
                 t1 = time.perf_counter()
-                h.run()
+                if qv_on:
+                    h.run(qv=True)
+                else:
+                    h.run()
                 t2 = time.perf_counter()
                 up_dev = h.last_timing["ms_pack"] * 1e-3
                 run_dev = h.last_timing["ms_total"] * 1e-3
@@ -308,7 +314,10 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
             rb = free_results.get()
             t0 = time.perf_counter()
             try:
-                res, buf, coff = h.results_fetch(rb, shape)
+                if qv_on:
+                    res, buf, coff, qv = h.results_fetch_qv(rb, shape)
+                else:
+                    (res, buf, coff), qv = h.results_fetch(rb, shape), None
             except Exception as e:                  # noqa: BLE001
                 errors.append(e)
                 fetched[w].set()
@@ -319,7 +328,7 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
             with lock:
                 t["fetch"] += time.perf_counter() - t0
             del h, item
-            to_write[w].put((hb, sid, res, buf, coff, rb))
+            to_write[w].put((hb, sid, res, buf, coff, qv, rb))
         to_write[w].put(None)
 
     def writer_thread(w):                           # c3_write_group releases the GIL: overlaps parsing and the GPUs
@@ -327,17 +336,19 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
             item = to_write[w].get()
             if item is None:
                 break
-            hb, sid, res, buf, coff, rb = item
+            hb, sid, res, buf, coff, qv, rb = item
             t0 = time.perf_counter()
             try:
                 if not errors:
                     _lib.write_group(hb, res, buf, coff, sid, cons_paths, sub_paths, getattr(args, "zero", True))
+                    if qv_on:
+                        _lib.write_consensus_fastq(hb, res, buf, coff, qv, sid, fq_paths, getattr(args, "zero", True))
             except Exception as e:                  # noqa: BLE001
                 errors.append(e)
             with lock:
                 t["write"] += time.perf_counter() - t0
             k, j = hb.range_index, hb.set_index
-            del hb, item, res, buf, coff
+            del hb, item, res, buf, coff, qv
             free_results.put(rb)
             free_sets[k].put(j)
 
@@ -363,9 +374,9 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
     t["at_readers_closed"] = time.perf_counter() - t_start
     if fused:
         os.replace(finder_psl + ".part", finder_psl)              # a rerun finds the PSL and takes the two-pass route
-        for n, cp, sp in zip(splint_names, cons_paths, sub_paths):
+        for k, (n, cp, sp) in enumerate(zip(splint_names, cons_paths, sub_paths)):
             if n not in seen:                                       # adapter_set of bin/preprocess.py:34,43 = splints that were hit
-                for p in (cp, sp):
+                for p in (cp, sp) + ((fq_paths[k],) if qv_on else ()):
                     if os.path.exists(p) and os.stat(p).st_size == 0:
                         os.remove(p)
                 try:
@@ -374,7 +385,7 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
                     pass
         t["adapter_set"] = sorted(seen)
     if compress:                                                        # -co (C3POa.py:88-90)
-        for p in cons_paths + sub_paths:
+        for p in cons_paths + sub_paths + fq_paths:
             if os.path.exists(p):
                 with open(p, "rb") as src, gzip.open(p + ".gz", "wb", compresslevel=6) as dst:
                     shutil.copyfileobj(src, dst, 1 << 24)

@@ -324,6 +324,65 @@ int c3_demux_indexes(c3_handle* h, int n, const char* heads, int n_a, const char
 int c3_demux_host(int n, const char* heads, int n_a, const char* a_cat, const int64_t* a_off,
                   int n_b, const char* b_cat, const int64_t* b_off, int32_t* win, uint8_t* dist);
 
+/* ---- per-base consensus quality values (opt-in; the reference writes FASTA only) ----
+ * Every consensus base C[j] gets a SUPPORT score from the pieces the polish used, realigned to the consensus:
+ *   kept subread k < n_sub     read[sub_beg[k]:sub_end[k]]  mode 0 (global: whole piece against whole C)
+ *   tail piece (has_tail)      read[tail_beg:L]             mode 1 (anchored at start: begins at C[0] / piece[0], ends at the best cell)
+ *   front piece (has_front)    read[0:front_end]            mode 2 (anchored at end: mode 1 on both sequences reversed, mapped back)
+ * Alignment: piece rows i = 0..m against C columns j = 0..n, 2-bit codes (c3poa.h conventions), linear scores match
+ * +C3_QV_MATCH, mismatch C3_QV_MISMATCH, gap C3_QV_GAP, H maximised, H[0][0] = 0.  Only C3_QV_BAND cells per row exist:
+ * c(i) - 64 <= j <= c(i) + 63 with c(i) = floor((i*n + floor(m/2)) / m) in mode 0 and c(i) = i in modes 1 / 2.  The end
+ * cell is (m, n) in mode 0, else the band cell of largest H (smallest i, then smallest j).  Traceback priority: diagonal,
+ * deletion (consumes C[j-1]), insertion.  With q(b) = Phred byte - 33 clamped to 0..93, each piece adds to S[j] of the
+ * columns it covers (all in mode 0, else the consumed ones): +q(b) for a matching diagonal, -q(b) for a mismatching one,
+ * -q(last piece base consumed before it, else piece[0]) for a deletion, -max q of every maximal insertion run to the column
+ * after it (or to the last covered column).  QV[j] = min(C3_QV_MAX, max(0, S[j])), written as QV + 33; uncovered columns get 0.
+ * A mode-0 pair with max(m, n) > C3_QV_SKEW * min(m, n) is not aligned.  These values measure SUPPORT: they are not calibrated
+ * error probabilities.  DESIGN.md "Consensus quality values" has the full statement. */
+#define C3_STAGE_QV 16            /* c3_batch_run(h, C3_STAGES_ALL | C3_STAGE_QV): k_qv after the polish (C3_STAGES_ALL stays 15) */
+#define C3_QV_BAND 128            /* band cells per DP row */
+#define C3_QV_MAX 60              /* QV clamp */
+#define C3_QV_MATCH 2
+#define C3_QV_MISMATCH (-4)
+#define C3_QV_GAP (-4)
+#define C3_QV_SKEW 4              /* mode-0 pairs beyond this length ratio are refused (stand-alone) / skipped (batch) */
+#define C3_QV_MAX_PIECES 252      /* C3_MAX_SUB subreads + the two dangling pieces */
+#define C3_QV_GLOBAL 0
+#define C3_QV_ANCHOR_START 1
+#define C3_QV_ANCHOR_END 2
+
+/* kernel figures of the last c3_batch_run with C3_STAGE_QV (c3_timing is not extended: its size is part of the ABI) */
+typedef struct {
+  float ms_qv;               /* k_qv, hipEvents on the library's stream */
+  int64_t n_reads;           /* reads given QVs (status OK, cons_len > 0) */
+  int64_t n_pieces;          /* pieces aligned */
+  int64_t n_skipped;         /* mode-0 pieces beyond the skew limit (cover no column) */
+  int64_t band_cells;        /* C3_QV_BAND * DP rows computed, row 0 included */
+  int64_t edge_hits;         /* pieces whose traceback touched an interior band edge (band adequacy diagnostic, not an error) */
+} c3_qv_timing;
+int c3_batch_qv_timing(c3_handle* h, c3_qv_timing* t);
+
+/* c3_batch_results + the QV bytes: qv[cons_off[i] ..] receives read i's QVs, same offsets and cap as cons.
+ * _fetch_qv follows the rules of c3_batch_results_fetch (may overlap the next batch's run); c3_batch_results_qv = snapshot +
+ * fetch_qv.  C3_E_STATE when the resident batch (at snapshot time) did not run C3_STAGE_QV. */
+int c3_batch_results_fetch_qv(c3_handle* h, c3_read_result* res, char* cons, int64_t cons_cap, int64_t* cons_off, char* qv);
+int c3_batch_results_qv(c3_handle* h, c3_read_result* res, char* cons, int64_t cons_cap, int64_t* cons_off, char* qv);
+
+/* stand-alone QVs of one consensus cons[0..n) from n_pieces pieces (seq_cat / qual_cat, piece_off[n_pieces+1], modes[k] =
+ * C3_QV_GLOBAL / _ANCHOR_START / _ANCHOR_END); qv_out[n] receives Phred+33 bytes.  c3_consensus_qv runs k_qv on the
+ * handle's device; c3_consensus_qv_host is its host statement (full band DP per piece), errors through c3_last_error(NULL).
+ * Both refuse an empty consensus, an empty piece, more than C3_QV_MAX_PIECES pieces, an unknown mode and a mode-0 pair beyond
+ * the skew limit. */
+int c3_consensus_qv(c3_handle* h, const char* cons, int n, int n_pieces, const char* seq_cat, const char* qual_cat,
+                    const int64_t* piece_off, const int32_t* modes, char* qv_out);
+int c3_consensus_qv_host(const char* cons, int n, int n_pieces, const char* seq_cat, const char* qual_cat,
+                         const int64_t* piece_off, const int32_t* modes, char* qv_out);
+
+/* R2C2_Consensus.fastq: @<header>\n<cons>\n+\n<qv>\n for exactly the reads c3_write_group gives a FASTA record (same header,
+ * same order), appended to fq_paths[splint_id[i]] with c3_write_group's per-file reservation and locking.  Host code. */
+int c3_write_consensus_fastq(const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
+                             const char* qv, const int16_t* splint_id, int n_splints, const char* const* fq_paths, int zero);
+
 #ifdef __cplusplus
 }
 #endif
