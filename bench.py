@@ -19,13 +19,19 @@ rank processes --reads reads per step.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
     python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR   # + the last step's results as DIR/*.npy (dump_outputs)
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full               # + every check and further measurement (below)
     python bench.py --gpus N ...            # WORLD_SIZE unset: starts N workers itself (child torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0.  roofline = algorithmic HBM bytes of the dominant kernel per launch / its HIP-event
-duration (events recorded by the library on its own stream); cpu_baseline = the oracle (own CPU restatement, "port") on
-a bounded sample, rank 0, N=1 only.
+duration (events recorded by the library on its own stream), from the timed steps themselves.
+
+A plain run does only what the headline needs: inputs, setup, warm-up, the timed steps, --dump-outputs, the line.  --full
+adds, all outside the timed region: config.identity_vs_truth = consensus identity vs the synthetic truth on 200 reads;
+parity_sample = the oracle on 64 random reads of the last batch (rank 0); other_configs = the same step on cfg3 / cfg4 /
+cfgL (--other-configs, rank 0, N=1 only), each with its own parity sample; cpu_baseline = the oracle (own CPU
+restatement, "port") on a bounded sample, rank 0, N=1 only.  --no-cpu drops the oracle legs.
 """
 import argparse
 import json
@@ -195,12 +201,15 @@ def parse_args(argv=None):
     ap.add_argument("--reads", type=int, default=0, help="reads per step per GPU (0 = the config's size: cfg2 100k)")
     ap.add_argument("--cfg", default="cfg2")
     ap.add_argument("--unique", type=int, default=0, help="distinct synthetic reads generated per rank (0 = all)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every check and further measurement after the timed region: identity vs truth, oracle parity "
+                         "sample, other configs, CPU baseline (a plain run does only what the headline needs)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the oracle legs (parity samples, CPU baseline)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: CPU baseline sample size in seconds")
     ap.add_argument("--other-configs", default="auto",
-                    help="comma list of further configs run for 3 steps after the headline (rank 0, N=1): 'auto' = cfg3,cfg4,cfgL "
+                    help="--full: comma list of further configs run for 3 steps after the headline (rank 0, N=1): 'auto' = cfg3,cfg4,cfgL "
                          "when the headline is cfg2 at full size, 'none' = skip")
-    ap.add_argument("--other-unique", type=int, default=0, help="distinct reads generated for each of the other configs (0 = all distinct, no tiling)")
+    ap.add_argument("--other-unique", type=int, default=0, help="--full: distinct reads generated for each of the other configs (0 = all distinct, no tiling)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step delivered (rank 0's records + consensus bytes, seeded sample of reads) as DIR/<name>.npy")
     a = ap.parse_args(argv)
@@ -228,12 +237,12 @@ def main():
     t_gen = time.time()
     recs = make_reads(a.cfg, n_unique, rank * a.reads, max(1, effective_cores() // max(world, 1)))
     t_gen = time.time() - t_gen
-    # inputs of the other configs too (rank 0, N=1): the fork pool must run before anything touches the GPU
+    # inputs of the other configs too (--full, rank 0, N=1): the fork pool must run before anything touches the GPU
     others = a.other_configs
     if others == "auto":
         others = "cfg3,cfg4,cfgL" if (a.cfg == "cfg2" and a.reads >= 100000) else "none"
     other_recs = {}
-    if rank == 0 and world == 1 and others != "none":
+    if a.full and rank == 0 and world == 1 and others != "none":
         for c in [x for x in others.split(",") if x]:
             t_ = time.time()
             other_recs[c] = (make_reads(c, DEFAULT_READS[c] if a.other_unique <= 0 else min(a.other_unique, DEFAULT_READS[c]), 0, effective_cores()), time.time() - t_)
@@ -350,11 +359,12 @@ def main():
         alg_bytes = float(np.sum((lens + 3) // 4 + lens) + np.sum(res["cons_len"][ok]) + 4 * np.sum(res["n_peaks"]))
         achieved = alg_bytes / (avg[dom] * 1e-3) / 1e9
         cells = tm["cells_conk"] + tm["cells_poa"] + tm["cells_polish"]
-        # consensus % identity vs the synthetic truth (second half of BASELINE.json's metric), on a sample
-        n_id = min(200, n_unique)
-        raw = cbuf.tobytes()
-        idents = np.array([synth.identity(raw[coff[i]:coff[i + 1]].decode(), recs[i][3]) if coff[i + 1] > coff[i] else 0.0
-                           for i in range(n_id)])
+        # --full: consensus % identity vs the synthetic truth (second half of BASELINE.json's metric), on a sample (~5 s of host time)
+        if a.full:
+            n_id = min(200, n_unique)
+            raw = cbuf.tobytes()
+            idents = np.array([synth.identity(raw[coff[i]:coff[i + 1]].decode(), recs[i][3]) if coff[i + 1] > coff[i] else 0.0
+                               for i in range(n_id)])
         # HBM traffic of the dominant kernel: PMC counters cannot be collected from inside this process; the number
         # comes from the committed rocprofv3 passes of THIS command when the workload matches
         traffic, tsrc = None, None
@@ -383,7 +393,8 @@ def main():
                        "stages": "stage(H2D+pack, overlapped) | conk+peaks/split+POA+polish | results snapshot (D2H by a helper thread beside the next run) | commit",
                        "reads_per_gpu_step": a.reads, "shard_digests": digests,
                        "consensus_ok": int(ok.sum()), "mean_read_len": float(lens.mean()),
-                       "identity_vs_truth": {"mean": round(float(idents.mean()), 5), "median": round(float(np.median(idents)), 5), "reads": int(n_id)},
+                       **({"identity_vs_truth": {"mean": round(float(idents.mean()), 5), "median": round(float(np.median(idents)), 5),
+                                                 "reads": int(n_id)}} if a.full else {}),
                        "resident_only_reads_per_s": round(a.reads * world / float(np.mean(run_s)), 1),
                        "run_ms": round(float(np.mean(run_s)) * 1e3, 2), "fetch_ms_exposed": round(float(np.sum(fetch_s)) / a.steps * 1e3, 2),
                        "upload_ms_unoverlapped": round(t_up * 1e3, 1)},
@@ -406,11 +417,12 @@ def main():
             out["dump_outputs"] = dumped
     h.close()
     host.close()
-    if rank == 0 and not a.no_cpu:
+    # --full: checks and further measurements, after the headline's handle is gone
+    if a.full and rank == 0 and not a.no_cpu:
         out["parity_sample"] = parity_sample(recs, n_unique, res, cbuf, coff, md)
-    if rank == 0 and world == 1 and other_recs:
+    if rank == 0 and world == 1 and other_recs:                            # (other_recs is empty without --full)
         out["other_configs"] = {c: run_other_config(c, local_rank, *other_recs[c], check=not a.no_cpu) for c in other_recs}
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         out["cpu_baseline"] = cpu_baseline(recs, md, a.cpu_seconds)
     if dist is not None:
         dist.barrier()
