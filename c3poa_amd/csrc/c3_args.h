@@ -25,6 +25,7 @@ struct PoaArgs {
   int* overflow;            // reads whose scratch overflowed (count in counter[4]): redone with worst-case scratch; nullptr in the passes that have it
   int* overflow16;          // reads with a score beyond the 16-bit cells (count in counter[5]): redone by the 32-bit instance; nullptr in that pass
   int rb_span;              // 0 = default; test hook C3_DEBUG_POA_RBSPAN: width of the window a row maximum may move in before the 16-bit base follows it
+  int no2col;               // test hook C3_DEBUG_POA_NO2COL: no two-column rows (those rows take the near rows, as before them)
 };
 struct WLayer { int qbeg, len, begin, end; };
 struct WinRec { int rid, w, n_layers, blen, tgs, out_len, polished, pad_; };

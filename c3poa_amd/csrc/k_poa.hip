@@ -32,6 +32,7 @@ struct Ctx {
   int far_shift;             // far arena (32-bit H, E1, E2, direction words of the FEW rows that keep them): cells_cap >> far_shift cells, behind the byte cells
   int osel;                  // which of the two order buffers is current (g_reorder writes the other one and flips)
   int rb_span;               // RB_HI16 - RB_LO16 (smaller under the C3_DEBUG_POA_RBSPAN test hook: the base moves every few rows)
+  int two_col;               // two-column rows allowed (0 under the C3_DEBUG_POA_NO2COL test hook)
   const uint32_t* pk;        // packed read
 #ifdef C3_DEBUG_PUNT
   unsigned long long* dbg;
@@ -370,14 +371,17 @@ __device__ int poa_align(Ctx& c, const C3Params& P, int qb, int Q, int lane, lon
     // row, must be idle when the band did not move)
     // (DIRECTION BYTE, all rows): bit0 E1 opened (0 = extended), bit1 E2 opened, bits2-3 Ht source (2 M, 1 E1, 0 E2),
     // bits4-5 H source (2 Ht, 1 F1, 0 F2), bit6 F1 extended, bit7 F2 extended.
-    if (!W32 && ((fl >> 18) & 1) && pv_ok) {
-      UNI(u_beg); UNI(u_end); UNI(u_left); UNI(u_right); UNI(u_ncell);
-      const bool nonempty = u_end >= u_beg;
-      const int mplv = nonempty ? u_left + 1 : INT32_MAX / 2, mprv = nonempty ? u_right + 1 : 0;
-      const int beg = max(max(0, min(mplv, qr) - w), u_beg);
-      int end = min(min(Q, max(mprv, qr) + w), u_end + 1);
-      end = max(end, beg - 1);
+    // band of a row whose one predecessor is the row above (fast and two-column rows)
+#define C3_BAND_OF_ROW_ABOVE \
+      UNI(u_beg); UNI(u_end); UNI(u_left); UNI(u_right); UNI(u_ncell); \
+      const bool nonempty = u_end >= u_beg; \
+      const int mplv = nonempty ? u_left + 1 : INT32_MAX / 2, mprv = nonempty ? u_right + 1 : 0; \
+      const int beg = max(max(0, min(mplv, qr) - w), u_beg); \
+      int end = min(min(Q, max(mprv, qr) + w), u_end + 1); \
+      end = max(end, beg - 1); \
       const int wd = end - beg + 1, sh = beg - u_beg;
+    if (!W32 && ((fl >> 18) & 1) && pv_ok) {
+      C3_BAND_OF_ROW_ABOVE
       // (64 cells of head room instead of wd: the stores below are not masked)
       if (__builtin_amdgcn_ballot_w64(((int)((unsigned)(wd - 1) < 64u) & (int)(wd + sh <= 64) & ((int)(sh >= 1) | (int)(u_end - u_beg < 63)) & (int)(u_ncell + 64 <= c.cells_cap) & (int)(!far || u_nfar + 64 <= c.far_cap()) & (int)(!WIDE || (max(beg - 1, 0) >= qwb && end <= qwb + PQW * 16))) != 0) != 0) {
         const int ro = u_ncell;
@@ -446,11 +450,97 @@ __device__ int poa_align(Ctx& c, const C3Params& P, int qb, int Q, int lane, lon
         }
         u_beg = beg; u_end = end; u_left = left; u_right = right; u_ncell = ro + wd; u_b8 = nb8;
 #ifdef C3_PHASE_PROF
-        { unsigned long long t_ = __builtin_readcyclecounter(); ph_acc_[8] += t_ - row_t0; row_t0 = t_; }
+        { unsigned long long t_ = __builtin_readcyclecounter(); ph_acc_[8] += t_ - row_t0; row_t0 = t_; ph_acc_[12] += 1; }
 #endif
         continue;
       }
     }
+    // ---- TWO-COLUMN ROW (NARROW): the same predecessor, but a band of 65-128 columns (a narrower row whose row above is not
+    // in registers takes the one-chunk near row, which hands its cells on to the fast rows after it; a two-column row cannot
+    // without spills).  Lane l owns the columns beg + 2l and beg + 2l + 1.  The row above is read from
+    // its LDS ring slot (written by every row up to 128 columns): the reads of the active columns stay inside that slot and
+    // its pads (column - u_beg lies in [-1, wd_above]), which hold NEG16 outside its band -- no validity compares, as in the
+    // near rows; lanes past the band read cells nobody uses.  Per lane: the two cells, an in-lane step of the F states
+    // (the lane's first column feeds its second), then the fast row's three interleaved DPP scans over the lanes.  Tie order,
+    // direction byte and cell type are the fast row's.
+    if (!WIDE && !W32 && ((fl >> 18) & 1) && c.two_col) {
+      C3_BAND_OF_ROW_ABOVE
+      if (__builtin_amdgcn_ballot_w64(((int)((unsigned)(wd - 65) < 64u) & (int)((unsigned)(u_end - u_beg) < (unsigned)PW) & (int)(u_ncell + 128 <= c.cells_cap) & (int)(!far || u_nfar + 128 <= c.far_cap())) != 0) != 0) {
+        const int ro = u_ncell;
+        int c0l = 2 * lane; UNI(c0l);                                            // the lane's first column - beg (computed here: derived
+                                                                                 // from the loop's lane constants it was a spill reload)
+        const bool act0 = c0l < wd, act1 = c0l + 1 < wd;
+        const int j0 = beg + c0l;
+        const int jq0 = max(j0 - 1, 0), jq1 = j0;                                // query bases of the two columns
+        const unsigned qw0 = Lqpk[min(jq0 >> 4, PQW - 1)], qw1 = Lqpk[min(jq1 >> 4, PQW - 1)];
+        const int rx = (slot == 0 ? PR - 1 : slot - 1) * PWT + PADL + sh + c0l;    // ring index of column j0 in the row above
+        const int hd0 = LH[rx - 1], hp0 = LH[rx], hp1 = LH[rx + 1];
+        const int e1p0 = LE1[rx], e1p1 = LE1[rx + 1], e2p0 = LE2[rx], e2p1 = LE2[rx + 1];
+        const int qc0 = (int)((qw0 >> ((jq0 & 15) * 2)) & 3), qc1 = (int)((qw1 >> ((jq1 & 15) * 2)) & 3);
+        const int M0 = hd0 + ((vb == qc0) ? mt8 + 2 : mm8 + 2), M1 = hp0 + ((vb == qc1) ? mt8 + 2 : mm8 + 2);
+        const int E1t0 = maxu16(hp0 - (oe1_8 - 1), e1p0 - e1_8), E1t1 = maxu16(hp1 - (oe1_8 - 1), e1p1 - e1_8);
+        const int E2t0 = maxu16(hp0 - (oe2_8 - 2), e2p0 - e2_8), E2t1 = maxu16(hp1 - (oe2_8 - 2), e2p1 - e2_8);
+        const int E1c0 = E1t0 & ~7, E2c0 = E2t0 & ~7, E1c1 = E1t1 & ~7, E2c1 = E2t1 & ~7;
+        const int k20 = maxu16(maxu16(M0, E1c0 + 1), E2c0), k21 = maxu16(maxu16(M1, E1c1 + 1), E2c1);
+        const int ht0 = k20 & ~7, ht1 = k21 & ~7;
+        const int htm0 = act0 ? ht0 : NEG2_16, htm1 = act1 ? ht1 : NEG2_16;
+        // F in lane coordinates as in the fast row, e * (column - beg) = e * c0l for the first column; the lane's value for the
+        // scans is the larger of its two columns' terms
+        const int l1 = e1_8 * c0l, l2 = e2_8 * c0l;
+        const int t10 = htm0 + l1, t20 = htm0 + l2;
+        int s1 = max(t10, htm1 + l1 + e1_8), s2 = max(t20, htm1 + l2 + e2_8), s3 = max(htm0, htm1);
+        wave_scan_max3(s1, s2, s3);
+        const int px1 = wave_shr1(s1, NEG2_16), px2 = wave_shr1(s2, NEG2_16);
+        const int f10 = px1 - o1_8 - l1, f20 = px2 - o2_8 - l2;
+        const int f11 = max(px1, t10) - (o1_8 + e1_8) - l1, f21 = max(px2, t20) - (o2_8 + e2_8) - l2;
+        const int htl0 = wave_shr1(htm1, NEG16);                                // Ht of column j0 - 1 (the second column of the lane before)
+        const int k30 = maxu16(maxu16(ht0 + 2, f10 + 1), f20), k31 = maxu16(maxu16(ht1 + 2, f11 + 1), f21);
+        const int h0 = k30 & ~7, h1 = k31 & ~7;
+        unsigned d0 = ((unsigned)E1t0 & 1u) | ((unsigned)E2t0 & 2u) | (((unsigned)k20 & 3u) << 2) | (((unsigned)k30 & 3u) << 4);
+        unsigned d1 = ((unsigned)E1t1 & 1u) | ((unsigned)E2t1 & 2u) | (((unsigned)k21 & 3u) << 2) | (((unsigned)k31 & 3u) << 4);
+        d0 |= (((unsigned)(htl0 - oe1_8 - f10)) >> 25) & 64u; d0 |= (((unsigned)(htl0 - oe2_8 - f20)) >> 24) & 128u;
+        d1 |= (((unsigned)(htm0 - oe1_8 - f11)) >> 25) & 64u; d1 |= (((unsigned)(htm0 - oe2_8 - f21)) >> 24) & 128u;
+        const int rb = __builtin_amdgcn_readlane(s3, 63);                       // row maximum (of Ht == of H)
+        const unsigned long long mx0 = __ballot(htm0 == rb), mx1 = __ballot(htm1 == rb);
+        const int left = beg + min(mx0 ? 2 * (int)__builtin_ctzll(mx0) : 256, mx1 ? 2 * (int)__builtin_ctzll(mx1) + 1 : 256);
+        const int right = beg + max(mx0 ? 2 * (63 - (int)__builtin_clzll(mx0)) : -1, mx1 ? 2 * (63 - (int)__builtin_clzll(mx1)) + 1 : -1);
+        int vH0 = maxu16(act0 ? h0 : NEG16, FLOOR16), vE10 = act0 ? E1c0 : NEG16, vE20 = act0 ? E2c0 : NEG16;
+        int vH1 = maxu16(act1 ? h1 : NEG16, FLOOR16), vE11 = act1 ? E1c1 : NEG16, vE21 = act1 ? E2c1 : NEG16;
+        int nb8 = u_b8;
+        if ((unsigned)(rb - RB_LO16) > (unsigned)c.rb_span) {         // rare (see the fast row): the base follows the row maximum, saturating
+          const int m1 = rb - BIAS16, fl1 = FLOOR16 + max(m1, 0);
+          nb8 += m1; punt |= (int)(rb < GLO16);
+          vH0 = act0 ? maxu16(h0, fl1) - m1 : NEG16; vE10 = act0 ? maxu16(E1c0, fl1) - m1 : NEG16; vE20 = act0 ? maxu16(E2c0, fl1) - m1 : NEG16;
+          vH1 = act1 ? maxu16(h1, fl1) - m1 : NEG16; vE11 = act1 ? maxu16(E1c1, fl1) - m1 : NEG16; vE21 = act1 ? maxu16(E2c1, fl1) - m1 : NEG16;
+        }
+        gacc = minu16(minu16(gacc, vH0 - (ZHI16 + 1)), vH1 - (ZHI16 + 1));
+        // unmasked stores: the row's 128 ring cells (NEG16 past the band) and 128 direction bytes (past the band: overwritten
+        // by the next rows / never selected)
+        c.D8()[(unsigned)(ro + c0l)] = (uint8_t)d0; c.D8()[(unsigned)(ro + c0l + 1)] = (uint8_t)d1;
+        { const int cb = slot * PWT + PADL + c0l;
+          LH[cb] = (unsigned short)vH0; LE1[cb] = (unsigned short)vE10; LE2[cb] = (unsigned short)vE20;
+          LH[cb + 1] = (unsigned short)vH1; LE1[cb + 1] = (unsigned short)vE11; LE2[cb + 1] = (unsigned short)vE21; }
+        if (lane == 0) {
+          L.meta[slot] = make_int4(beg, end, left, right); L.base8[slot] = nb8;
+          int off = 3 * idx; UNI(off);
+          int* rm = c.rowm() + off; rm[0] = beg; rm[1] = end; rm[2] = ro;                 // type 0: byte cells, one predecessor
+        }
+        if (far) {
+          const int fo = wave_first(u_nfar);
+          if (act0) { c.H()[fo + c0l] = cv_16to9(vH0, nb8); c.E1()[fo + c0l] = cv_16to9(vE10, nb8); c.E2()[fo + c0l] = cv_16to9(vE20, nb8); }
+          if (act1) { c.H()[fo + c0l + 1] = cv_16to9(vH1, nb8); c.E1()[fo + c0l + 1] = cv_16to9(vE11, nb8); c.E2()[fo + c0l + 1] = cv_16to9(vE21, nb8); }
+          if (lane == 0) { c.mpl()[idx] = left; c.mpr()[idx] = right; c.foff()[idx] = fo; }
+          u_nfar = fo + wave_first(wd);
+        }
+        u_beg = beg; u_end = end; u_left = left; u_right = right; u_ncell = ro + wd; u_b8 = nb8;
+        pv_ok = false;                                                          // (its cells are not in the fast row's layout)
+#ifdef C3_PHASE_PROF
+        { unsigned long long t_ = __builtin_readcyclecounter(); ph_acc_[15] += t_ - row_t0; row_t0 = t_; ph_acc_[12] += 1ull << 32; }
+#endif
+        continue;
+      }
+    }
+#undef C3_BAND_OF_ROW_ABOVE
     const int v = __builtin_amdgcn_readlane(dA.x, li);
     const int nin = (fl >> 8) & 0xff;
     const bool ovf = (fl >> 17) & 1;
@@ -599,7 +689,11 @@ __device__ int poa_align(Ctx& c, const C3Params& P, int qb, int Q, int lane, lon
       u_beg = beg; u_end = end; u_left = left; u_right = right; u_ncell = ro + wd; u_b8 = nb8;
 #endif
 #ifdef C3_PHASE_PROF
-      { unsigned long long t_ = __builtin_readcyclecounter(); ph_acc_[10] += t_ - row_t0; row_t0 = t_; }
+      { unsigned long long t_ = __builtin_readcyclecounter(); ph_acc_[10] += t_ - row_t0;
+        // row census: [12] fast | two-column rows (low | high half), [13] near rows of one | two chunks, [14] cycles of the
+        // two-chunk near rows, [15] cycles of the two-column rows
+        ph_acc_[13] += NCH == 1 ? 1ull : (1ull << 32); if (NCH > 1) ph_acc_[14] += t_ - row_t0;
+        row_t0 = t_; }
 #endif
       return true;
       };
@@ -1082,7 +1176,7 @@ __global__ __launch_bounds__(64, C3_POA_WAVES) void k_poa(PoaArgs a) {
   c.far_shift = W32 ? 0 : 2;
   c.C = a.cellsb + (size_t)slot * (2 * (size_t)a.cells_cap + 16 * (size_t)(a.cells_cap >> c.far_shift)); c.B8 = a.bbase + (size_t)slot * 5 * N;
   c.score_ = a.score + (size_t)slot * N; c.desc_ = a.desc + (size_t)slot * 2 * N; c.jump_ = a.jump + (size_t)slot * C3_JUMP_LEVELS * N;
-  c.K = a.K; c.Ncap = a.Ncap; c.cells_cap = a.cells_cap; c.osel = 0; c.rb_span = a.rb_span > 0 ? a.rb_span : RB_HI16 - RB_LO16;
+  c.K = a.K; c.Ncap = a.Ncap; c.cells_cap = a.cells_cap; c.osel = 0; c.rb_span = a.rb_span > 0 ? a.rb_span : RB_HI16 - RB_LO16; c.two_col = !a.no2col;
 #ifdef C3_DEBUG_PUNT
   c.dbg = a.phases;
 #endif

@@ -40,4 +40,13 @@ for which, kn in ((0, "k_poa"), (1, "k_window")):
             print("   band traceback: %d blocks, load+sync %.0f cycles per block (%.1f%% of the wave time), %.1f steps per block, %.0f cycles per step (%.1f%%)" % (
                 out[12], out[13] / out[12], 100.0 * out[13] / tot, out[14] / out[12], out[15] / max(out[14], 1), 100.0 * out[15] / tot))
     if which == 0 and out[1]:
-        print("   DP rows by kind (cycles): fast %.1f%%, near %.1f%%, general %.1f%% of the row loop" % tuple(100.0 * out[i] / max(out[8] + out[10] + out[11], 1) for i in (8, 10, 11)))
+        print("   DP rows by kind (cycles): fast %.1f%%, two-column %.1f%%, near %.1f%%, general %.1f%% of the row loop" % tuple(100.0 * out[i] / max(out[8] + out[10] + out[11] + out[15], 1) for i in (8, 15, 10, 11)))
+        lo = lambda x: x & 0xffffffff
+        hi = lambda x: x >> 32
+        nf, n2c, n1, n2 = lo(out[12]), hi(out[12]), lo(out[13]), hi(out[13])
+        if nf + n2c + n1 + n2:
+            rows = nf + n2c + n1 + n2           # (+ the general rows, ~0.1 %: not counted)
+            print("   rows %d: fast %.1f%%, two-column %.1f%%, near one chunk %.1f%%, near two chunks %.1f%%" % (
+                rows, 100.0 * nf / rows, 100.0 * n2c / rows, 100.0 * n1 / rows, 100.0 * n2 / rows))
+            print("   cycles per row: fast %.0f, two-column %.0f, near one chunk %.0f, near two chunks %.0f; near rows %.1f%%, two-column rows %.1f%% of the wave time" % (
+                out[8] / max(nf, 1), out[15] / max(n2c, 1), (out[10] - out[14]) / max(n1, 1), out[14] / max(n2, 1), 100.0 * out[10] / tot, 100.0 * out[15] / tot))
