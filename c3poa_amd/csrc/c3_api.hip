@@ -130,8 +130,14 @@ static inline double dbg_now_ms() { using namespace std::chrono; return duration
 
 // ---- handle -----------------------------------------------------------------------------
 static thread_local double g_alloc_ms = 0.0;   // host time spent growing device buffers (hipFree synchronises the device)
-struct DBuf {
+struct DBuf {                                   // owns one device allocation (move-only)
   void* p = nullptr; size_t cap = 0;
+  DBuf() = default;
+  DBuf(DBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DBuf& operator=(DBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+  DBuf(const DBuf&) = delete;
+  DBuf& operator=(const DBuf&) = delete;
+  ~DBuf() { if (p) (void)hipFree(p); }
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     const double t0 = dbg_now_ms();
@@ -145,7 +151,6 @@ struct DBuf {
     g_alloc_ms += dbg_now_ms() - t0;
     return e;
   }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
   template <class T> T* as() const { return (T*)p; }
 };
 
@@ -160,7 +165,7 @@ struct c3_handle {
   DBuf d_info_snap, d_coff_part;
   struct Staged { DBuf d_ascii, d_pk, d_woff, d_qual, d_off, d_strand, d_sid; std::vector<int64_t> off, woff; std::vector<int16_t> sid; std::string strand;
                   int n = 0; int64_t total = 0, words = 0, maxL = 0; bool pending = false; } st;
-  hipEvent_t ev[EV_N];
+  hipEvent_t ev[EV_N] = {};
   // splints
   int n_spl = 0, max_spl = 0; std::vector<int> sp_len; DBuf d_sp_codes, d_sp_len;
   // batch
@@ -170,7 +175,7 @@ struct c3_handle {
   DBuf s_poa_i, s_poa_nk, s_poa_cells, s_poa_b, s_poa_sc, s_poa_desc, s_poa_jump, s_poa_path, d_overflow;      // POA scratch
   int n_poa_redo = 0;        // reads of the last run that needed the full-size second POA pass
   int n_poa_redo16 = 0;      // ... of them: because a score left the 16-bit cells
-  DBuf s_eH, s_eD, s_lw, d_wrec, d_wlay, d_wbase, d_wout;       // prep / windows
+  DBuf s_eD, s_lw, d_wrec, d_wlay, d_wbase, d_wout;       // prep / windows
   DBuf s_win_i, s_win_nk, s_win_h, s_win_d, s_win_b, s_win_sc, s_win_desc, s_win_h2, s_win_d2, d_wovf;
   DBuf s_zero_d, d_zinfo, d_zflag, d_zwork; std::vector<int> zwork;  // zero-repeat rescue: k_zero direction bytes, per-read records, work list
   DBuf s_zero_l;                                                      // k_zero_long slots
@@ -193,6 +198,15 @@ static int c3_hip_fail(c3_handle* h, hipError_t e, const char* what, int line) {
   return C3_E_HIP;
 }
 static int c3_fail(c3_handle* h, int code, const char* msg) { if (h) h->err = msg; return code; }
+
+// the device counter block (C3Counters, c3_args.h): zeroed and read by field
+static C3Counters* dev_cnt(c3_handle* h) { return h->d_counter.as<C3Counters>(); }
+template <class T> static hipError_t zero_cnt(c3_handle* h, T* field) { return hipMemsetAsync(field, 0, sizeof(T), h->stream); }
+static hipError_t zero_counters(c3_handle* h) { return hipMemsetAsync(h->d_counter.p, 0, sizeof(C3Counters), h->stream); }
+static hipError_t read_counters(c3_handle* h, C3Counters* c) {
+  hipError_t e = hipMemcpyAsync(c, h->d_counter.p, sizeof(*c), hipMemcpyDeviceToHost, h->stream);
+  return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
+}
 
 extern "C" void c3_default_config(c3_config* c) {
   memset(c, 0, sizeof(*c));
@@ -233,47 +247,38 @@ extern "C" int c3_create(const c3_config* cfg, c3_handle** out) {
   if (cfg->zero_max_cells < 1 || cfg->zero_max_cells > INT32_MAX) { g_create_err = "zero_max_cells must be 1..2147483647"; return C3_E_ARG; }
   c3_handle* h = new c3_handle();
   h->cfg = *cfg;
-  if ((e = hipSetDevice(cfg->device)) != hipSuccess) { g_create_err = hipGetErrorString(e); delete h; return C3_E_HIP; }
-  // synchronisation points sleep instead of spinning: the stages are milliseconds long, and a spinning waiter per
-  // handle eats the CPU quota the reader / writer threads need (refused once the context exists: ignored)
-  (void)hipSetDeviceFlags(hipDeviceScheduleBlockingSync); (void)hipGetLastError();
   hipDeviceProp_t prop;
-  if ((e = hipGetDeviceProperties(&prop, cfg->device)) != hipSuccess) { g_create_err = hipGetErrorString(e); delete h; return C3_E_HIP; }
+  e = hipSetDevice(cfg->device);
+  if (e == hipSuccess) {
+    // synchronisation points sleep instead of spinning: the stages are milliseconds long, and a spinning waiter per
+    // handle eats the CPU quota the reader / writer threads need (refused once the context exists: ignored)
+    (void)hipSetDeviceFlags(hipDeviceScheduleBlockingSync); (void)hipGetLastError();
+    e = hipGetDeviceProperties(&prop, cfg->device);
+  }
+  if (e == hipSuccess) e = hipStreamCreate(&h->stream);
+  if (e == hipSuccess) e = hipStreamCreate(&h->stream_up);
+  if (e == hipSuccess) e = hipStreamCreate(&h->stream_dn);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_dn, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_tot, 64, hipHostMallocDefault);
+  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev_up[i]);
+  for (int i = 0; i < EV_N && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
+  if (e != hipSuccess) { g_create_err = hipGetErrorString(e); c3_destroy(h); return C3_E_HIP; }
   h->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   h->mem_total = prop.totalGlobalMem;
-  if ((e = hipStreamCreate(&h->stream)) != hipSuccess) { g_create_err = hipGetErrorString(e); delete h; return C3_E_HIP; }
-  if ((e = hipStreamCreate(&h->stream_up)) != hipSuccess) { g_create_err = hipGetErrorString(e); delete h; return C3_E_HIP; }
-  if ((e = hipStreamCreate(&h->stream_dn)) != hipSuccess) { g_create_err = hipGetErrorString(e); delete h; return C3_E_HIP; }
-  if ((e = hipEventCreateWithFlags(&h->ev_dn, hipEventDisableTiming)) != hipSuccess) { g_create_err = hipGetErrorString(e); delete h; return C3_E_HIP; }
-  if ((e = hipHostMalloc((void**)&h->h_tot, 64, hipHostMallocDefault)) != hipSuccess) { g_create_err = hipGetErrorString(e); delete h; return C3_E_HIP; }
-  for (int i = 0; i < 2; ++i) if ((e = hipEventCreate(&h->ev_up[i])) != hipSuccess) { g_create_err = hipGetErrorString(e); delete h; return C3_E_HIP; }
-  for (int i = 0; i < EV_N; ++i) if ((e = hipEventCreate(&h->ev[i])) != hipSuccess) { g_create_err = hipGetErrorString(e); delete h; return C3_E_HIP; }
   memset(&h->tm, 0, sizeof(h->tm));
   *out = h;
   return C3_E_OK;
 }
 
+// also takes a handle that c3_create left half made (null members); the device buffers free themselves (DBuf)
 extern "C" void c3_destroy(c3_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->cfg.device);
-  (void)hipStreamSynchronize(h->stream);
-  if (h->stream_dn) { (void)hipStreamSynchronize(h->stream_dn); (void)hipStreamDestroy(h->stream_dn); }
-  if (h->ev_dn) (void)hipEventDestroy(h->ev_dn);
+  for (hipStream_t s : {h->stream, h->stream_up, h->stream_dn}) if (s) (void)hipStreamSynchronize(s);
+  for (hipStream_t s : {h->stream, h->stream_up, h->stream_dn}) if (s) (void)hipStreamDestroy(s);
+  for (hipEvent_t ev : {h->ev_dn, h->ev_up[0], h->ev_up[1], h->ev_qv[0], h->ev_qv[1]}) if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : h->ev) if (ev) (void)hipEventDestroy(ev);
   if (h->h_tot) (void)hipHostFree(h->h_tot);
-  h->d_info_snap.release(); h->d_coff_part.release(); h->s_win_h2.release(); h->s_win_d2.release(); h->d_wovf.release();
-  DBuf* all[] = {&h->d_sp_codes, &h->d_sp_len, &h->d_ascii, &h->d_pk, &h->d_woff, &h->d_qual, &h->d_off, &h->d_strand, &h->d_sid,
-                 &h->d_info, &h->d_track, &h->d_draft, &h->d_tpos, &h->d_cons, &h->d_counter, &h->d_raw, &h->d_nraw, &h->d_sum,
-                 &h->d_work, &h->d_bufA, &h->d_bufB, &h->d_cand, &h->d_cst, &h->d_msa, &h->d_msa_off, &h->d_msa_len,
-                 &h->s_poa_i, &h->s_poa_nk, &h->s_poa_cells, &h->s_poa_b, &h->s_poa_sc, &h->s_poa_desc, &h->s_poa_jump, &h->s_poa_path, &h->d_overflow, &h->s_eH, &h->s_eD, &h->s_lw, &h->d_wrec,
-                 &h->d_wlay, &h->d_wbase, &h->d_wout, &h->s_win_i, &h->s_win_nk, &h->s_win_h, &h->s_win_d, &h->s_win_b, &h->s_win_sc, &h->s_win_desc, &h->s_zero_d, &h->s_zero_l, &h->d_zinfo, &h->d_zflag, &h->d_zwork, &h->d_gather, &h->d_gather_off,
-                 &h->d_dmx_heads, &h->d_dmx_meta, &h->d_dmx_out, &h->d_qv, &h->s_qv_dirs, &h->s_qv_g, &h->d_qv_cnt, &h->d_gather_qv};
-  for (DBuf* b : all) b->release();
-  { DBuf* sh[] = {&h->st.d_ascii, &h->st.d_pk, &h->st.d_woff, &h->st.d_qual, &h->st.d_off, &h->st.d_strand, &h->st.d_sid}; for (DBuf* b : sh) b->release(); }
-  if (h->stream_up) { (void)hipStreamSynchronize(h->stream_up); (void)hipStreamDestroy(h->stream_up); }
-  for (int i = 0; i < 2; ++i) if (h->ev_up[i]) (void)hipEventDestroy(h->ev_up[i]);
-  for (int i = 0; i < EV_N; ++i) (void)hipEventDestroy(h->ev[i]);
-  for (int i = 0; i < 2; ++i) if (h->ev_qv[i]) (void)hipEventDestroy(h->ev_qv[i]);
-  (void)hipStreamDestroy(h->stream);
   delete h;
 }
 
@@ -380,7 +385,7 @@ extern "C" int c3_batch_commit(c3_handle* h) {
   t.pending = false;
   const int n = h->n;
   HIPCHK(h->d_info.ensure(sizeof(C3Info) * (size_t)n));
-  HIPCHK(h->d_counter.ensure(256));
+  HIPCHK(h->d_counter.ensure(sizeof(C3Counters)));
   HIPCHK(hipMemsetAsync(h->d_info.p, 0, sizeof(C3Info) * (size_t)n, h->stream));   // the unused tails of peaks[] / sub_*[] read as 0
   hipLaunchKernelGGL(k_init_info, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_info.as<C3Info>(), n);
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -431,9 +436,9 @@ static int auto_slots(c3_handle* h, int want, size_t per_slot_bytes, int n_items
 
 static int run_conk(c3_handle* h) {
   HIPCHK(h->d_track.ensure(sizeof(int32_t) * (size_t)h->total + 64));
-  HIPCHK(hipMemsetAsync(h->d_counter.p, 0, 64, h->stream));
+  HIPCHK(zero_cnt(h, &dev_cnt(h)->queue));
   ConkArgs a; a.b = dev_batch(h); a.sp_codes = h->d_sp_codes.as<uint8_t>(); a.sp_len = h->d_sp_len.as<int>();
-  a.track = h->d_track.as<int32_t>(); a.info = h->d_info.as<C3Info>(); a.counter = h->d_counter.as<int>();
+  a.track = h->d_track.as<int32_t>(); a.info = h->d_info.as<C3Info>(); a.cnt = dev_cnt(h);
   a.match = h->cfg.conk_match; a.mismatch = h->cfg.conk_mismatch; a.penalty = h->cfg.conk_penalty; a.n_spl = h->n_spl; a.scan = nullptr;
   int waves = std::min(h->n, h->n_cus * 32);
   c3k_launch_conk(&a, h->max_spl, (waves + 3) / 4, 0, h->stream);
@@ -462,8 +467,8 @@ static int run_peaks(c3_handle* h) {
   a.raw_peaks = h->d_raw.as<int32_t>(); a.n_raw = h->d_nraw.as<int32_t>(); a.sp_len = h->d_sp_len.as<int>();
   savgol_coeffs(h->cfg.sg_window, a.coef);
   a.maxL = (int64_t)mL; a.window = h->cfg.sg_window; a.iters = h->cfg.sg_iters; a.min_dist = h->cfg.mdistcutoff;
-  a.queue = h->d_counter.as<int>() + 60;
-  HIPCHK(hipMemsetAsync(a.queue, 0, sizeof(int), h->stream));
+  a.cnt = dev_cnt(h);
+  HIPCHK(zero_cnt(h, &a.cnt->peaks_queue));
   c3k_launch_peaks(&a, grid, h->stream);
   HIPCHK(hipGetLastError());
   return 0;
@@ -494,7 +499,7 @@ static int copy_summary(c3_handle* h) {
 
 static void fill_zero_args(c3_handle* h, ZeroArgs& z, int nz) {
   memset(&z, 0, sizeof(z));
-  z.b = dev_batch(h); z.info = h->d_info.as<C3Info>(); z.p = dev_params(h->cfg); z.counter = h->d_counter.as<int>();
+  z.b = dev_batch(h); z.info = h->d_info.as<C3Info>(); z.p = dev_params(h->cfg); z.cnt = dev_cnt(h);
   z.work = h->d_zwork.as<int>(); z.n_work = nz;
   z.D = h->s_zero_d.as<uint8_t>(); z.zinfo = h->d_zinfo.as<int4>(); z.zflag = h->d_zflag.as<uint8_t>();
   z.draft = h->d_draft.as<uint8_t>(); z.cons = h->d_cons.as<char>();
@@ -566,7 +571,7 @@ static int fetch_summary(c3_handle* h) {
   if (rc) return rc;
   const auto wl0 = std::chrono::steady_clock::now();
   struct WlTimer { c3_handle* h; std::chrono::steady_clock::time_point t0; ~WlTimer() { h->tm.ms_host_worklist = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); } } wl_timer_{h, wl0};
-  HIPCHK(hipMemsetAsync(h->d_counter.p, 0, 64, h->stream));
+  HIPCHK(zero_cnt(h, &dev_cnt(h)->zero_cells));
   if ((rc = run_zero(h))) return rc;
   const int n = h->n;
   h->work.clear();
@@ -604,24 +609,20 @@ static int fetch_summary(c3_handle* h) {
 
 // one launch of k_poa over `nw` reads of `d_work` with the given capacities
 static int launch_poa(c3_handle* h, const int* d_work, int nw, int Ncap, int K, int Pcap, long long cells, int* d_overflow, int* d_overflow16, int waves_per_cu, int wide_ring) {
-  const size_t N = (size_t)Ncap;
-  const int NI = 19;      // int arrays of N (c3_args.h)
   cells = (cells + 15) & ~15LL;                   // every per-slot arena starts 16-byte aligned
   cells = (cells + 63) & ~63LL;
   // far arena (32-bit cells of rows with a successor beyond the LDS ring, rows wider than a ring slot, rows with > 4 predecessors):
   // a quarter of the cells in the first pass (a few per cent are used), all of them in the 32-bit pass, where every row is far
   const bool w32 = d_overflow16 == nullptr || getenv("C3_DEBUG_POA32");      // the pass that takes the reads beyond 16 bits (test hook: every pass)
-  const long long far = w32 ? cells : cells >> 2;
-  const size_t per_slot = N * (NI * 4 + 8 + 5 + 32 + 4 * C3_JUMP_LEVELS) + N * K * 12 + (size_t)cells * 2 + (size_t)far * 16 + (size_t)Pcap * 4;
-  const int slots = auto_slots(h, h->cfg.slots_poa, per_slot, nw, waves_per_cu);
-  HIPCHK(h->s_poa_i.ensure(sizeof(int) * N * NI * slots)); HIPCHK(h->s_poa_nk.ensure(sizeof(int) * N * K * 3 * slots));
-  HIPCHK(h->s_poa_cells.ensure(((size_t)cells * 2 + (size_t)far * 16) * slots + 256)); HIPCHK(h->s_poa_b.ensure(N * 5 * slots)); HIPCHK(h->s_poa_sc.ensure(sizeof(long long) * N * slots));
-  HIPCHK(h->s_poa_desc.ensure(sizeof(uint4) * 2 * N * slots));
-  HIPCHK(h->s_poa_jump.ensure(sizeof(int) * C3_JUMP_LEVELS * N * slots));
-  HIPCHK(h->s_poa_path.ensure(sizeof(int) * (size_t)Pcap * slots));
+  const PoaLayout L = c3_poa_layout(Ncap, K, (int)cells, c3_poa_far_shift(w32), Pcap);
+  const int slots = auto_slots(h, h->cfg.slots_poa, L.total, nw, waves_per_cu);
+  const size_t S = (size_t)slots;
+  HIPCHK(h->s_poa_i.ensure(L.ints * S)); HIPCHK(h->s_poa_nk.ensure(L.edges * S));
+  HIPCHK(h->s_poa_cells.ensure(L.cells * S + 256)); HIPCHK(h->s_poa_b.ensure(L.bases * S)); HIPCHK(h->s_poa_sc.ensure(L.score * S));
+  HIPCHK(h->s_poa_desc.ensure(L.desc * S)); HIPCHK(h->s_poa_jump.ensure(L.jump * S)); HIPCHK(h->s_poa_path.ensure(L.path * S));
   PoaArgs a; memset(&a, 0, sizeof(a));
   a.b = dev_batch(h); a.info = h->d_info.as<C3Info>(); a.p = dev_params(h->cfg);
-  a.counter = h->d_counter.as<int>(); a.work = d_work; a.n_work = nw;
+  a.cnt = dev_cnt(h); a.work = d_work; a.n_work = nw;
   a.ibase = h->s_poa_i.as<int>(); a.ebase = h->s_poa_nk.as<int>(); a.cellsb = h->s_poa_cells.as<char>();
   a.bbase = h->s_poa_b.as<uint8_t>(); a.score = h->s_poa_sc.as<long long>();
   a.Ncap = Ncap; a.K = K; a.Pcap = Pcap; a.cells_cap = (int)cells; a.desc = h->s_poa_desc.as<uint4>(); a.jump = h->s_poa_jump.as<int>();
@@ -631,8 +632,7 @@ static int launch_poa(c3_handle* h, const int* d_work, int nw, int Ncap, int K, 
   a.draft = h->d_draft.as<uint8_t>(); a.tpos = h->d_tpos.as<int32_t>();
   a.msa_dbg = nullptr; a.msa_off = nullptr; a.msa_len = nullptr;
   if (h->debug_msa) { a.msa_dbg = h->d_msa.as<uint8_t>(); a.msa_off = h->d_msa_off.as<int64_t>(); a.msa_len = h->d_msa_len.as<int>(); }
-  a.phases = (unsigned long long*)(h->d_counter.as<char>() + 64);
-  DBG("poa: nw=%d Ncap=%d K=%d cells=%lld slots=%d (%.1f MB per slot)%s\n", nw, Ncap, K, cells, slots, per_slot / 1048576.0, d_overflow ? "" : (d_overflow16 ? " [full-size pass]" : " [32-bit pass]"));
+  DBG("poa: nw=%d Ncap=%d K=%d cells=%lld slots=%d (%.1f MB per slot)%s\n", nw, Ncap, K, cells, slots, L.total / 1048576.0, d_overflow ? "" : (d_overflow16 ? " [full-size pass]" : " [32-bit pass]"));
   // the pass with an overflow list runs the 16-bit rows; the final pass (no list) the 32-bit rows only (C3_DEBUG_POA32: test hook, first pass too)
   c3k_launch_poa(&a, slots, w32 ? 1 : 0, wide_ring, h->stream);
   HIPCHK(hipGetLastError());
@@ -671,8 +671,9 @@ static int run_poa(c3_handle* h) {
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   HIPCHK(h->d_overflow.ensure(sizeof(int) * 2 * (size_t)nw));
-  HIPCHK(hipMemsetAsync(h->d_counter.p, 0, 4, h->stream));                       // work queue only: [2..3] already holds the zero-repeat cells
-  HIPCHK(hipMemsetAsync(h->d_counter.as<char>() + 16, 0, 240, h->stream));       // [4] overflow count, phase counters
+  C3Counters* dc = dev_cnt(h);        // (zero_cells of run_zero stay: tm.cells_poa counts them)
+  HIPCHK(zero_cnt(h, &dc->queue)); HIPCHK(zero_cnt(h, &dc->cells)); HIPCHK(zero_cnt(h, &dc->poa_ovf)); HIPCHK(zero_cnt(h, &dc->poa_ovf16));
+  HIPCHK(zero_cnt(h, &dc->phases));
   // ring geometry of the first pass: subreads beyond the LDS query copy (1792 bases) or with bands beyond two 64-column chunks
   // (w = band_b + band_f * Q; a row holds 2w+1 columns + the drift of its predecessors' maxima) take the WIDE instance
   // (4 ring rows of 192 cells, sliding query window); C3_DEBUG_POA_WIDE = 0 / 1 forces one (test hook)
@@ -684,29 +685,25 @@ static int run_poa(c3_handle* h) {
   int rc = launch_poa(h, h->d_work.as<int>(), nw, Ncap, K, Pcap, cells, ovA, ovB, 24, wide_ring);
   if (rc) return rc;
   h->n_poa_redo = 0; h->n_poa_redo16 = 0;
-  {
-    int cnt[8];
-    HIPCHK(hipMemcpyAsync(cnt, h->d_counter.p, 32, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (cnt[4] > 0) {
-      h->n_poa_redo = cnt[4];
-      HIPCHK(hipMemsetAsync(h->d_counter.p, 0, 4, h->stream));
-      if ((rc = launch_poa(h, ovA, cnt[4], Ncap_full, K, Pcap, cells_full, nullptr, ovB, 24, wide_ring))) return rc;
-      HIPCHK(hipMemcpyAsync(cnt, h->d_counter.p, 32, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    if (cnt[5] > 0) {
-      h->n_poa_redo += cnt[5]; h->n_poa_redo16 = cnt[5];
-      HIPCHK(hipMemsetAsync(h->d_counter.p, 0, 4, h->stream));
-      if ((rc = launch_poa(h, ovB, cnt[5], Ncap_full, K, Pcap, cells_full, nullptr, nullptr, 24, 0))) return rc;
-    }
+  C3Counters c;
+  HIPCHK(read_counters(h, &c));
+  if (c.poa_ovf > 0) {
+    h->n_poa_redo = c.poa_ovf;
+    HIPCHK(zero_cnt(h, &dc->queue));
+    if ((rc = launch_poa(h, ovA, c.poa_ovf, Ncap_full, K, Pcap, cells_full, nullptr, ovB, 24, wide_ring))) return rc;
+    HIPCHK(read_counters(h, &c));
+  }
+  if (c.poa_ovf16 > 0) {
+    h->n_poa_redo += c.poa_ovf16; h->n_poa_redo16 = c.poa_ovf16;
+    HIPCHK(zero_cnt(h, &dc->queue));
+    if ((rc = launch_poa(h, ovB, c.poa_ovf16, Ncap_full, K, Pcap, cells_full, nullptr, nullptr, 24, 0))) return rc;
   }
   if (!h->zwork.empty()) {             // zero-repeat rescue, second half: stitch left + overlap consensus + right
     ZeroArgs z; fill_zero_args(h, z, (int)h->zwork.size());
     c3k_launch_zero_finish(&z, std::min((int)h->zwork.size(), 512), h->stream);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipMemcpyAsync(h->phase_poa, h->d_counter.as<char>() + 64, 128, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(h->phase_poa, dc->phases, sizeof(h->phase_poa), hipMemcpyDeviceToHost, h->stream));
   return 0;
 }
 
@@ -731,25 +728,24 @@ static int run_polish(c3_handle* h, float* ms_prep, float* ms_win, float* ms_st)
   HIPCHK(h->d_wbase.ensure(sizeof(int) * (size_t)h->n));
   PrepArgs p; memset(&p, 0, sizeof(p));
   p.b = dev_batch(h); p.info = h->d_info.as<C3Info>(); p.p = dev_params(h->cfg);
-  p.counter = h->d_counter.as<int>(); p.work = h->d_work.as<int>(); p.n_work = nw;
+  p.cnt = dev_cnt(h); p.work = h->d_work.as<int>(); p.n_work = nw;
   p.draft = h->d_draft.as<uint8_t>(); p.tpos = h->d_tpos.as<int32_t>();
-  p.eH = h->s_eH.as<int32_t>(); p.eD = h->s_eD.as<uint8_t>(); p.ecap = ecap;
+  p.eD = h->s_eD.as<uint8_t>(); p.ecap = ecap;
   p.lw_first = h->s_lw.as<int>(); p.lw_last = p.lw_first + (size_t)NLcap * NWcap * slots_p; p.NLcap = NLcap; p.NWcap = NWcap;
   p.wrec = h->d_wrec.as<WinRec>(); p.wlay = h->d_wlay.as<WLayer>(); p.win_base = h->d_wbase.as<int>();
-  p.n_windows = h->d_counter.as<int>() + 8; p.wcap = (int)std::min<long long>(wcap, 0x7fffffff);
-  HIPCHK(hipMemsetAsync(h->d_counter.p, 0, 64, h->stream));
+  p.wcap = (int)std::min<long long>(wcap, 0x7fffffff);
+  HIPCHK(zero_counters(h));
   HIPCHK(hipEventRecord(h->ev[5], h->stream));
   DBG("prep: slots=%d ecap=%lld NL=%d NW=%d wcap=%lld\n", slots_p, (long long)ecap, NLcap, NWcap, (long long)wcap);
   c3k_launch_prep(&p, slots_p, h->stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(h->ev[6], h->stream));
-  int cnt[16];
-  HIPCHK(hipMemcpyAsync(cnt, h->d_counter.p, 64, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  h->tm.cells_polish += *(long long*)(cnt + 2); h->tm.cells_polish_computed += *(long long*)(cnt + 2);       // dangling-piece extensions
+  C3Counters c;
+  HIPCHK(read_counters(h, &c));
+  h->tm.cells_polish += c.cells; h->tm.cells_polish_computed += c.cells;       // dangling-piece extensions
   // k_prep reserves windows with an atomicAdd BEFORE its capacity check: after an overflow the counter exceeds wcap, and
   // the records past wcap were never written (the reads that overflowed carry C3_ST_LIMIT and n_win = 0)
-  const int n_win = (int)std::min<long long>(cnt[8], std::min<long long>(wcap, 0x7fffffff));
+  const int n_win = (int)std::min<long long>(c.n_windows, std::min<long long>(wcap, 0x7fffffff));
   h->n_windows = n_win;
   DBG("prep done: n_win=%d\n", n_win);
   const int wout_cap = 3 * WL + 64;
@@ -767,21 +763,19 @@ static int run_polish(c3_handle* h, float* ms_prep, float* ms_win, float* ms_st)
     const int R_typ = std::min(Ncap, WL + WL / 4 + 30 * NLcap + 64);
     long long hcap = std::min(hcap_full, (long long)(R_typ + R_typ / 2 + 4) * 256);      // (a window in the second launch runs alone on an idle device, ~1.5 ms: sized so that a usual batch has none -- at + R_typ / 4 one cfg2 window in 400 000 took it)
     if (const char* e = getenv("C3_DEBUG_HCAP_DIV")) hcap = std::max(4096LL, hcap_full / std::max(1, atoi(e)) / 64 * 64);       // test hook: smaller first-launch scratch (more windows take the second launch)
-    const size_t N = (size_t)Ncap;
-    const int NI = 19;      // W_INTS of k_polish.hip
-    const size_t per_slot = N * (NI * 4 + 8 + 2) + N * K * 16 + (size_t)hcap * 5;
-    const int slots = auto_slots(h, h->cfg.slots_win, per_slot, n_win, 20);
+    const WinLayout L = c3_win_layout(Ncap, K, hcap), L2 = c3_win_layout(Ncap, K, hcap_full);
+    const int slots = auto_slots(h, h->cfg.slots_win, L.total, n_win, 20);
     const int slots2 = hcap < hcap_full ? std::min(slots, 256) : 0;
-    HIPCHK(h->s_win_i.ensure(sizeof(int) * N * NI * slots + 64)); HIPCHK(h->s_win_nk.ensure(sizeof(int) * N * K * 4 * slots));
-    HIPCHK(h->s_win_h.ensure(sizeof(int32_t) * (size_t)hcap * slots)); HIPCHK(h->s_win_d.ensure((size_t)hcap * slots + 256));
-    HIPCHK(h->s_win_b.ensure(N * 2 * slots)); HIPCHK(h->s_win_sc.ensure(sizeof(long long) * N * slots));
-    HIPCHK(h->s_win_desc.ensure(sizeof(uint4) * (N + 1) * slots));
-    if (slots2) {
-      HIPCHK(h->s_win_h2.ensure(sizeof(int32_t) * (size_t)hcap_full * slots2)); HIPCHK(h->s_win_d2.ensure((size_t)hcap_full * slots2 + 256));
+    const size_t S = (size_t)slots, S2 = (size_t)slots2;
+    HIPCHK(h->s_win_i.ensure(L.ints * S + 64)); HIPCHK(h->s_win_nk.ensure(L.edges * S));
+    HIPCHK(h->s_win_h.ensure(L.H * S)); HIPCHK(h->s_win_d.ensure(L.D * S + 256));
+    HIPCHK(h->s_win_b.ensure(L.bases * S)); HIPCHK(h->s_win_sc.ensure(L.score * S)); HIPCHK(h->s_win_desc.ensure(L.desc * S));
+    if (slots2) {                      // the second launch: worst-case DP cells on fewer slots, the other regions shared
+      HIPCHK(h->s_win_h2.ensure(L2.H * S2)); HIPCHK(h->s_win_d2.ensure(L2.D * S2 + 256));
       HIPCHK(h->d_wovf.ensure(sizeof(int) * (size_t)n_win));
     }
     WinArgs a; memset(&a, 0, sizeof(a));
-    a.b = dev_batch(h); a.p = dev_params(h->cfg); a.counter = h->d_counter.as<int>(); a.n_win = n_win;
+    a.b = dev_batch(h); a.p = dev_params(h->cfg); a.cnt = dev_cnt(h); a.n_win = n_win;
     a.wrec_in = h->d_wrec.as<WinRec>(); a.wrec = h->d_wrec.as<WinRec>(); a.wlay = h->d_wlay.as<WLayer>(); a.NLcap = NLcap;
     a.draft = h->d_draft.as<uint8_t>();
     a.ibase = h->s_win_i.as<int>(); a.ebase = h->s_win_nk.as<int>();
@@ -789,19 +783,18 @@ static int run_polish(c3_handle* h, float* ms_prep, float* ms_win, float* ms_st)
     a.H = h->s_win_h.as<int32_t>(); a.D = h->s_win_d.as<uint16_t>(); a.rdesc = h->s_win_desc.as<uint4>(); a.Ncap = Ncap; a.K = K; a.hcap = hcap; a.Lcap = std::min(std::min(Ncap, 2 * WL + 30 * NLcap), ((getenv("C3_DEBUG_WIN_LDS") ? atoi(getenv("C3_DEBUG_WIN_LDS")) : 6656) - 16) / 6);       // (LDS per wave capped at 6.5 KB: at cfg4 the uncapped sweep arrays took 8.5 KB and k_window ran 7 % slower; larger graphs use the global-scratch sweep)
     if (const char* e = getenv("C3_DEBUG_WIN_LCAP")) a.Lcap = std::max(64, std::min(Ncap, atoi(e)));   // test hook: forces the global-scratch consensus path
     a.wout = h->d_wout.as<uint8_t>(); a.wout_cap = wout_cap;
-    HIPCHK(hipMemsetAsync(h->d_counter.p, 0, 256, h->stream));
-    a.phases = (unsigned long long*)(h->d_counter.as<char>() + 64);
+    HIPCHK(zero_counters(h));
     if (const char* e = getenv("C3_DEBUG_BAND")) a.band_mode = !strcmp(e, "off") ? 1 : !strcmp(e, "fail") ? 2 : !strcmp(e, "verify") ? 3 : 0;    // test hook (tests/test_gpu_band.py)
     a.ovf_list = slots2 ? h->d_wovf.as<int>() : nullptr;
     c3k_launch_window(&a, slots, h->stream);
     HIPCHK(hipGetLastError());
     if (slots2) {
       a.H = h->s_win_h2.as<int32_t>(); a.D = h->s_win_d2.as<uint16_t>(); a.hcap = hcap_full;
-      a.wlist = h->d_wovf.as<int>(); a.n_win_dev = h->d_counter.as<int>() + W_CNT_OVF; a.ovf_list = nullptr;
+      a.wlist = h->d_wovf.as<int>(); a.ovf_list = nullptr;
       c3k_launch_window(&a, slots2, h->stream);
       HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipMemcpyAsync(h->phase_win, h->d_counter.as<char>() + 64, 128, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->phase_win, dev_cnt(h)->phases, sizeof(h->phase_win), hipMemcpyDeviceToHost, h->stream));
   }
   HIPCHK(hipEventRecord(h->ev[8], h->stream));
   StitchArgs s; memset(&s, 0, sizeof(s));
@@ -812,12 +805,13 @@ static int run_polish(c3_handle* h, float* ms_prep, float* ms_win, float* ms_st)
   c3k_launch_stitch(&s, std::min(nw, h->n_cus * 16), h->stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(h->ev[9], h->stream));
-  int cnt_all[64];
-  HIPCHK(hipMemcpyAsync(cnt_all, h->d_counter.p, 256, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  memcpy(cnt, cnt_all, 64);
-  if (n_win > 0) h->tm.n_win_redo = cnt_all[W_CNT_OVF];
-  if (n_win > 0) { h->tm.cells_polish += *(long long*)(cnt + 2); h->tm.cells_polish_computed += *(long long*)(cnt + 4); h->tm.n_band_layers = cnt[6]; h->tm.n_band_fallback = cnt[7]; h->tm.n_band_mismatch = cnt[8]; if (cnt[8]) fprintf(stderr, "c3poa: band verify mismatch in window %d layer %d (R = %d): last differing base q = %d, band row %d, full row %d, row of q+1 = %d\n", cnt[9], cnt[10], cnt[11], cnt[12], cnt[13], cnt[14], cnt[15]); }
+  HIPCHK(read_counters(h, &c));
+  if (n_win > 0) {
+    h->tm.n_win_redo = c.win_ovf; h->tm.cells_polish += c.cells; h->tm.cells_polish_computed += c.cells_computed;
+    h->tm.n_band_layers = c.band_layers; h->tm.n_band_fallback = c.band_fallback; h->tm.n_band_mismatch = c.band_mismatch;
+    if (c.band_mismatch) fprintf(stderr, "c3poa: band verify mismatch in window %d layer %d (R = %d): last differing base q = %d, band row %d, full row %d, row of q+1 = %d\n",
+                                 c.verify.window, c.verify.layer, c.verify.R, c.verify.q, c.verify.band_row, c.verify.full_row, c.verify.next_row);
+  }
   HIPCHK(hipEventElapsedTime(ms_prep, h->ev[5], h->ev[6]));
   HIPCHK(hipEventElapsedTime(ms_win, h->ev[7], h->ev[8]));
   HIPCHK(hipEventElapsedTime(ms_st, h->ev[8], h->ev[9]));
@@ -905,10 +899,9 @@ extern "C" int c3_batch_run(c3_handle* h, int stages) {
     }
     HIPCHK(hipEventRecord(t4, h->stream));
     if (stages & C3_STAGE_POA) {
-      int cnt[16];
-      HIPCHK(hipMemcpyAsync(cnt, h->d_counter.p, 64, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));
-      if (!h->work.empty()) h->tm.cells_poa = *(long long*)(cnt + 2);
+      C3Counters c;
+      HIPCHK(read_counters(h, &c));
+      if (!h->work.empty()) h->tm.cells_poa = (int64_t)(c.zero_cells + c.cells);      // zero-repeat overlaps + POA
       h->tm.n_poa_redo = h->n_poa_redo; h->tm.n_poa_redo16 = h->n_poa_redo16;
       DBG("run: poa done\n");
       HIPCHK(hipEventElapsedTime(&ms, t3, t4)); h->tm.ms_poa = ms;
@@ -1203,10 +1196,10 @@ extern "C" int c3_scan_splints(c3_handle* h, int32_t* out /* [n][n_spl][2][4] */
   const size_t items = (size_t)h->n * h->n_spl * 2;
   DBuf scan;
   HIPCHK(scan.ensure(sizeof(int32_t) * 4 * items));
-  HIPCHK(hipMemsetAsync(h->d_counter.p, 0, 64, h->stream));
+  HIPCHK(zero_cnt(h, &dev_cnt(h)->queue));
   ConkArgs a; memset(&a, 0, sizeof(a));
   a.b = dev_batch(h); a.sp_codes = h->d_sp_codes.as<uint8_t>(); a.sp_len = h->d_sp_len.as<int>();
-  a.track = nullptr; a.info = h->d_info.as<C3Info>(); a.counter = h->d_counter.as<int>();
+  a.track = nullptr; a.info = h->d_info.as<C3Info>(); a.cnt = dev_cnt(h);
   a.match = h->cfg.conk_match; a.mismatch = h->cfg.conk_mismatch; a.penalty = h->cfg.conk_penalty;
   a.n_spl = h->n_spl; a.scan = scan.as<int32_t>();
   const int waves = (int)std::min<size_t>(items, (size_t)h->n_cus * 32);
@@ -1215,7 +1208,6 @@ extern "C" int c3_scan_splints(c3_handle* h, int32_t* out /* [n][n_spl][2][4] */
   std::vector<int32_t> tmp(4 * items);
   HIPCHK(hipMemcpyAsync(tmp.data(), scan.p, sizeof(int32_t) * 4 * items, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  scan.release();
   if (out) memcpy(out, tmp.data(), sizeof(int32_t) * 4 * items);
   for (int i = 0; i < h->n; ++i) {
     int best = -1, bs = -1;
@@ -1242,16 +1234,15 @@ extern "C" int c3_scan_adapters(c3_handle* h, int32_t* out) {
   const int grid = (int)std::min<size_t>(items, (size_t)h->n_cus * 16);
   DBuf res, dd;
   HIPCHK(res.ensure(sizeof(int32_t) * 12 * items)); HIPCHK(dd.ensure((size_t)dcap * grid));
-  HIPCHK(hipMemsetAsync(h->d_counter.p, 0, 64, h->stream));
+  HIPCHK(zero_cnt(h, &dev_cnt(h)->queue));
   AdapterArgs a; memset(&a, 0, sizeof(a));
-  a.b = dev_batch(h); a.p = dev_params(h->cfg); a.counter = h->d_counter.as<int>();
+  a.b = dev_batch(h); a.p = dev_params(h->cfg); a.cnt = dev_cnt(h);
   a.ad_codes = h->d_sp_codes.as<uint8_t>(); a.ad_len = h->d_sp_len.as<int>(); a.n_ad = h->n_spl;
   a.D = dd.as<uint8_t>(); a.dcap = dcap; a.out = res.as<int32_t>();
   c3k_launch_adapter(&a, grid, h->stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, res.p, sizeof(int32_t) * 12 * items, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  res.release(); dd.release();
   return C3_E_OK;
 }
 
@@ -1277,7 +1268,6 @@ extern "C" int c3_match_index_batch(c3_handle* h, int n, const char* pieces, con
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, dout.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  dp.release(); dl.release(); di.release(); doff.release(); dout.release();
   return C3_E_OK;
 }
 
@@ -1359,14 +1349,13 @@ extern "C" int c3_consensus_qv(c3_handle* h, const char* cons, int n, int n_piec
   QvArgs a; memset(&a, 0, sizeof(a));
   int grid = 0;
   const int rc = qv_scratch(h, max_m, n, 1, a, &grid);
-  if (rc) { d.release(); return rc; }
+  if (rc) return rc;
   a.cons = b; a.qv = b + o_qv; a.qual = (const uint8_t*)(b + o_q); a.pk = (const uint32_t*)(b + o_pk);
   a.sa_np = np; a.sa_n = n; a.sa_woff = (const int64_t*)(b + o_wo); a.sa_off = (const int64_t*)(b + o_off); a.sa_mode = (const int32_t*)(b + o_md);
   c3k_launch_qv(&a, 1, h->stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(qv_out, b + o_qv, (size_t)n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));           // pk / woff are host vectors of this frame
-  d.release();
   return C3_E_OK;
 }
 
@@ -1403,7 +1392,6 @@ extern "C" int c3_pairwise_consensus(c3_handle* h, const char* rowA, const char*
   HIPCHK(hipStreamSynchronize(h->stream));
   for (int i = 0; i < n; ++i) out[i] = "ACGT"[codes[(size_t)i] & 3];
   *out_len = n;
-  d_rows.release(); d_qa.release(); d_qb.release(); d_scr.release(); d_out.release(); d_len.release();
   return C3_E_OK;
 }
 

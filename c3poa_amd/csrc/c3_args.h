@@ -1,69 +1,117 @@
 // c3_args.h -- kernel argument blocks shared by the launchers (c3_api.hip) and the kernels.
 #pragma once
 #include "c3_dev.h"
+#include <cstddef>
+
+// Device counter block of a handle (c3_api.hip: d_counter).  Every field has one purpose; the host zeroes a stage's fields
+// before its launch and reads them by name.
+struct C3Counters {
+  int queue;                            // work queue of k_conk, k_adapter, k_poa, k_prep and the first k_window launch
+  int peaks_queue;                      // k_peaks: read queue
+  unsigned long long cells;             // DP cells counted by the last k_poa, k_prep or k_window stage
+  unsigned long long cells_computed;    // k_window: cells actually computed (a banded row counts its band only)
+  unsigned long long zero_cells;        // k_zero / k_zero_long: overlap cells of the zero-repeat rescue
+  int poa_ovf;                          // k_poa: reads whose scratch overflowed (list PoaArgs::overflow)
+  int poa_ovf16;                        // k_poa: reads with a score beyond the 16-bit cells (list PoaArgs::overflow16)
+  int n_windows;                        // k_prep: windows reserved (may exceed PrepArgs::wcap)
+  int win_ovf;                          // first k_window launch: windows queued for the second one (WinArgs::ovf_list)
+  int win_queue2;                       // second k_window launch: work queue
+  int band_layers, band_fallback;       // k_window: layers aligned with banded rows / band certificates that failed
+  int band_mismatch;                    // k_window (test hook C3_DEBUG_BAND=verify): layers whose band and full tracebacks differ
+  struct { int window, layer, R, q, band_row, full_row, next_row; } verify;   // ... the last such layer (q = last differing base)
+  unsigned long long phases[16];        // diagnostic builds (-DC3_PHASE_PROF): per-phase cycle sums of k_poa / k_window
+};
+static_assert(offsetof(C3Counters, cells) % 8 == 0 && offsetof(C3Counters, cells_computed) % 8 == 0 &&
+              offsetof(C3Counters, zero_cells) % 8 == 0 && offsetof(C3Counters, phases) % 8 == 0, "u64 counters must be 8-byte aligned");
 
 struct ConkArgs {
-  C3Batch b; const uint8_t* sp_codes; const int* sp_len; int32_t* track; C3Info* info; int* counter;
+  C3Batch b; const uint8_t* sp_codes; const int* sp_len; int32_t* track; C3Info* info; C3Counters* cnt;
   int match, mismatch, penalty;
   int n_spl; int32_t* scan;      // scan mode: [n * n_spl * 2][4] = max, argmax, mean, L
 };
 struct PeaksArgs {
   C3Batch b; const int32_t* track; C3Info* info; double* bufA; double* bufB; int32_t* cand; uint8_t* cstate;
   int32_t* raw_peaks; int32_t* n_raw; const int* sp_len; double coef[64]; int64_t maxL; int window, iters, min_dist;
-  int* queue;                              // read queue (one int, zeroed before the launch)
+  C3Counters* cnt;
 };
 struct PoaArgs {
-  C3Batch b; C3Info* info; C3Params p; int* counter; const int* work; int n_work;
-  // per-slot scratch, one block per kind (the kernel derives every array from these bases: few live SGPRs):
-  //   ibase: 19*Ncap ints  (n_in n_out grp order order2 index gfirst glast rem mpl mpr rowm[3N] anchor col col2t nxt foff)
-  //   ebase: 3*Ncap*K ints (in_from out_to out_w);  cellsb: 2*cells_cap bytes (direction bytes D8, predecessor bytes P8) + 16 * (cells_cap >> 2) bytes (first pass; >> 0 in the 32-bit pass) of 32-bit cells H E1 E2 D for the few rows that keep them;  bbase: 5*Ncap bytes (base rows2[4N])
+  C3Batch b; C3Info* info; C3Params p; C3Counters* cnt; const int* work; int n_work;
+  // per-slot scratch, one block per kind strided by slot (c3_poa_layout; the kernel derives every array from these bases: few live SGPRs)
   int* ibase; int* ebase; char* cellsb; uint8_t* bbase; long long* score;
   int Ncap, K, Pcap, cells_cap;
   uint8_t* draft; int32_t* tpos; uint8_t* msa_dbg; const int64_t* msa_off; int* msa_len;
-  unsigned long long* phases; uint4* desc; int* jump;
-  int* pbase;               // [slots][Pcap] node of every fused base
-  int* overflow;            // reads whose scratch overflowed (count in counter[4]): redone with worst-case scratch; nullptr in the passes that have it
-  int* overflow16;          // reads with a score beyond the 16-bit cells (count in counter[5]): redone by the 32-bit instance; nullptr in that pass
   int rb_span;              // 0 = default; test hook C3_DEBUG_POA_RBSPAN: width of the window a row maximum may move in before the 16-bit base follows it
   int no2col;               // test hook C3_DEBUG_POA_NO2COL: no two-column rows (those rows take the near rows, as before them)
+  uint4* desc; int* jump;
+  int* pbase;               // [slots][Pcap] node of every fused base
+  int* overflow;            // reads whose scratch overflowed (count in cnt->poa_ovf): redone with worst-case scratch; nullptr in the passes that have it
+  int* overflow16;          // reads with a score beyond the 16-bit cells (count in cnt->poa_ovf16): redone by the 32-bit instance; nullptr in that pass
 };
+// k_poa scratch of one slot, bytes per region (each region is one buffer strided by slot):
+//   ints  C3_POA_NI * Ncap ints (n_in n_out grp order order2 index gfirst glast rem mpl mpr rowm[3N] anchor col col2t nxt foff)
+//   edges 3 * Ncap * K ints (in_from out_to out_w)
+//   cells 2 bytes per cell (direction bytes D8, predecessor bytes P8) + 16 bytes per far cell (32-bit H E1 E2 D of the few rows
+//         that keep them): cells_cap >> far_shift far cells, a quarter in the 16-bit instance, all of them in the 32-bit one
+//   bases 5 * Ncap bytes (base rows2[4N]); score Ncap long longs; desc 2 * Ncap uint4; jump C3_JUMP_LEVELS * Ncap ints; path Pcap ints
+#define C3_POA_NI 19
+__host__ __device__ inline int c3_poa_far_shift(bool w32) { return w32 ? 0 : 2; }
+struct PoaLayout { size_t ints, edges, cells, bases, score, desc, jump, path, total; };
+__host__ __device__ inline PoaLayout c3_poa_layout(size_t Ncap, size_t K, int cells_cap, int far_shift, size_t Pcap) {
+  PoaLayout l;
+  l.ints = sizeof(int) * C3_POA_NI * Ncap; l.edges = sizeof(int) * 3 * Ncap * K;
+  l.cells = 2 * (size_t)cells_cap + 16 * (size_t)(cells_cap >> far_shift);
+  l.bases = 5 * Ncap; l.score = sizeof(long long) * Ncap; l.desc = sizeof(uint4) * 2 * Ncap;
+  l.jump = sizeof(int) * C3_JUMP_LEVELS * Ncap; l.path = sizeof(int) * Pcap;
+  l.total = l.ints + l.edges + l.cells + l.bases + l.score + l.desc + l.jump + l.path;
+  return l;
+}
+
 struct WLayer { int qbeg, len, begin, end; };
 struct WinRec { int rid, w, n_layers, blen, tgs, out_len, polished, pad_; };
 struct PrepArgs {
-  C3Batch b; C3Info* info; C3Params p; int* counter; const int* work; int n_work;
-  const uint8_t* draft; int32_t* tpos; int32_t* eH; uint8_t* eD; int64_t ecap; int* lw_first; int* lw_last; int NLcap, NWcap;
-  WinRec* wrec; WLayer* wlay; int* win_base; int* n_windows; int wcap;
+  C3Batch b; C3Info* info; C3Params p; C3Counters* cnt; const int* work; int n_work;
+  const uint8_t* draft; int32_t* tpos; int wcap; uint8_t* eD; int64_t ecap; int* lw_first; int* lw_last; int NLcap, NWcap;
+  WinRec* wrec; WLayer* wlay; int* win_base;
 };
 struct WinArgs {
-  C3Batch b; C3Params p; int* counter; int n_win; const WinRec* wrec_in; WinRec* wrec; const WLayer* wlay; int NLcap;
+  C3Batch b; C3Params p; C3Counters* cnt; int n_win; const WinRec* wrec_in; WinRec* wrec; const WLayer* wlay; int NLcap;
   const uint8_t* draft;
   uint8_t* base; int* ibase; int* ebase; long long* score;
   int32_t* H; uint16_t* D; uint4* rdesc; int Ncap, K; long long hcap; uint8_t* wout; int wout_cap;
   int Lcap;                               // nodes the LDS consensus sweep can hold (<= Ncap)
-  unsigned long long* phases;
   int band_mode;                          // 0 = banded rows with certificate (default), 1 = never banded, 2 = every certificate counts as failed (test hook: C3_DEBUG_BAND)
   // two launches: the first with DP scratch for the typical layer (hcap small); a window one of whose layers does not fit is
-  // dropped untouched into `ovf_list` (count in counter[W_CNT_OVF]) and redone by the second launch, which has worst-case scratch,
-  // takes its windows from `wlist`, their number from device memory (`n_win_dev`) and its queue from counter[W_CNT_Q2]
+  // dropped untouched into `ovf_list` (count in cnt->win_ovf) and redone by the second launch, which has worst-case scratch,
+  // takes its windows from `wlist`, their number from device memory (cnt->win_ovf) and its queue from cnt->win_queue2
   // (k_window<true>: the first launch's code carries none of this)
-  const int* wlist; const int* n_win_dev; int* ovf_list;
+  const int* wlist; int* ovf_list;
 };
-#define W_CNT_OVF 48                      /* d_counter ints: [0] queue of the first launch, [48] overflow count, [49] queue of the second */
-#define W_CNT_Q2 49
+// k_window scratch of one slot, bytes per region (each region is one buffer strided by slot): ints W_INTS * Ncap ints (WCtx::I,
+// 18 * Ncap + 9 used), edges 4 * Ncap * K ints, bases 2 * Ncap bytes (base, mask), score Ncap long longs, DP cells hcap * (4 bytes
+// of H + 1 direction byte), row descriptors Ncap + 1 uint4
+#define W_INTS 19
+struct WinLayout { size_t ints, edges, bases, score, H, D, desc, total; };
+__host__ __device__ inline WinLayout c3_win_layout(size_t Ncap, size_t K, size_t hcap) {
+  WinLayout l;
+  l.ints = sizeof(int) * W_INTS * Ncap; l.edges = sizeof(int) * 4 * Ncap * K; l.bases = 2 * Ncap; l.score = sizeof(long long) * Ncap;
+  l.H = sizeof(int32_t) * hcap; l.D = hcap; l.desc = sizeof(uint4) * (Ncap + 1);
+  l.total = l.ints + l.edges + l.bases + l.score + l.H + l.D + l.desc;
+  return l;
+}
 struct StitchArgs {
   C3Batch b; C3Info* info; const int* work; int n_work; const WinRec* wrec; const int* win_base; const uint8_t* wout; int wout_cap; char* cons;
   const uint8_t* zflag;
 };
 // adapter finder (k_adapter): every read x every entry of the splint table x both strands
 struct AdapterArgs {
-  C3Batch b; C3Params p; int* counter;
+  C3Batch b; C3Params p; C3Counters* cnt;
   const uint8_t* ad_codes; const int* ad_len; int n_ad;
   uint8_t* D; long long dcap;           // [grid][dcap] direction bytes
   int32_t* out;                         // [n * n_ad * 2][12]
 };
 
 struct ZeroArgs {
-  C3Batch b; C3Info* info; C3Params p; int* counter; const int* work; int n_work;
+  C3Batch b; C3Info* info; C3Params p; C3Counters* cnt; const int* work; int n_work;
   uint8_t* D; long long dcap;           // [grid][dcap] direction bytes
   int4* zinfo; uint8_t* zflag;          // per read: r_st, r_en, q_st, q_en; rescue in progress / done
   const uint8_t* draft; char* cons;

@@ -30,7 +30,7 @@ __global__ __launch_bounds__(64) void k_adapter(AdapterArgs a) {
   uint8_t* D = a.D + (size_t)blockIdx.x * a.dcap;
   for (;;) {
     int item = 0;
-    if (lane == 0) item = atomicAdd(a.counter, 1);
+    if (lane == 0) item = atomicAdd(&a.cnt->queue, 1);
     item = wave_first(item);
     if (item >= n_items) break;
     const int rid = item / (a.n_ad * 2), aid = (item >> 1) % a.n_ad, rc = item & 1;

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void k_conk(ConkArgs a) {
   const int n_items = SCAN ? a.b.n * a.n_spl * 2 : a.b.n;
   for (;;) {
     int item = 0;
-    if (lane == 0) item = atomicAdd(a.counter, 1);
+    if (lane == 0) item = atomicAdd(&a.cnt->queue, 1);
     item = wave_first(item);
     if (item >= n_items) break;
     const int rid = SCAN ? item / (a.n_spl * 2) : item;

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(PK_T) void k_peaks(PeaksArgs a) {
   __shared__ int s_rid;
   for (;;) {
     __syncthreads();
-    if (tid == 0) s_rid = atomicAdd(a.queue, 1);
+    if (tid == 0) s_rid = atomicAdd(&a.cnt->peaks_queue, 1);
     __syncthreads();
     const int rid = s_rid;
     if (rid >= a.b.n) break;

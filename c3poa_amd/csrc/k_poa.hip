@@ -19,7 +19,6 @@
 // adjacency slot k of node v.  Slot-major (all first edges, then all second edges, ...): nearly every node has one or two
 // edges, so the arrays a wave actually touches are contiguous runs of Ncap ints instead of one 64-byte line per node
 #define EI(v, k) ((size_t)(k) * (size_t)c.Ncap + (size_t)(v))
-#define C3_POA_NI 19       // int arrays of Ncap per slot in Ctx::I
 #define SRC 0
 #define SNK 1
 
@@ -1173,18 +1172,18 @@ __global__ __launch_bounds__(64, C3_POA_WAVES) void k_poa(PoaArgs a) {
   Ctx c;
   const size_t N = (size_t)a.Ncap;
   c.I = a.ibase + (size_t)slot * C3_POA_NI * N; c.path_ = a.pbase + (size_t)slot * a.Pcap; c.E = a.ebase + (size_t)slot * 3 * N * a.K;
-  c.far_shift = W32 ? 0 : 2;
-  c.C = a.cellsb + (size_t)slot * (2 * (size_t)a.cells_cap + 16 * (size_t)(a.cells_cap >> c.far_shift)); c.B8 = a.bbase + (size_t)slot * 5 * N;
+  c.far_shift = c3_poa_far_shift(W32);
+  c.C = a.cellsb + (size_t)slot * c3_poa_layout(N, a.K, a.cells_cap, c.far_shift, a.Pcap).cells; c.B8 = a.bbase + (size_t)slot * 5 * N;
   c.score_ = a.score + (size_t)slot * N; c.desc_ = a.desc + (size_t)slot * 2 * N; c.jump_ = a.jump + (size_t)slot * C3_JUMP_LEVELS * N;
   c.K = a.K; c.Ncap = a.Ncap; c.cells_cap = a.cells_cap; c.osel = 0; c.rb_span = a.rb_span > 0 ? a.rb_span : RB_HI16 - RB_LO16; c.two_col = !a.no2col;
 #ifdef C3_DEBUG_PUNT
-  c.dbg = a.phases;
+  c.dbg = a.cnt->phases;
 #endif
   PH_DECL
 
   for (;;) {
     int wi = 0;
-    if (lane == 0) wi = atomicAdd(a.counter, 1);
+    if (lane == 0) wi = atomicAdd(&a.cnt->queue, 1);
     wi = wave_first(wi);
     if (wi >= a.n_work) break;
     const int rid = a.work[wi];
@@ -1386,17 +1385,17 @@ __global__ __launch_bounds__(64, C3_POA_WAVES) void k_poa(PoaArgs a) {
     int* const olist = to16 ? a.overflow16 : a.overflow;
     const bool redo = fail == 2 && olist != nullptr;
     if (lane == 0) {
-      if (redo) olist[atomicAdd(a.counter + (to16 ? 5 : 4), 1)] = rid;
+      if (redo) olist[atomicAdd(to16 ? &a.cnt->poa_ovf16 : &a.cnt->poa_ovf, 1)] = rid;
       else {
         info->draft_len = C;
         if (fail) { info->status = C3_ST_LIMIT; info->draft_len = 0; }
         else if (C == 0) info->status = C3_ST_NO_CONSENSUS;
-        atomicAdd((unsigned long long*)(a.counter + 2), (unsigned long long)cells);
+        atomicAdd(&a.cnt->cells, (unsigned long long)cells);
       }
     }
     WSYNC();
   }
-  PH_FLUSH(a.phases)
+  PH_FLUSH(a.cnt->phases)
 }
 
 extern "C" void c3k_launch_poa(const PoaArgs* a, int slots, int wide32, int wide_ring, hipStream_t stream) {

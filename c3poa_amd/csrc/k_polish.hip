@@ -264,7 +264,7 @@ __device__ __forceinline__ void prep_one(const PrepArgs& a, int wi, int lane, ui
     }
     const int tgs = tl > 1000L * nl;
     int wbase = 0;
-    if (lane == 0) wbase = atomicAdd(a.n_windows, nwin);
+    if (lane == 0) wbase = atomicAdd(&a.cnt->n_windows, nwin);
     wbase = wave_first(wbase);
     if (wbase + nwin > a.wcap) {
       // the reservation cannot be undone: the slots below wcap become empty windows (no layers, no backbone), so k_window
@@ -332,7 +332,7 @@ __device__ __forceinline__ void prep_one(const PrepArgs& a, int wi, int lane, ui
     }
     if (lane == 0) {
       info->n_win = nwin; a.win_base[rid] = wbase;
-      atomicAdd((unsigned long long*)(a.counter + 2), (unsigned long long)cells);
+      atomicAdd(&a.cnt->cells, (unsigned long long)cells);
     }
     WSYNC();
 }
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(64, C3_PREP_WAVES) void k_prep(PrepArgs a) {
   const int WL = a.p.pol_window;
   for (;;) {
     int wi = 0;
-    if (lane == 0) wi = atomicAdd(a.counter, 1);
+    if (lane == 0) wi = atomicAdd(&a.cnt->queue, 1);
     wi = wave_first(wi);
     if (wi >= a.n_work) break;
     prep_one(a, wi, lane, ldraft, eD, lwf, lwl, WL);
@@ -398,7 +398,6 @@ struct WCtx {
   __device__ __forceinline__ WArr<uint8_t> base() const { return {B8, 0u}; }
   __device__ __forceinline__ WArr<uint8_t> mask() const { return {B8, (unsigned)Ncap}; }
 };
-#define W_INTS 19   // ints of Ncap per slot in WCtx::I (18*Ncap + 9 used)
 
 // The graph phases are chains of dependent memory round trips (position -> node -> its group / edges ...), and a wave that
 // waits for one has nothing else to do: every loop over the nodes therefore takes WU chunks of 64 per iteration, all loads of
@@ -1069,7 +1068,7 @@ __global__ __launch_bounds__(64, C3_WIN_WAVES) void k_window(WinArgs a) {
   const int slot = blockIdx.x;
   WCtx c;
   const size_t N = (size_t)a.Ncap;
-  c.I = a.ibase + (size_t)slot * W_INTS * N; c.E = a.ebase + (size_t)slot * 4 * N * a.K;
+  c.I = a.ibase + (size_t)slot * W_INTS * N; c.E = a.ebase + (size_t)slot * 4 * N * a.K;          // (strides: c3_win_layout)
   c.B8 = a.base + (size_t)slot * 2 * N; c.score = a.score + slot * N;
   c.H = a.H + (size_t)slot * a.hcap; c.D = (uint8_t*)a.D + (size_t)slot * a.hcap; c.rdesc = a.rdesc + slot * (N + 1);
   c.K = a.K; c.Ncap = a.Ncap; c.hcap = a.hcap;
@@ -1087,10 +1086,10 @@ __global__ __launch_bounds__(64, C3_WIN_WAVES) void k_window(WinArgs a) {
     int wi = 0;
     if (lane == 0) {
       if (SECOND) {                                 // the windows the first launch could not hold: list and count in device memory
-        wi = atomicAdd(a.counter + W_CNT_Q2, 1);
-        wi = wi < *(const volatile int*)a.n_win_dev ? a.wlist[wi] : -1;
+        wi = atomicAdd(&a.cnt->win_queue2, 1);
+        wi = wi < *(const volatile int*)&a.cnt->win_ovf ? a.wlist[wi] : -1;
       } else {
-        wi = atomicAdd(a.counter, 1);
+        wi = atomicAdd(&a.cnt->queue, 1);
         if (wi >= a.n_win) wi = -1;
       }
     }
@@ -1380,8 +1379,8 @@ __global__ __launch_bounds__(64, C3_WIN_WAVES) void k_window(WinArgs a) {
             int qd = -1;
             for (int q = lane; q < Q; q += 64) if (c.opq()[q] != rq.get(q)) qd = q;
             qd = wave_max(qd);
-            if (lane == 0) { atomicAdd(a.counter + 8, 1); a.counter[9] = wi; a.counter[10] = t; a.counter[11] = R; a.counter[12] = qd; a.counter[13] = c.opq()[qd]; a.counter[14] = rq.get(qd);
-                             a.counter[15] = qd + 1 < Q ? rq.get(qd + 1) : -1; }
+            if (lane == 0) { atomicAdd(&a.cnt->band_mismatch, 1); a.cnt->verify.window = wi; a.cnt->verify.layer = t; a.cnt->verify.R = R; a.cnt->verify.q = qd;
+                             a.cnt->verify.band_row = c.opq()[qd]; a.cnt->verify.full_row = rq.get(qd); a.cnt->verify.next_row = qd + 1 < Q ? rq.get(qd + 1) : -1; }
           }
         }
         WSYNC();
@@ -1505,18 +1504,18 @@ __global__ __launch_bounds__(64, C3_WIN_WAVES) void k_window(WinArgs a) {
       }
     }
     if (fail == 2 && a.ovf_list) {
-      if (lane == 0) a.ovf_list[atomicAdd(a.counter + W_CNT_OVF, 1)] = wi;          // nothing of this window has been published
+      if (lane == 0) a.ovf_list[atomicAdd(&a.cnt->win_ovf, 1)] = wi;          // nothing of this window has been published
     } else if (lane == 0) {
       WinRec* r = &a.wrec[wi];
       r->out_len = fail ? -1 : olen; r->polished = polished;        // (fail == 2 with no second launch to take it: the window is over the limits)
-      atomicAdd((unsigned long long*)(a.counter + 2), (unsigned long long)cells);
-      atomicAdd((unsigned long long*)(a.counter + 4), (unsigned long long)cells_done);
-      if (n_band) atomicAdd(a.counter + 6, n_band);
-      if (n_fallback) atomicAdd(a.counter + 7, n_fallback);
+      atomicAdd(&a.cnt->cells, (unsigned long long)cells);
+      atomicAdd(&a.cnt->cells_computed, (unsigned long long)cells_done);
+      if (n_band) atomicAdd(&a.cnt->band_layers, n_band);
+      if (n_fallback) atomicAdd(&a.cnt->band_fallback, n_fallback);
     }
     WSYNC();
   }
-  PH_FLUSH(a.phases)
+  PH_FLUSH(a.cnt->phases)
 }
 
 // ------------------------------------------------------------------------------------------

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(64) void k_zero(ZeroArgs a) {
         z.x = j; z.y = gj; z.z = i; z.w = gi;           // r_st, r_en, q_st, q_en
         ok = gj > j && gi > i;
       } else ok = false;
-      if (lane == 0) atomicAdd((unsigned long long*)(a.counter + 2), (unsigned long long)n0 * n1);
+      if (lane == 0) atomicAdd(&a.cnt->zero_cells, (unsigned long long)n0 * n1);
     }
     if (lane == 0) {
       a.zinfo[rid] = z;
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(64 * ZL_WAVES) void k_zero_long(ZeroArgs a) {
         ok = gj > j && gi > i;
       } else ok = false;
       // counted cells = the oracle's (n0 * n1); the traceback's recomputed rows are not counted
-      if (threadIdx.x == 0) atomicAdd((unsigned long long*)(a.counter + 2), (unsigned long long)n0 * n1);
+      if (threadIdx.x == 0) atomicAdd(&a.cnt->zero_cells, (unsigned long long)n0 * n1);
     }
     if (threadIdx.x == 0) {
       a.zinfo[rid] = z;
