@@ -49,6 +49,9 @@ def parse_args(argv=None):
     parser.add_argument("--blatThreads", "-b", action="store_true", default=False, help="Accepted for compatibility.")
     parser.add_argument("--compress_output", "-co", action="store_true", default=False,
                         help="Use to compress (gzip) both the consensus fasta and subread fastq output files.")
+    parser.add_argument("--bgzf", action="store_true", default=False,
+                        help="Compress the outputs to BGZF on the GPU while the run goes (implies -co: the same .gz file "
+                             "names, readable by gzip, without an uncompressed file or a pass after the run). Off by default.")
     parser.add_argument("--consensus-fastq", dest="consensus_fastq", action="store_true", default=False,
                         help="Also write <splint>/R2C2_Consensus.fastq: every consensus with per-base support QVs computed on "
                              "the GPU (not calibrated error probabilities; see DESIGN.md). Off by default.")
@@ -56,7 +59,10 @@ def parse_args(argv=None):
     if argv is None and len(sys.argv) == 1:
         parser.print_help()
         sys.exit(0)
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    if args.bgzf:
+        args.compress_output = True
+    return args
 
 
 def configReader(path, configIn):

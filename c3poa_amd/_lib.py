@@ -26,7 +26,9 @@ EXPORTS = ["c3_default_config", "c3_version", "c3_device_count", "c3_warm_device
            "c3_assign_open", "c3_assign_close", "c3_assign_batch", "c3_assign_seen", "c3_write_splint_psl",
            "c3_host_alloc", "c3_host_free", "c3_writer_reset",
            "c3_batch_results_fetch_qv", "c3_batch_results_qv", "c3_batch_qv_timing", "c3_consensus_qv", "c3_consensus_qv_host",
-           "c3_write_consensus_fastq"]
+           "c3_write_consensus_fastq",
+           "c3_bgzf_create", "c3_bgzf_destroy", "c3_bgzf_bound", "c3_bgzf_compress", "c3_bgzf_compress_host",
+           "c3_write_group_bgzf", "c3_write_consensus_fastq_bgzf"]
 
 
 ZERO_MAX_CELLS = 16777216       # c3_default_config's zero_max_cells: largest front * tail the zero-repeat rescue takes
@@ -151,6 +153,15 @@ def load():
     lib.c3_consensus_qv.argtypes = [vp, cp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     lib.c3_consensus_qv_host.argtypes = [cp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     lib.c3_write_consensus_fastq.argtypes = [C.POINTER(HostBatchStruct), vp, vp, vp, vp, vp, C.c_int, C.POINTER(cp), C.c_int]
+    lib.c3_bgzf_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.c3_bgzf_destroy.argtypes = [vp]
+    lib.c3_bgzf_destroy.restype = None
+    lib.c3_bgzf_bound.argtypes = [C.c_int64]
+    lib.c3_bgzf_bound.restype = C.c_int64
+    lib.c3_bgzf_compress.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64)]
+    lib.c3_bgzf_compress_host.argtypes = [vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64)]
+    lib.c3_write_group_bgzf.argtypes = [vp, C.POINTER(HostBatchStruct), vp, vp, vp, vp, C.c_int, C.POINTER(cp), C.POINTER(cp), C.c_int]
+    lib.c3_write_consensus_fastq_bgzf.argtypes = [vp, C.POINTER(HostBatchStruct), vp, vp, vp, vp, vp, C.c_int, C.POINTER(cp), C.c_int]
     _lib = lib
     return lib
 
@@ -847,3 +858,79 @@ def write_consensus_fastq(hb, res, cons_buf, cons_off, qv_buf, splint_ids, fq_pa
                                       sid.ctypes.data, n_spl, fp, 1 if zero else 0)
     if rc != 0:
         raise OSError("c3_write_consensus_fastq failed (%d)" % rc)
+
+
+# ---- BGZF output (--bgzf; include/c3poa.h "BGZF output") ----
+BGZF_BLOCK = 65280              # input bytes per member
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")   # the SAM specification's EOF member
+
+
+def _bgzf_call(fn, first, data):
+    lib = load()
+    src = _b(data) if not isinstance(data, (bytes, bytearray, memoryview)) else bytes(data)
+    cap = int(lib.c3_bgzf_bound(len(src)))
+    out = C.create_string_buffer(max(cap, 1))
+    olen = C.c_int64(0)
+    rc = fn(*(first + (src, len(src), out, cap, C.byref(olen))))
+    if rc != 0:
+        raise C3Error("c3 error %d: %s" % (rc, lib.c3_last_error(None).decode()))
+    return out.raw[:olen.value]
+
+
+def bgzf_compress_host(data):
+    """c3_bgzf_compress_host: BGZF members of `data` (no EOF member), the host statement of Bgzf.compress"""
+    return _bgzf_call(load().c3_bgzf_compress_host, (), data)
+
+
+class Bgzf:
+    """c3_bgzf: k_bgzf on one device (device buffers and a stream of its own; one per thread)"""
+
+    def __init__(self, device=0):
+        self.lib = load()
+        self.z = C.c_void_p()
+        rc = self.lib.c3_bgzf_create(int(device), C.byref(self.z))
+        if rc != 0:
+            raise C3Error("c3_bgzf_create failed (%d): %s" % (rc, self.lib.c3_last_error(None).decode()))
+
+    def compress(self, data):
+        return _bgzf_call(self.lib.c3_bgzf_compress, (self.z,), data)
+
+    def close(self):
+        if self.z:
+            self.lib.c3_bgzf_destroy(self.z)
+            self.z = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def write_group_bgzf(z, hb, res, cons_buf, cons_off, splint_ids, cons_paths, sub_paths, zero=True):
+    """c3_write_group_bgzf: write_group with each file's text compressed by k_bgzf; the paths name the .gz files"""
+    lib = load()
+    n_spl = len(cons_paths)
+    cp = (C.c_char_p * n_spl)(*[_b(p) for p in cons_paths])
+    sp = (C.c_char_p * n_spl)(*[_b(p) for p in sub_paths])
+    sid = np.ascontiguousarray(splint_ids, dtype=np.int16)
+    res = np.ascontiguousarray(res)
+    coff = np.ascontiguousarray(cons_off, dtype=np.int64)
+    rc = lib.c3_write_group_bgzf(z.z, C.byref(hb.c), res.ctypes.data, cons_buf.ctypes.data if cons_buf is not None else None,
+                                 coff.ctypes.data, sid.ctypes.data, n_spl, cp, sp, 1 if zero else 0)
+    if rc != 0:
+        raise OSError("c3_write_group_bgzf failed (%d): %s" % (rc, lib.c3_last_error(None).decode()))
+
+
+def write_consensus_fastq_bgzf(z, hb, res, cons_buf, cons_off, qv_buf, splint_ids, fq_paths, zero=True):
+    """c3_write_consensus_fastq_bgzf: write_consensus_fastq with each file's text compressed by k_bgzf"""
+    lib = load()
+    n_spl = len(fq_paths)
+    fp = (C.c_char_p * n_spl)(*[_b(p) for p in fq_paths])
+    sid = np.ascontiguousarray(splint_ids, dtype=np.int16)
+    res = np.ascontiguousarray(res)
+    coff = np.ascontiguousarray(cons_off, dtype=np.int64)
+    rc = lib.c3_write_consensus_fastq_bgzf(z.z, C.byref(hb.c), res.ctypes.data, cons_buf.ctypes.data, coff.ctypes.data,
+                                           qv_buf.ctypes.data, sid.ctypes.data, n_spl, fp, 1 if zero else 0)
+    if rc != 0:
+        raise OSError("c3_write_consensus_fastq_bgzf failed (%d): %s" % (rc, lib.c3_last_error(None).decode()))

@@ -2,6 +2,7 @@
 // No CPU fallback exists in this library: without a gfx950 device c3_create fails.
 #include "c3_dev.h"
 #include "c3_args.h"
+#include "c3_bgzf.h"
 #include <algorithm>
 #include <cstddef>
 #include <cstdio>
@@ -26,6 +27,7 @@ extern "C" void c3k_launch_zero_long(const ZeroArgs*, int, hipStream_t);
 extern "C" void c3k_launch_zero_finish(const ZeroArgs*, int, hipStream_t);
 extern "C" void c3k_launch_qv(const QvArgs*, int, hipStream_t);
 extern "C" int c3k_qv_lds_max(void);
+extern "C" void c3k_launch_bgzf(const uint8_t*, long long, int, uint8_t*, int*, uint8_t*, hipStream_t);
 
 // ---- small kernels ----------------------------------------------------------------------
 __device__ __forceinline__ uint32_t pack_code(uint32_t b) {
@@ -1486,4 +1488,100 @@ extern "C" int c3_determine_consensus(c3_handle* h, int n, const char* const* su
   if (rc) return rc;
   *out_len = (res[0].status == C3_ST_OK) ? res[0].cons_len : 0;
   return C3_E_OK;
+}
+
+// ---- BGZF output (k_bgzf.hip; host statement c3_bgzf.cpp) ---------------------------------
+// Input goes to the device in chunks of BGZF_CHUNK_BLOCKS blocks: copy in (the pieces land back to back), k_bgzf + k_bgzf_pack,
+// the member sizes back, then one copy of the packed members straight into the caller's buffer.
+#define BGZF_CHUNK_BLOCKS 2048
+struct c3_bgzf {
+  int device = 0; hipStream_t stream = nullptr; int* h_sizes = nullptr;
+  DBuf d_in, d_slots, d_sizes, d_packed;
+};
+
+extern "C" int c3_bgzf_create(int device, c3_bgzf** out) {
+  if (!out) return C3_E_ARG;
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); g_create_err = "no HIP device: the c3poa HIP backend has no CPU fallback"; return C3_E_NO_DEVICE; }
+  if (device < 0 || device >= ndev) { g_create_err = "bad device ordinal"; return C3_E_ARG; }
+  c3_bgzf* z = new c3_bgzf();
+  z->device = device;
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&z->h_sizes, BGZF_CHUNK_BLOCKS * sizeof(int), hipHostMallocDefault);
+  if (e != hipSuccess) { g_create_err = hipGetErrorString(e); c3_bgzf_destroy(z); return C3_E_HIP; }
+  *out = z;
+  return C3_E_OK;
+}
+
+extern "C" void c3_bgzf_destroy(c3_bgzf* z) {
+  if (!z) return;
+  (void)hipSetDevice(z->device);
+  if (z->stream) { (void)hipStreamSynchronize(z->stream); (void)hipStreamDestroy(z->stream); }
+  if (z->h_sizes) (void)hipHostFree(z->h_sizes);
+  delete z;
+}
+
+static int bgzf_fail(hipError_t e, const char* what) {
+  char buf[256];
+  snprintf(buf, sizeof buf, "HIP error %d (%s): %s", (int)e, hipGetErrorString(e), what);
+  g_create_err = buf;
+  return C3_E_HIP;
+}
+
+// the concatenation of pieces p[0..np) compressed as one text (the writers' formatter slices, c3_io.cpp)
+extern "C" int c3_bgzf_compress_pieces(c3_bgzf* z, const char* const* p, const int64_t* len, int np, char* dst, int64_t cap, int64_t* out_len) {
+  if (!z || !out_len || np < 0 || (np > 0 && (!p || !len))) { g_create_err = "c3_bgzf_compress: bad arguments"; return C3_E_ARG; }
+  int64_t n = 0;
+  for (int i = 0; i < np; ++i) { if (len[i] < 0 || (len[i] > 0 && !p[i])) { g_create_err = "c3_bgzf_compress: bad piece"; return C3_E_ARG; } n += len[i]; }
+  if (cap < c3_bgzf_bound(n) || (n > 0 && !dst)) { g_create_err = "c3_bgzf_compress: cap < c3_bgzf_bound(n)"; return C3_E_ARG; }
+  *out_len = 0;
+  if (n == 0) return C3_E_OK;
+  hipError_t e = hipSetDevice(z->device);
+  if (e != hipSuccess) return bgzf_fail(e, "hipSetDevice");
+  const int64_t CH = (int64_t)BGZF_CHUNK_BLOCKS * BGZF_BLOCK;
+  const int64_t first = std::min(CH, n);
+  const int nb_max = (int)((first + BGZF_BLOCK - 1) / BGZF_BLOCK);
+  // k_bgzf reads up to 8 bytes past a chunk's end (realigned dword loads): the input buffer has 256 bytes of slack
+  if ((e = z->d_in.ensure((size_t)first + 256)) != hipSuccess) return bgzf_fail(e, "input buffer");
+  if ((e = z->d_slots.ensure((size_t)nb_max * BGZF_SLOT)) != hipSuccess) return bgzf_fail(e, "slots");
+  if ((e = z->d_sizes.ensure((size_t)nb_max * sizeof(int))) != hipSuccess) return bgzf_fail(e, "sizes");
+  if ((e = z->d_packed.ensure((size_t)nb_max * BGZF_MAX_MEMBER)) != hipSuccess) return bgzf_fail(e, "packed members");
+  int64_t o = 0;
+  int pi = 0; int64_t pin = 0;                                  // piece index / bytes of it already sent
+  for (int64_t c0 = 0; c0 < n; c0 += CH) {
+    const int64_t cn = std::min(CH, n - c0);
+    const int nb = (int)((cn + BGZF_BLOCK - 1) / BGZF_BLOCK);
+    int64_t at = 0;
+    while (at < cn) {
+      while (pi < np && pin == len[pi]) { ++pi; pin = 0; }
+      const int64_t k = std::min(len[pi] - pin, cn - at);
+      e = hipMemcpyAsync(z->d_in.as<char>() + at, p[pi] + pin, (size_t)k, hipMemcpyHostToDevice, z->stream);
+      if (e != hipSuccess) return bgzf_fail(e, "copy in");
+      at += k; pin += k;
+    }
+    c3k_launch_bgzf(z->d_in.as<uint8_t>(), (long long)cn, nb, z->d_slots.as<uint8_t>(), z->d_sizes.as<int>(), z->d_packed.as<uint8_t>(), z->stream);
+    if ((e = hipGetLastError()) != hipSuccess) return bgzf_fail(e, "k_bgzf launch");
+    e = hipMemcpyAsync(z->h_sizes, z->d_sizes.p, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, z->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(z->stream);
+    if (e != hipSuccess) return bgzf_fail(e, "k_bgzf");
+    int64_t tot = 0;
+    for (int b = 0; b < nb; ++b) {
+      const int s = z->h_sizes[b];
+      if (s < BGZF_HDR + 13 || s > BGZF_MAX_MEMBER) { g_create_err = "k_bgzf: member size out of range"; return C3_E_HIP; }
+      tot += s;
+    }
+    e = hipMemcpyAsync(dst + o, z->d_packed.p, (size_t)tot, hipMemcpyDeviceToHost, z->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(z->stream);
+    if (e != hipSuccess) return bgzf_fail(e, "copy out");
+    o += tot;
+  }
+  *out_len = o;
+  return C3_E_OK;
+}
+
+extern "C" int c3_bgzf_compress(c3_bgzf* z, const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len) {
+  if (!z || !out_len || n < 0 || (n > 0 && !src)) { g_create_err = "c3_bgzf_compress: bad arguments"; return C3_E_ARG; }
+  return c3_bgzf_compress_pieces(z, &src, &n, 1, dst, cap, out_len);
 }

@@ -681,34 +681,111 @@ void release_append(int fd) {
 
 extern "C" void c3_writer_reset(void) { std::lock_guard<std::mutex> lk(g_res_mu); g_res.clear(); }
 
+namespace {
+// phases 0 and 1 of a writer call: the group cut into T contiguous read ranges, each range's records formatted (in
+// parallel) into its own (kind, splint) slices of one pooled arena.  Slice x = k * NS + s of thread k: consensus text
+// [sc[x], oc[x].p), subread text [ss[x], os[x].p).
+struct Formatted {
+  int T = 1; size_t NS = 0; Arena ar;
+  std::vector<char*> sc, ss; std::vector<Out> oc, os;
+  template <class F> void run_all(F&& fn) const {
+    std::vector<std::thread> th;
+    for (int k = 0; k < T; ++k) { if (k + 1 < T) th.emplace_back(fn, k); else fn(k); }
+    for (auto& x : th) x.join();
+  }
+  size_t len(int kind, size_t x) const { return kind ? (size_t)(os[x].p - ss[x]) : (size_t)(oc[x].p - sc[x]); }
+  const char* txt(int kind, size_t x) const { return kind ? ss[x] : sc[x]; }
+};
+int format_group(const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
+                 const int16_t* splint_id, int n_splints, int zero, Formatted& f) {
+  int T = 1;
+  if (b->n >= 4096) { T = 8; if (const char* e = getenv("C3_WRITER_THREADS")) T = std::max(1, std::min(64, atoi(e))); }
+  f.T = T;
+  const size_t NS = f.NS = (size_t)n_splints;
+  auto range = [&](int k, int* i0, int* i1) { *i0 = (int)((int64_t)b->n * k / T); *i1 = (int)((int64_t)b->n * (k + 1) / T); };
+  // phase 0: size of every (thread, kind, splint) slice from an upper bound of its records; one pooled arena holds them all
+  std::vector<size_t> bc((size_t)T * NS, 0), bs((size_t)T * NS, 0);
+  f.run_all([&](int k) { int i0, i1; range(k, &i0, &i1); bound_range(b, res, cons, cons_off, splint_id, n_splints, zero, i0, i1, &bc[(size_t)k * NS], &bs[(size_t)k * NS]); });
+  size_t need = 64;
+  for (size_t x : bc) need += x;
+  for (size_t x : bs) need += x;
+  f.ar = arena_get(need);
+  if (!f.ar.p) return C3_E_NOMEM;
+  f.sc.resize((size_t)T * NS); f.ss.resize((size_t)T * NS);             // slice starts
+  { char* p = f.ar.p; for (size_t x = 0; x < (size_t)T * NS; ++x) { f.sc[x] = p; p += bc[x]; f.ss[x] = p; p += bs[x]; } }
+  f.oc.resize((size_t)T * NS); f.os.resize((size_t)T * NS);
+  for (size_t x = 0; x < (size_t)T * NS; ++x) { f.oc[x].p = f.sc[x]; f.os[x].p = f.ss[x]; }
+  // phase 1: format (parallel), straight into the slices
+  f.run_all([&](int k) { int i0, i1; range(k, &i0, &i1); format_range(b, res, cons, cons_off, splint_id, n_splints, zero, i0, i1, &f.oc[(size_t)k * NS], &f.os[(size_t)k * NS]); });
+  return C3_E_OK;
+}
+
+// R2C2_Consensus.fastq text of splint s (the consensus records of c3_write_group, emit_of, same header, with the QV line)
+size_t format_consensus_fastq(const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
+                              const char* qv, const int16_t* splint_id, int n_splints, int zero, int s, char* buf) {
+  Out o{buf};
+  for (int i = 0; i < b->n; ++i) {
+    if (splint_id[i] != s) continue;
+    const int64_t clen = cons_off[i + 1] - cons_off[i];
+    const Emit e = emit_of(res[i], s, n_splints, zero, clen);
+    if (!e.cons) continue;
+    const char* name = b->names + b->name_off[i]; const size_t nl = (size_t)(b->name_off[i + 1] - b->name_off[i]);
+    const int64_t L = b->off[i + 1] - b->off[i];
+    o.put('@'); o.app(name, nl); o.put('_');
+    avg_qual_text(b->quals + b->off[i], L, o);
+    o.put('_'); o.num((long long)L); o.put('_'); o.num(e.ns);
+    o.put('_'); o.num((long long)clen); o.put('\n');
+    o.app(cons + cons_off[i], (size_t)clen); o.app("\n+\n", 3);
+    o.app(qv + cons_off[i], (size_t)clen); o.put('\n');
+  }
+  return (size_t)(o.p - buf);
+}
+std::vector<size_t> consensus_fastq_bounds(const c3_host_batch* b, const c3_read_result* res, const int64_t* cons_off,
+                                           const int16_t* splint_id, int n_splints, int zero) {
+  std::vector<size_t> bound((size_t)n_splints, 0);
+  for (int i = 0; i < b->n; ++i) {
+    const int64_t clen = cons_off[i + 1] - cons_off[i];
+    const Emit e = emit_of(res[i], splint_id[i], n_splints, zero, clen);
+    if (e.cons) bound[(size_t)splint_id[i]] += (size_t)(b->name_off[i + 1] - b->name_off[i]) + 2 * (size_t)clen + 96;
+  }
+  return bound;
+}
+
+// compressed bytes of one file: appended at a reserved range of the compressed file, by T threads (one contiguous piece each,
+// as c3_write_group's phase 2 does)
+bool append_file(const char* path, const char* p, size_t n, const Formatted* f = nullptr) {
+  const int fd = open(path, O_WRONLY | O_CREAT, 0644);
+  if (fd < 0) return false;
+  const off_t at = reserve_append(fd, n);
+  bool ok = true;
+  if (f && f->T > 1 && n >= ((size_t)1 << 20)) {
+    const int T = f->T;
+    std::vector<char> good((size_t)T, 1);
+    f->run_all([&](int k) {
+      const size_t b = n * (size_t)k / (size_t)T, e = n * (size_t)(k + 1) / (size_t)T;
+      if (!pwrite_all(fd, p + b, e - b, at + (off_t)b)) good[(size_t)k] = 0;
+    });
+    for (char g : good) ok = ok && g;
+  } else {
+    ok = pwrite_all(fd, p, n, at);
+  }
+  release_append(fd);
+  if (close(fd) != 0) ok = false;
+  return ok;
+}
+}  // namespace
+
+extern "C" int c3_bgzf_compress_pieces(c3_bgzf* z, const char* const* p, const int64_t* len, int np, char* dst, int64_t cap, int64_t* out_len);
+
 extern "C" int c3_write_group(const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
                               const int16_t* splint_id, int n_splints, const char* const* cons_paths,
                               const char* const* sub_paths, int zero) {
   if (!b || !res || !cons_off || !splint_id || n_splints <= 0 || !cons_paths || !sub_paths) return C3_E_ARG;
-  int T = 1;
-  if (b->n >= 4096) { T = 8; if (const char* e = getenv("C3_WRITER_THREADS")) T = std::max(1, std::min(64, atoi(e))); }
-  const size_t NS = (size_t)n_splints;
-  auto range = [&](int k, int* i0, int* i1) { *i0 = (int)((int64_t)b->n * k / T); *i1 = (int)((int64_t)b->n * (k + 1) / T); };
-  auto run_all = [&](auto&& fn) {
-    std::vector<std::thread> th;
-    for (int k = 0; k < T; ++k) { if (k + 1 < T) th.emplace_back(fn, k); else fn(k); }
-    for (auto& x : th) x.join();
-  };
-  // phase 0: size of every (thread, kind, splint) slice from an upper bound of its records; one pooled arena holds them all
-  std::vector<size_t> bc((size_t)T * NS, 0), bs((size_t)T * NS, 0);
-  run_all([&](int k) { int i0, i1; range(k, &i0, &i1); bound_range(b, res, cons, cons_off, splint_id, n_splints, zero, i0, i1, &bc[(size_t)k * NS], &bs[(size_t)k * NS]); });
-  size_t need = 64;
-  for (size_t x : bc) need += x;
-  for (size_t x : bs) need += x;
-  Arena ar = arena_get(need);
-  if (!ar.p) return C3_E_NOMEM;
-  std::vector<char*> sc((size_t)T * NS), ss((size_t)T * NS);             // slice starts
-  { char* p = ar.p; for (size_t x = 0; x < (size_t)T * NS; ++x) { sc[x] = p; p += bc[x]; ss[x] = p; p += bs[x]; } }
-  std::vector<Out> oc((size_t)T * NS), os((size_t)T * NS);
-  for (size_t x = 0; x < (size_t)T * NS; ++x) { oc[x].p = sc[x]; os[x].p = ss[x]; }
-  // phase 1: format (parallel), straight into the slices
-  run_all([&](int k) { int i0, i1; range(k, &i0, &i1); format_range(b, res, cons, cons_off, splint_id, n_splints, zero, i0, i1, &oc[(size_t)k * NS], &os[(size_t)k * NS]); });
-  if (getenv("C3_WRITER_NO_IO")) { arena_put(ar); return C3_E_OK; }      // diagnostic (tools/formatter_throughput.py): the formatter alone
+  Formatted f;
+  int rc = format_group(b, res, cons, cons_off, splint_id, n_splints, zero, f);
+  if (rc) return rc;
+  const int T = f.T; const size_t NS = f.NS;
+  if (getenv("C3_WRITER_NO_IO")) { arena_put(f.ar); return C3_E_OK; }      // diagnostic (tools/formatter_throughput.py): the formatter alone
   // phase 2: one pwrite stream per (thread, file), offsets from the current file size
   struct Job { int fd; const char* txt; size_t len; off_t at; };
   std::vector<std::vector<Job>> jobs((size_t)T);
@@ -718,7 +795,7 @@ extern "C" int c3_write_group(const c3_host_batch* b, const c3_read_result* res,
     for (int kind = 0; kind < 2 && ok; ++kind) {
       const char* path = kind ? sub_paths[s] : cons_paths[s];
       size_t total = 0;
-      for (int k = 0; k < T; ++k) { const size_t x = (size_t)k * NS + (size_t)s; total += kind ? (size_t)(os[x].p - ss[x]) : (size_t)(oc[x].p - sc[x]); }
+      for (int k = 0; k < T; ++k) total += f.len(kind, (size_t)k * NS + (size_t)s);
       if (!total || !path) continue;
       int fd = open(path, O_WRONLY | O_CREAT, 0644);
       if (fd < 0) { ok = false; break; }
@@ -726,20 +803,50 @@ extern "C" int c3_write_group(const c3_host_batch* b, const c3_read_result* res,
       off_t at = reserve_append(fd, total);                 // several writer threads (one per GPU worker) append to one file
       for (int k = 0; k < T; ++k) {
         const size_t x = (size_t)k * NS + (size_t)s;
-        const char* t0 = kind ? ss[x] : sc[x];
-        const size_t len = kind ? (size_t)(os[x].p - ss[x]) : (size_t)(oc[x].p - sc[x]);
-        if (len) { jobs[(size_t)k].push_back({fd, t0, len, at}); at += (off_t)len; }
+        const size_t len = f.len(kind, x);
+        if (len) { jobs[(size_t)k].push_back({fd, f.txt(kind, x), len, at}); at += (off_t)len; }
       }
     }
   }
   if (ok) {
     std::vector<char> good((size_t)T, 1);
-    run_all([&](int k) { for (const Job& j : jobs[(size_t)k]) if (!pwrite_all(j.fd, j.txt, j.len, j.at)) good[(size_t)k] = 0; });
+    f.run_all([&](int k) { for (const Job& j : jobs[(size_t)k]) if (!pwrite_all(j.fd, j.txt, j.len, j.at)) good[(size_t)k] = 0; });
     for (char g : good) ok = ok && g;
   }
-  arena_put(ar);
+  arena_put(f.ar);
   for (int fd : fds) { release_append(fd); if (close(fd) != 0) ok = false; }
   return ok ? C3_E_OK : C3_E_ARG;
+}
+
+// --bgzf: the same slices; each file's text of the call (its T slices in record order) is compressed through z as one text
+// (the slices land back to back on the device), so the members do not depend on C3_WRITER_THREADS
+extern "C" int c3_write_group_bgzf(c3_bgzf* z, const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
+                                   const int16_t* splint_id, int n_splints, const char* const* cons_paths,
+                                   const char* const* sub_paths, int zero) {
+  if (!z || !b || !res || !cons_off || !splint_id || n_splints <= 0 || !cons_paths || !sub_paths) return C3_E_ARG;
+  Formatted f;
+  int rc = format_group(b, res, cons, cons_off, splint_id, n_splints, zero, f);
+  if (rc) return rc;
+  const int T = f.T; const size_t NS = f.NS;
+  std::vector<const char*> pp((size_t)T);
+  std::vector<int64_t> pl((size_t)T);
+  Arena zb;
+  for (int s = 0; s < n_splints && rc == C3_E_OK; ++s) {
+    for (int kind = 0; kind < 2 && rc == C3_E_OK; ++kind) {
+      const char* path = kind ? sub_paths[s] : cons_paths[s];
+      int64_t total = 0;
+      for (int k = 0; k < T; ++k) { const size_t x = (size_t)k * NS + (size_t)s; pp[(size_t)k] = f.txt(kind, x); pl[(size_t)k] = (int64_t)f.len(kind, x); total += pl[(size_t)k]; }
+      if (!total || !path) continue;
+      const int64_t cap = c3_bgzf_bound(total);
+      if (zb.cap < (size_t)cap) { arena_put(zb); zb = arena_get((size_t)cap); if (!zb.p) { rc = C3_E_NOMEM; break; } }
+      int64_t clen = 0;
+      rc = c3_bgzf_compress_pieces(z, pp.data(), pl.data(), T, zb.p, (int64_t)zb.cap, &clen);
+      if (rc == C3_E_OK && !append_file(path, zb.p, (size_t)clen, &f)) rc = C3_E_ARG;
+    }
+  }
+  arena_put(zb);
+  arena_put(f.ar);
+  return rc;
 }
 
 // R2C2_Consensus.fastq beside the FASTA: the consensus records of c3_write_group (emit_of, same header) with the QV line.
@@ -748,32 +855,12 @@ extern "C" int c3_write_group(const c3_host_batch* b, const c3_read_result* res,
 extern "C" int c3_write_consensus_fastq(const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
                                         const char* qv, const int16_t* splint_id, int n_splints, const char* const* fq_paths, int zero) {
   if (!b || !res || !cons || !cons_off || !qv || !splint_id || n_splints <= 0 || !fq_paths) return C3_E_ARG;
-  std::vector<size_t> bound((size_t)n_splints, 0);
-  for (int i = 0; i < b->n; ++i) {
-    const int64_t clen = cons_off[i + 1] - cons_off[i];
-    const Emit e = emit_of(res[i], splint_id[i], n_splints, zero, clen);
-    if (e.cons) bound[(size_t)splint_id[i]] += (size_t)(b->name_off[i + 1] - b->name_off[i]) + 2 * (size_t)clen + 96;
-  }
+  const std::vector<size_t> bound = consensus_fastq_bounds(b, res, cons_off, splint_id, n_splints, zero);
   bool ok = true;
   for (int s = 0; s < n_splints && ok; ++s) {
     if (!bound[(size_t)s] || !fq_paths[s]) continue;
     std::vector<char> buf(bound[(size_t)s]);
-    Out o{buf.data()};
-    for (int i = 0; i < b->n; ++i) {
-      if (splint_id[i] != s) continue;
-      const int64_t clen = cons_off[i + 1] - cons_off[i];
-      const Emit e = emit_of(res[i], s, n_splints, zero, clen);
-      if (!e.cons) continue;
-      const char* name = b->names + b->name_off[i]; const size_t nl = (size_t)(b->name_off[i + 1] - b->name_off[i]);
-      const int64_t L = b->off[i + 1] - b->off[i];
-      o.put('@'); o.app(name, nl); o.put('_');
-      avg_qual_text(b->quals + b->off[i], L, o);
-      o.put('_'); o.num((long long)L); o.put('_'); o.num(e.ns);
-      o.put('_'); o.num((long long)clen); o.put('\n');
-      o.app(cons + cons_off[i], (size_t)clen); o.app("\n+\n", 3);
-      o.app(qv + cons_off[i], (size_t)clen); o.put('\n');
-    }
-    const size_t total = (size_t)(o.p - buf.data());
+    const size_t total = format_consensus_fastq(b, res, cons, cons_off, qv, splint_id, n_splints, zero, s, buf.data());
     if (!total) continue;
     const int fd = open(fq_paths[s], O_WRONLY | O_CREAT, 0644);
     if (fd < 0) { ok = false; break; }
@@ -783,6 +870,25 @@ extern "C" int c3_write_consensus_fastq(const c3_host_batch* b, const c3_read_re
     if (close(fd) != 0) ok = false;
   }
   return ok ? C3_E_OK : C3_E_ARG;
+}
+
+extern "C" int c3_write_consensus_fastq_bgzf(c3_bgzf* z, const c3_host_batch* b, const c3_read_result* res, const char* cons,
+                                             const int64_t* cons_off, const char* qv, const int16_t* splint_id, int n_splints,
+                                             const char* const* fq_paths, int zero) {
+  if (!z || !b || !res || !cons || !cons_off || !qv || !splint_id || n_splints <= 0 || !fq_paths) return C3_E_ARG;
+  const std::vector<size_t> bound = consensus_fastq_bounds(b, res, cons_off, splint_id, n_splints, zero);
+  int rc = C3_E_OK;
+  for (int s = 0; s < n_splints && rc == C3_E_OK; ++s) {
+    if (!bound[(size_t)s] || !fq_paths[s]) continue;
+    std::vector<char> buf(bound[(size_t)s]);
+    const int64_t total = (int64_t)format_consensus_fastq(b, res, cons, cons_off, qv, splint_id, n_splints, zero, s, buf.data());
+    if (!total) continue;
+    std::vector<char> zbuf((size_t)c3_bgzf_bound(total));
+    int64_t clen = 0;
+    rc = c3_bgzf_compress(z, buf.data(), total, zbuf.data(), (int64_t)zbuf.size(), &clen);
+    if (rc == C3_E_OK && !append_file(fq_paths[s], zbuf.data(), (size_t)clen)) rc = C3_E_ARG;
+  }
+  return rc;
 }
 
 // ---- oligo-dT index matcher of the post-processing step (C3POa_postprocessing.py:266-285, match_index) ----------

@@ -73,6 +73,9 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
     if isinstance(assigner, dict):
         assigner = DictAssigner(assigner, splint_names)
     compress = bool(getattr(args, "compress_output", False))
+    # --bgzf (implies -co): every writer call compresses its text on the GPU (k_bgzf) and appends BGZF members to <path>.gz;
+    # no uncompressed file is created and there is no pass after the run
+    bgzf = bool(getattr(args, "bgzf", False))
     cons_paths = [args.out_path + n + "/R2C2_Consensus.fasta" for n in splint_names]
     sub_paths = [args.out_path + n + "/R2C2_Subreads.fastq" for n in splint_names]
     # --consensus-fastq: per-base QVs on the GPU (STAGE_QV) and R2C2_Consensus.fastq beside the FASTA
@@ -86,13 +89,24 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
         sp_lens = [len(splint_dict[n][0]) for n in splint_names]
     if isinstance(assigner, DictAssigner):
         used |= set(v[0] for v in assigner.d.values())
+    gz_made = []                                    # --bgzf: the .gz files of this run (each gets the EOF member at the end)
     for k, (n, cp, sp) in enumerate(zip(splint_names, cons_paths, sub_paths)):
         if n in used:
             os.makedirs(args.out_path + n, exist_ok=True)
             for p in (cp, sp) + ((fq_paths[k],) if qv_on else ()):                                   # "w+" semantics of cat_files (C3POa.py:88-92)
+                if bgzf:
+                    open(p + ".gz", "w").close()
+                    gz_made.append(p + ".gz")
+                    if os.path.exists(p):
+                        os.remove(p)
+                    continue
                 open(p, "w").close()
                 if os.path.exists(p + ".gz"):
                     os.remove(p + ".gz")
+    if bgzf:
+        cons_w, sub_w, fq_w = [p + ".gz" for p in cons_paths], [p + ".gz" for p in sub_paths], [p + ".gz" for p in fq_paths]
+    else:
+        cons_w, sub_w, fq_w = cons_paths, sub_paths, fq_paths
     # C3_GPU_BATCH_READS overrides the GPU batch size (tests drive the multi-batch pipeline with small inputs)
     gpu_batch = int(os.environ.get("C3_GPU_BATCH_READS", "0"))
     batch_reads = gpu_batch if gpu_batch > 0 else max(int(args.groupSize), GPU_BATCH_READS)
@@ -179,11 +193,15 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
                 free_sets[k].put(ks)
             parsed[k].put(None)
 
-    def device_thread(w):                           # one per GPU: c3_batch_run sizes its stages on the host, so it blocks
+    def worker_device(w):                           # the physical device of worker w
         dev = w % n_dev
         if os.environ.get("C3_DEVICE_MAP"):             # test hook: worker -> physical device (two workers on one GPU)
             dmap = [int(x) for x in os.environ["C3_DEVICE_MAP"].split(",")]
             dev = dmap[dev % len(dmap)]
+        return dev
+
+    def device_thread(w):                           # one per GPU: c3_batch_run sizes its stages on the host, so it blocks
+        dev = worker_device(w)
         mine = [k for k in range(n_ranges) if k % n_work == w]      # the ranges this worker serves, round-robin
         live = list(mine)
         rr = [0]
@@ -332,6 +350,7 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
         to_write[w].put(None)
 
     def writer_thread(w):                           # c3_write_group releases the GIL: overlaps parsing and the GPUs
+        z = None                                    # --bgzf: this writer's c3_bgzf, on its worker's device
         while True:
             item = to_write[w].get()
             if item is None:
@@ -340,9 +359,16 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
             t0 = time.perf_counter()
             try:
                 if not errors:
-                    _lib.write_group(hb, res, buf, coff, sid, cons_paths, sub_paths, getattr(args, "zero", True))
-                    if qv_on:
-                        _lib.write_consensus_fastq(hb, res, buf, coff, qv, sid, fq_paths, getattr(args, "zero", True))
+                    if bgzf:
+                        if z is None:
+                            z = _lib.Bgzf(worker_device(w))
+                        _lib.write_group_bgzf(z, hb, res, buf, coff, sid, cons_w, sub_w, getattr(args, "zero", True))
+                        if qv_on:
+                            _lib.write_consensus_fastq_bgzf(z, hb, res, buf, coff, qv, sid, fq_w, getattr(args, "zero", True))
+                    else:
+                        _lib.write_group(hb, res, buf, coff, sid, cons_paths, sub_paths, getattr(args, "zero", True))
+                        if qv_on:
+                            _lib.write_consensus_fastq(hb, res, buf, coff, qv, sid, fq_paths, getattr(args, "zero", True))
             except Exception as e:                  # noqa: BLE001
                 errors.append(e)
             with lock:
@@ -351,6 +377,8 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
             del hb, item, res, buf, coff, qv
             free_results.put(rb)
             free_sets[k].put(j)
+        if z is not None:
+            z.close()
 
     t_start = time.perf_counter()
     rthreads = [threading.Thread(target=reader_thread, args=(k,), daemon=True) for k in range(n_ranges)]
@@ -377,6 +405,7 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
         for k, (n, cp, sp) in enumerate(zip(splint_names, cons_paths, sub_paths)):
             if n not in seen:                                       # adapter_set of bin/preprocess.py:34,43 = splints that were hit
                 for p in (cp, sp) + ((fq_paths[k],) if qv_on else ()):
+                    p = p + ".gz" if bgzf else p                    # (before the EOF members: an unused .gz is still empty)
                     if os.path.exists(p) and os.stat(p).st_size == 0:
                         os.remove(p)
                 try:
@@ -384,7 +413,12 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
                 except OSError:
                     pass
         t["adapter_set"] = sorted(seen)
-    if compress:                                                        # -co (C3POa.py:88-90)
+    if bgzf:                                                            # every writer is done: the EOF member ends each file
+        for p in gz_made:
+            if os.path.exists(p):
+                with open(p, "ab") as fh:
+                    fh.write(_lib.BGZF_EOF)
+    elif compress:                                                      # -co (C3POa.py:88-90)
         for p in cons_paths + sub_paths + fq_paths:
             if os.path.exists(p):
                 with open(p, "rb") as src, gzip.open(p + ".gz", "wb", compresslevel=6) as dst:

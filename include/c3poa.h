@@ -383,6 +383,28 @@ int c3_consensus_qv_host(const char* cons, int n, int n_pieces, const char* seq_
 int c3_write_consensus_fastq(const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
                              const char* qv, const int16_t* splint_id, int n_splints, const char* const* fq_paths, int zero);
 
+/* ---- BGZF output (--bgzf) ----
+ * Text is cut into blocks of 65 280 bytes (the last one shorter); each block becomes one BGZF member holding one final
+ * deflate block: dynamic Huffman with literals and end-of-block only (optimal length-limited codes), or a stored block
+ * where that is not smaller.  Output = the members back to back (no EOF member; n = 0 gives no bytes).
+ * c3_bgzf_compress runs k_bgzf on the device of a c3_bgzf (device buffers and a stream of its own; one per thread, not
+ * thread-safe); c3_bgzf_compress_host is its host statement, byte for byte.  cap < c3_bgzf_bound(n) and null arguments
+ * return C3_E_ARG before anything is launched.  Errors of the handle-free calls through c3_last_error(NULL). */
+typedef struct c3_bgzf c3_bgzf;
+int c3_bgzf_create(int device, c3_bgzf** out);
+void c3_bgzf_destroy(c3_bgzf* z);
+int64_t c3_bgzf_bound(int64_t n);
+int c3_bgzf_compress(c3_bgzf* z, const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len);
+int c3_bgzf_compress_host(const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len);
+/* c3_write_group / c3_write_consensus_fastq with each file's text of the call (all records, in record order) compressed
+ * through z and appended (compressed size reserved as in c3_write_group) to the paths, which name the .gz files.  The
+ * caller appends the 28-byte BGZF EOF member once the last writer of a file is done. */
+int c3_write_group_bgzf(c3_bgzf* z, const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
+                        const int16_t* splint_id, int n_splints, const char* const* cons_paths, const char* const* sub_paths, int zero);
+int c3_write_consensus_fastq_bgzf(c3_bgzf* z, const c3_host_batch* b, const c3_read_result* res, const char* cons,
+                                  const int64_t* cons_off, const char* qv, const int16_t* splint_id, int n_splints,
+                                  const char* const* fq_paths, int zero);
+
 #ifdef __cplusplus
 }
 #endif
