@@ -52,6 +52,10 @@ def parse_args(argv=None):
     parser.add_argument("--bgzf", action="store_true", default=False,
                         help="Compress the outputs to BGZF on the GPU while the run goes (implies -co: the same .gz file "
                              "names, readable by gzip, without an uncompressed file or a pass after the run). Off by default.")
+    parser.add_argument("--inflate", choices=["host", "gpu"], default="host",
+                        help="Where a BGZF .gz input is inflated: zlib threads on the host (default), or the GPU (the "
+                             "inflater threads' cores go back to the parser and the writers). Any other gzip file is read "
+                             "as before.")
     parser.add_argument("--consensus-fastq", dest="consensus_fastq", action="store_true", default=False,
                         help="Also write <splint>/R2C2_Consensus.fastq: every consensus with per-base support QVs computed on "
                              "the GPU (not calibrated error probabilities; see DESIGN.md). Off by default.")

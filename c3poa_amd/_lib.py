@@ -28,7 +28,8 @@ EXPORTS = ["c3_default_config", "c3_version", "c3_device_count", "c3_warm_device
            "c3_batch_results_fetch_qv", "c3_batch_results_qv", "c3_batch_qv_timing", "c3_consensus_qv", "c3_consensus_qv_host",
            "c3_write_consensus_fastq",
            "c3_bgzf_create", "c3_bgzf_destroy", "c3_bgzf_bound", "c3_bgzf_compress", "c3_bgzf_compress_host",
-           "c3_write_group_bgzf", "c3_write_consensus_fastq_bgzf"]
+           "c3_write_group_bgzf", "c3_write_consensus_fastq_bgzf",
+           "c3_bgzf_scan", "c3_bgzf_decompress", "c3_bgzf_decompress_host", "c3_reader_open_inflate", "c3_reader_inflate_wait"]
 
 
 ZERO_MAX_CELLS = 16777216       # c3_default_config's zero_max_cells: largest front * tail the zero-repeat rescue takes
@@ -162,12 +163,21 @@ def load():
     lib.c3_bgzf_compress_host.argtypes = [vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64)]
     lib.c3_write_group_bgzf.argtypes = [vp, C.POINTER(HostBatchStruct), vp, vp, vp, vp, C.c_int, C.POINTER(cp), C.POINTER(cp), C.c_int]
     lib.c3_write_consensus_fastq_bgzf.argtypes = [vp, C.POINTER(HostBatchStruct), vp, vp, vp, vp, vp, C.c_int, C.POINTER(cp), C.c_int]
+    lib.c3_bgzf_scan.argtypes = [vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.c3_bgzf_decompress.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64)]
+    lib.c3_bgzf_decompress_host.argtypes = [vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64)]
+    lib.c3_reader_open_inflate.argtypes = [cp, C.c_int, C.c_int, C.POINTER(vp)]
+    lib.c3_reader_inflate_wait.argtypes = [vp]
+    lib.c3_reader_inflate_wait.restype = C.c_double
     _lib = lib
     return lib
 
 
 class C3Error(RuntimeError):
-    pass
+    code = None                 # the c3_err value, where the raising call knows it (E_DATA: damaged input)
+
+
+E_ARG, E_DATA = -3, -7          # include/c3poa.h c3_err
 
 
 def default_config(**kw):
@@ -728,11 +738,18 @@ class HostBatch:
 class Reader:
     """native streaming FASTA/FASTQ(.gz) reader (c3_reader_*): mm.fastx_read replacement that yields SoA groups"""
 
-    def __init__(self, path, n_sets=3, names_only=False, byte_range=None):
-        """byte_range = (beg, end): only the records that START inside [beg, end) (plain files; c3_reader_open_range)"""
+    def __init__(self, path, n_sets=3, names_only=False, byte_range=None, inflate_device=None):
+        """byte_range = (beg, end): only the records that START inside [beg, end) (plain files; c3_reader_open_range)
+        inflate_device = d: a BGZF file is inflated by k_inflate on device d (c3_reader_open_inflate; whole-file readers)"""
         self.lib = load()
         self.r = C.c_void_p()
-        if byte_range is None:
+        if inflate_device is not None:
+            if byte_range is not None:
+                raise ValueError("inflate_device goes with a whole-file reader")
+            rc = self.lib.c3_reader_open_inflate(_b(str(path)), n_sets, int(inflate_device), C.byref(self.r))
+            if rc not in (0, E_ARG):
+                raise C3Error("c3_reader_open_inflate failed (%d): %s" % (rc, self.lib.c3_last_error(None).decode()))
+        elif byte_range is None:
             rc = self.lib.c3_reader_open(_b(str(path)), n_sets, C.byref(self.r))
         else:
             rc = self.lib.c3_reader_open_range(_b(str(path)), n_sets, int(byte_range[0]), int(byte_range[1]), C.byref(self.r))
@@ -760,6 +777,10 @@ class Reader:
 
     def reserved_bytes(self):
         return int(self.lib.c3_reader_reserved_bytes(self.r))
+
+    def inflate_wait(self):
+        """seconds the parser waited for inflated bytes of a BGZF file (either inflater); 0 for other files"""
+        return float(self.lib.c3_reader_inflate_wait(self.r))
 
     def range_lost(self):
         """a byte-range reader whose range holds bytes but no record start (multi-line FASTQ): read the file with one reader"""
@@ -882,6 +903,43 @@ def bgzf_compress_host(data):
     return _bgzf_call(load().c3_bgzf_compress_host, (), data)
 
 
+# ---- BGZF input (--inflate gpu; include/c3poa.h "BGZF input") ----
+def _c3_fail(rc):
+    e = C3Error("c3 error %d: %s" % (rc, load().c3_last_error(None).decode()))
+    e.code = rc
+    return e
+
+
+def _bytes(data):
+    return _b(data) if not isinstance(data, (bytes, bytearray, memoryview)) else bytes(data)
+
+
+def bgzf_scan(data):
+    """c3_bgzf_scan: (members, inflated bytes) of a buffer of whole BGZF members, from the headers alone"""
+    src = _bytes(data)
+    nm, ob = C.c_int64(0), C.c_int64(0)
+    rc = load().c3_bgzf_scan(src, len(src), C.byref(nm), C.byref(ob))
+    if rc != 0:
+        raise _c3_fail(rc)
+    return nm.value, ob.value
+
+
+def _bgzf_inflate(fn, first, data):
+    src = _bytes(data)
+    cap = bgzf_scan(src)[1]
+    out = C.create_string_buffer(max(cap, 1))
+    olen = C.c_int64(0)
+    rc = fn(*(first + (src, len(src), out, cap, C.byref(olen))))
+    if rc != 0:
+        raise _c3_fail(rc)
+    return out.raw[:olen.value]
+
+
+def bgzf_decompress_host(data):
+    """c3_bgzf_decompress_host: the text of the BGZF members `data`; the host statement of Bgzf.decompress (no zlib)"""
+    return _bgzf_inflate(load().c3_bgzf_decompress_host, (), data)
+
+
 class Bgzf:
     """c3_bgzf: k_bgzf on one device (device buffers and a stream of its own; one per thread)"""
 
@@ -894,6 +952,10 @@ class Bgzf:
 
     def compress(self, data):
         return _bgzf_call(self.lib.c3_bgzf_compress, (self.z,), data)
+
+    def decompress(self, data):
+        """c3_bgzf_decompress: the text of the BGZF members `data` (k_inflate); C3Error with code E_DATA on a damaged member"""
+        return _bgzf_inflate(self.lib.c3_bgzf_decompress, (self.z,), data)
 
     def close(self):
         if self.z:

@@ -3,6 +3,7 @@
 #include "c3_dev.h"
 #include "c3_args.h"
 #include "c3_bgzf.h"
+#include "c3_inflate.h"
 #include <algorithm>
 #include <cstddef>
 #include <cstdio>
@@ -28,6 +29,7 @@ extern "C" void c3k_launch_zero_finish(const ZeroArgs*, int, hipStream_t);
 extern "C" void c3k_launch_qv(const QvArgs*, int, hipStream_t);
 extern "C" int c3k_qv_lds_max(void);
 extern "C" void c3k_launch_bgzf(const uint8_t*, long long, int, uint8_t*, int*, uint8_t*, hipStream_t);
+extern "C" void c3k_launch_inflate(const uint8_t*, const C3BgzfMember*, int, uint8_t*, int2*, hipStream_t);
 
 // ---- small kernels ----------------------------------------------------------------------
 __device__ __forceinline__ uint32_t pack_code(uint32_t b) {
@@ -1497,6 +1499,8 @@ extern "C" int c3_determine_consensus(c3_handle* h, int n, const char* const* su
 struct c3_bgzf {
   int device = 0; hipStream_t stream = nullptr; int* h_sizes = nullptr;
   DBuf d_in, d_slots, d_sizes, d_packed;
+  C3BgzfMember* h_mem = nullptr; int2* h_res = nullptr;         // k_inflate: descriptors in, (status, CRC) out; first use
+  DBuf d_mem, d_res, d_out;
 };
 
 extern "C" int c3_bgzf_create(int device, c3_bgzf** out) {
@@ -1520,6 +1524,8 @@ extern "C" void c3_bgzf_destroy(c3_bgzf* z) {
   (void)hipSetDevice(z->device);
   if (z->stream) { (void)hipStreamSynchronize(z->stream); (void)hipStreamDestroy(z->stream); }
   if (z->h_sizes) (void)hipHostFree(z->h_sizes);
+  if (z->h_mem) (void)hipHostFree(z->h_mem);
+  if (z->h_res) (void)hipHostFree(z->h_res);
   delete z;
 }
 
@@ -1584,4 +1590,69 @@ extern "C" int c3_bgzf_compress_pieces(c3_bgzf* z, const char* const* p, const i
 extern "C" int c3_bgzf_compress(c3_bgzf* z, const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len) {
   if (!z || !out_len || n < 0 || (n > 0 && !src)) { g_create_err = "c3_bgzf_compress: bad arguments"; return C3_E_ARG; }
   return c3_bgzf_compress_pieces(z, &src, &n, 1, dst, cap, out_len);
+}
+
+// ---- BGZF input (k_inflate.hip; host statement c3_inflate.cpp) ----------------------------
+// The host walks the member headers (c3_bgzf_member_at); INFLATE_CHUNK_MEMBERS members at a time go to the device: their
+// bytes as they stand in src, the descriptors, k_inflate, (status, CRC) back, and -- only when every member of the chunk
+// was accepted -- the inflated bytes straight into the caller's buffer.
+#define INFLATE_CHUNK_MEMBERS 4096             // measured 1 024 .. 16 384 per launch: 2 048 leaves 2 waves per SIMD
+static int inflate_chunk() {                                          // C3_INFLATE_CHUNK: measurement hook (tools/inflate_throughput.py)
+  static const int v = [] { const char* e = getenv("C3_INFLATE_CHUNK"); const int x = e ? atoi(e) : 0; return x >= 64 && x <= 16384 ? x : INFLATE_CHUNK_MEMBERS; }();
+  return v;
+}
+int c3_bgzf_data_error(const char* who, int64_t member, int st);      // c3_inflate.cpp
+
+extern "C" int c3_bgzf_decompress(c3_bgzf* z, const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len) {
+  if (!z || !out_len || n < 0 || (n > 0 && !src)) { g_create_err = "c3_bgzf_decompress: bad arguments"; return C3_E_ARG; }
+  *out_len = 0;
+  int64_t nm = 0, ob = 0;
+  const int rc = c3_bgzf_scan(src, n, &nm, &ob);
+  if (rc) return rc;
+  if (cap < ob || (ob > 0 && !dst)) { g_create_err = "c3_bgzf_decompress: cap < inflated size (c3_bgzf_scan)"; return C3_E_ARG; }
+  if (nm == 0) return C3_E_OK;
+  hipError_t e = hipSetDevice(z->device);
+  if (e != hipSuccess) return bgzf_fail(e, "hipSetDevice");
+  const int CH = inflate_chunk();
+  if (!z->h_mem) e = hipHostMalloc((void**)&z->h_mem, CH * sizeof(C3BgzfMember), hipHostMallocDefault);
+  if (e == hipSuccess && !z->h_res) e = hipHostMalloc((void**)&z->h_res, CH * sizeof(int2), hipHostMallocDefault);
+  if (e != hipSuccess) return bgzf_fail(e, "descriptor buffers");
+  if ((e = z->d_mem.ensure(CH * sizeof(C3BgzfMember))) != hipSuccess) return bgzf_fail(e, "descriptors");
+  if ((e = z->d_res.ensure(CH * sizeof(int2))) != hipSuccess) return bgzf_fail(e, "statuses");
+  int64_t at = 0, o = 0, done = 0;
+  while (done < nm) {
+    const int k = (int)std::min<int64_t>(CH, nm - done);
+    const int64_t c0 = at;
+    uint32_t oo = 0;
+    for (int i = 0; i < k; ++i) {
+      C3BgzfMember& m = z->h_mem[i];
+      const uint32_t size = c3_bgzf_member_at((const unsigned char*)src, n, at, &m);      // (c3_bgzf_scan accepted them all)
+      m.poff += (uint32_t)(at - c0); m.ooff = oo;
+      oo += m.isize; at += size;
+    }
+    const int64_t cn = at - c0;
+    if ((e = z->d_in.ensure((size_t)cn + 256)) != hipSuccess) return bgzf_fail(e, "input buffer");
+    if ((e = z->d_out.ensure((size_t)oo + 256)) != hipSuccess) return bgzf_fail(e, "output buffer");
+    e = hipMemcpyAsync(z->d_in.p, src + c0, (size_t)cn, hipMemcpyHostToDevice, z->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(z->d_mem.p, z->h_mem, (size_t)k * sizeof(C3BgzfMember), hipMemcpyHostToDevice, z->stream);
+    if (e != hipSuccess) return bgzf_fail(e, "copy in");
+    c3k_launch_inflate(z->d_in.as<uint8_t>(), z->d_mem.as<C3BgzfMember>(), k, z->d_out.as<uint8_t>(), z->d_res.as<int2>(), z->stream);
+    if ((e = hipGetLastError()) != hipSuccess) return bgzf_fail(e, "k_inflate launch");
+    e = hipMemcpyAsync(z->h_res, z->d_res.p, (size_t)k * sizeof(int2), hipMemcpyDeviceToHost, z->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(z->stream);
+    if (e != hipSuccess) return bgzf_fail(e, "k_inflate");
+    for (int i = 0; i < k; ++i) {
+      int st = z->h_res[i].x;
+      if (st == C3_INF_OK && (uint32_t)z->h_res[i].y != z->h_mem[i].crc) st = C3_INF_CRC;
+      if (st != C3_INF_OK) return c3_bgzf_data_error("c3_bgzf_decompress", done + i, st);
+    }
+    if (oo) {
+      e = hipMemcpyAsync(dst + o, z->d_out.p, (size_t)oo, hipMemcpyDeviceToHost, z->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(z->stream);
+      if (e != hipSuccess) return bgzf_fail(e, "copy out");
+    }
+    o += oo; done += k;
+  }
+  *out_len = o;
+  return C3_E_OK;
 }

@@ -88,4 +88,21 @@ C3_BGZF_HD inline uint32_t bgzf_multmodp(uint32_t a, uint32_t b) {
   }
   return p;
 }
+// entry t of the byte-wise CRC table
+C3_BGZF_HD inline uint32_t bgzf_crc_entry(uint32_t t) {
+  for (int k = 0; k < 8; ++k) t = (t & 1) ? (t >> 1) ^ 0xEDB88320u : t >> 1;
+  return t;
+}
+// x2n[k] = x^(2^k) mod p, k < 20
+C3_BGZF_HD inline void bgzf_x2n_init(uint32_t* x2n) {
+  uint32_t p = 1u << 30;                                       // x^1
+  x2n[0] = p;
+  for (int k = 1; k < 20; ++k) { p = bgzf_multmodp(p, p); x2n[k] = p; }
+}
+// the CRC of a piece moved in front of `after` < 65536 more bytes: multiplication by x^(8 * after)
+C3_BGZF_HD inline uint32_t bgzf_crc_shift(const uint32_t* x2n, uint32_t after, uint32_t crc) {
+  uint32_t p = 1u << 31;                                       // x^0
+  for (int k = 0; k < 16; ++k) if ((after >> k) & 1u) p = bgzf_multmodp(x2n[k + 3], p);
+  return bgzf_multmodp(p, crc);
+}
 #endif

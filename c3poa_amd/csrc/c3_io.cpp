@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
+#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -84,6 +85,9 @@ struct Bgzf {
   size_t dpos = 0;                          // unread part of st[cur].dec starts here
   std::thread pre; bool pre_on = false, pre_ok = false;
   std::atomic<bool> eof{false}, bad{false};  // (written by the prefetch thread, read by the parser)
+  c3_bgzf* dev = nullptr;                   // c3_reader_open_inflate: stretches are inflated by k_inflate, not by zlib threads
+  std::string why;                          // the device call's error text (written before bad is set)
+  double wait_s = 0;                        // the parser waiting for a stretch (c3_reader_inflate_wait)
 };
 
 struct c3_reader {
@@ -135,6 +139,7 @@ bool bgzf_inflate(const unsigned char* m, size_t msz, char* out, size_t osz) {
 
 // next stretch of the file: up to `max_members` members read, located by their headers, inflated by b->threads threads
 bool bgzf_next_stretch(Bgzf* bz, BgzfStretch* b, size_t max_members = 512) {
+  if (bz->dev) max_members = 4096;                              // one k_inflate launch: a wave per member
   b->comp.clear(); b->coff.clear(); b->csz.clear(); b->doff.clear();
   b->dend = 0;
   size_t dtot = 0;
@@ -173,6 +178,13 @@ bool bgzf_next_stretch(Bgzf* bz, BgzfStretch* b, size_t max_members = 512) {
   if (b->coff.empty()) return false;
   b->dec.resize(dtot);
   const size_t nm = b->coff.size();
+  if (bz->dev) {                                                // one device call for the stretch; never zlib when the device was asked for
+    int64_t got = 0;
+    const int rc = c3_bgzf_decompress(bz->dev, (const char*)b->comp.data(), (int64_t)b->comp.size(), b->dec.data(), (int64_t)dtot, &got);
+    if (rc != C3_E_OK || (size_t)got != dtot) { bz->why = c3_last_error(nullptr); bz->bad = true; return false; }
+    b->dend = dtot;
+    return true;
+  }
   auto work = [&](size_t t0, size_t step, bool* ok) {
     for (size_t i = t0; i < nm; i += step) {
       const size_t osz = (i + 1 < nm ? b->doff[i + 1] : dtot) - b->doff[i];
@@ -194,6 +206,8 @@ bool bgzf_next_stretch(Bgzf* bz, BgzfStretch* b, size_t max_members = 512) {
 // thread of its own (which fans out to b->threads inflaters): the reader thread only waits when inflating is the slower side
 long bgzf_read(Bgzf* b, char* dst, size_t room) {
   if (b->dpos == b->st[b->cur].dend) {
+    struct Wait { Bgzf* b; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+                  ~Wait() { b->wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } wait{b};
     if (b->pre_on) { b->pre.join(); b->pre_on = false; if (b->pre_ok) { b->cur ^= 1; b->dpos = 0; } else b->st[b->cur].dend = b->dpos = 0; }
     else { if (b->bad || !bgzf_next_stretch(b, &b->st[b->cur])) return b->bad ? -1 : 0; b->dpos = 0; }
     if (b->bad) return -1;
@@ -215,7 +229,7 @@ bool refill(c3_reader* r) {
   long got = r->bz ? bgzf_read(r->bz, r->buf.data() + r->end, room)
            : r->gz ? (long)gzread(r->gz, r->buf.data() + r->end, (unsigned)std::min<size_t>(room, 1u << 30))
                    : (long)fread(r->buf.data() + r->end, 1, room, r->fp);
-  if (got < 0 && r->bz) r->err = "BGZF input: a member is damaged (size, inflate or CRC)";
+  if (got < 0 && r->bz) r->err = "BGZF input: a member is damaged (size, inflate or CRC)" + (r->bz->why.empty() ? std::string() : ": " + r->bz->why);
   if (got <= 0) { r->eof = true; return false; }
   r->end += (size_t)got;
   return true;
@@ -301,6 +315,20 @@ extern "C" int c3_reader_open(const char* path, int n_sets, c3_reader** out) {
   return C3_E_OK;
 }
 
+extern "C" int c3_reader_open_inflate(const char* path, int n_sets, int device, c3_reader** out) {
+  if (!path || !out) return C3_E_ARG;
+  *out = nullptr;
+  c3_bgzf* z = nullptr;
+  int rc = c3_bgzf_create(device, &z);                          // first: no usable GPU is an error whatever the file is
+  if (rc != C3_E_OK) return rc;
+  c3_reader* r = nullptr;
+  rc = c3_reader_open(path, n_sets, &r);
+  if (rc != C3_E_OK) { c3_bgzf_destroy(z); return rc; }
+  if (r->bz) r->bz->dev = z; else c3_bgzf_destroy(z);           // plain gzip / plain text: read as c3_reader_open reads it
+  *out = r;
+  return C3_E_OK;
+}
+
 namespace {
 
 // Is `p` (a line start inside [buf, buf+n)) the header of a record?  FASTA: '>' is unambiguous.  FASTQ: '@' also opens
@@ -379,13 +407,15 @@ extern "C" void c3_reader_close(c3_reader* r) {
   if (!r) return;
   if (r->gz) gzclose(r->gz);
   if (r->fp) fclose(r->fp);
-  if (r->bz) { if (r->bz->pre_on) r->bz->pre.join(); if (r->bz->fp) fclose(r->bz->fp); delete r->bz; }
+  if (r->bz) { if (r->bz->pre_on) r->bz->pre.join(); if (r->bz->fp) fclose(r->bz->fp); if (r->bz->dev) c3_bgzf_destroy(r->bz->dev); delete r->bz; }
   delete r;
 }
 
 // names_only != 0: sequences and qualities are parsed (lengths, offsets and the short-read count stay exact) but not
 // stored -- the first pass of C3POa.py:200-207 only needs names
 extern "C" void c3_reader_names_only(c3_reader* r, int names_only) { if (r) r->names_only = names_only != 0; }
+
+extern "C" double c3_reader_inflate_wait(const c3_reader* r) { return r && r->bz ? r->bz->wait_s : 0.0; }
 
 extern "C" const char* c3_reader_error(const c3_reader* r) { return r ? r->err.c_str() : "null reader"; }
 

@@ -80,14 +80,8 @@ __global__ __launch_bounds__(256) void k_bgzf(const uint8_t* src, long long n, u
     uint4* im = (uint4*)L.img;
     for (int i = t; i < BGZF_SLOT / 16; i += 256) im[i] = make_uint4(0, 0, 0, 0);
     for (int i = t; i < 4 * BGZF_NSYM; i += 256) (&L.u.hist[0][0])[i] = 0;
-    uint32_t c = (uint32_t)t;
-    for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
-    L.crc_tab[t] = c;
-    if (t == 0) {
-      uint32_t p = 1u << 30;                          // x^1
-      L.x2n[0] = p;
-      for (int k = 1; k < 20; ++k) { p = bgzf_multmodp(p, p); L.x2n[k] = p; }
-    }
+    L.crc_tab[t] = bgzf_crc_entry((uint32_t)t);
+    if (t == 0) bgzf_x2n_init(L.x2n);
   }
   __syncthreads();
   // ---- 1. histogram
@@ -212,11 +206,7 @@ __global__ __launch_bounds__(256) void k_bgzf(const uint8_t* src, long long n, u
   // shift lane t's CRC to the end of the block: multiply by x^(8 * after)
   {
     const uint32_t after = (uint32_t)(nb - start - clen);
-    if (clen > 0 && after) {
-      uint32_t p = 1u << 31;                           // x^0
-      for (int k = 0; k < 16; ++k) if ((after >> k) & 1u) p = bgzf_multmodp(L.x2n[k + 3], p);
-      crc = bgzf_multmodp(p, crc);
-    }
+    if (clen > 0 && after) crc = bgzf_crc_shift(L.x2n, after, crc);
     for (int d = 32; d > 0; d >>= 1) crc ^= __shfl_xor(crc, d, 64);
     if (lane == 0) L.wcrc[wv] = crc;
   }

@@ -28,6 +28,13 @@ READERS_PER_GPU = 2              # byte-range readers (parser threads) per GPU w
 MIN_RANGE_BYTES = 256 << 20      # no point in cutting small inputs
 
 
+def _is_bgzf(path):
+    """what c3_reader_open looks at: the first gzip member opens with the BGZF size subfield 'BC'"""
+    with open(path, "rb") as fh:
+        hd = fh.read(18)
+    return len(hd) == 18 and hd[:3] == b"\x1f\x8b\x08" and bool(hd[3] & 4) and hd[10:16] == b"\x06\x00BC\x02\x00"
+
+
 def count_reads(path, lencutoff, assigner):
     """first pass of C3POa.py:200-207 + the bookkeeping of bin/preprocess.py:36-44: (reads passing the length cut-off,
     short reads, reads without a splint).  Names-only parse, native lookups."""
@@ -131,15 +138,30 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
     # round-robin sets would let a reader overwrite a set a lagging device still holds).  Result buffers follow the same
     # rule: one object per batch in flight, returned by the writer.
     N_SETS = 5                                      # (a sixth set would cover every stage at once; it costs 20 % more page-locked memory and start-up time for a stall that the timeline does not show)
+    def worker_device(w):                           # the physical device of worker w
+        dev = w % n_dev
+        if os.environ.get("C3_DEVICE_MAP"):             # test hook: worker -> physical device (two workers on one GPU)
+            dmap = [int(x) for x in os.environ["C3_DEVICE_MAP"].split(",")]
+            dev = dmap[dev % len(dmap)]
+        return dev
+
+    # --inflate gpu: the (single, whole-file) reader of a .gz input inflates its BGZF stretches with k_inflate on worker 0's
+    # device instead of zlib threads; any other gzip file has no member sizes to split on and is read as before
+    inflate_dev = None
+    if getattr(args, "inflate", "host") == "gpu" and str(args.reads).endswith(".gz"):
+        if _is_bgzf(args.reads):
+            inflate_dev = worker_device(0)
+        else:
+            print("C3POa: --inflate gpu: %s is gzip but not BGZF (no member size in front); only BGZF can be inflated on the GPU, the file is read as before" % args.reads, file=sys.stderr)
     readers = [_lib.Reader(args.reads, n_sets=N_SETS, byte_range=(cuts[k], cuts[k + 1])) if n_ranges > 1
-               else _lib.Reader(args.reads, n_sets=N_SETS) for k in range(n_ranges)]
+               else _lib.Reader(args.reads, n_sets=N_SETS, inflate_device=inflate_dev) for k in range(n_ranges)]
     if n_ranges > 1 and any(r.range_lost() for r in readers):
         # a range with bytes but no 4-line record start (multi-line FASTQ, which mm.fastx_read accepts): such a file cannot be
         # entered in the middle -- its records would be dropped silently -- so ONE reader takes the whole file
         for r in readers:
             r.close()
         n_ranges, cuts = 1, [0, -1]
-        readers = [_lib.Reader(args.reads, n_sets=N_SETS)]
+        readers = [_lib.Reader(args.reads, n_sets=N_SETS, inflate_device=inflate_dev)]
     free_sets = [queue.Queue() for _ in range(n_ranges)]
     for fs in free_sets:
         for j in range(N_SETS):
@@ -192,13 +214,6 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
             if ks is not None:
                 free_sets[k].put(ks)
             parsed[k].put(None)
-
-    def worker_device(w):                           # the physical device of worker w
-        dev = w % n_dev
-        if os.environ.get("C3_DEVICE_MAP"):             # test hook: worker -> physical device (two workers on one GPU)
-            dmap = [int(x) for x in os.environ["C3_DEVICE_MAP"].split(",")]
-            dev = dmap[dev % len(dmap)]
-        return dev
 
     def device_thread(w):                           # one per GPU: c3_batch_run sizes its stages on the host, so it blocks
         dev = worker_device(w)
@@ -394,6 +409,7 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
         raise errors[0]
     for th in rthreads:
         th.join()
+    t["inflate_wait"] = sum(r.inflate_wait() for r in readers)         # BGZF input: the parser waiting for inflated bytes
     if keep_pinned:                                 # one-shot process (the CLI): process teardown releases the page-locked buffers
         _KEPT.extend(readers)
     else:

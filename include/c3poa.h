@@ -31,7 +31,8 @@ typedef enum {
   C3_E_ARG = -3,
   C3_E_NOMEM = -4,
   C3_E_STATE = -5,
-  C3_E_LIMIT = -6
+  C3_E_LIMIT = -6,
+  C3_E_DATA = -7                                /* damaged input: a BGZF member that does not inflate to what its trailer says */
 } c3_err;
 
 /* per-read status (same numbering as the oracle's) */
@@ -396,6 +397,25 @@ void c3_bgzf_destroy(c3_bgzf* z);
 int64_t c3_bgzf_bound(int64_t n);
 int c3_bgzf_compress(c3_bgzf* z, const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len);
 int c3_bgzf_compress_host(const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len);
+/* ---- BGZF input (--inflate gpu) ----
+ * replaces the zlib threads of the reader (mm.fastx_read on a .gz file, C3POa.py:201,239) for BGZF files.  A member is
+ * accepted exactly when its raw deflate stream (all of RFC 1951, zlib's rules for code sets) ends inside the payload,
+ * yields ISIZE <= 65536 bytes and their CRC-32 is the trailer's; bytes after the stream's end are ignored.  Any other
+ * member fails the whole call with C3_E_DATA and a c3_last_error(NULL) text naming the first bad member and the reason;
+ * never a short or altered result.
+ * c3_bgzf_scan walks the member headers of a buffer that holds whole members: count (empty members included) and total
+ * ISIZE; C3_E_DATA when it is not BGZF.  c3_bgzf_decompress runs k_inflate on the device of a c3_bgzf;
+ * c3_bgzf_decompress_host is its host statement (the same decoder, c3_inflate.h, on one CPU thread; no zlib).
+ * cap < out_bytes, null arguments and a null handle return C3_E_ARG; n == 0 is success with out_len = 0. */
+int c3_bgzf_scan(const char* src, int64_t n, int64_t* n_members, int64_t* out_bytes);
+int c3_bgzf_decompress(c3_bgzf* z, const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len);
+int c3_bgzf_decompress_host(const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len);
+/* c3_reader_open, but a BGZF file's stretches are inflated by k_inflate on `device` (a c3_bgzf owned by the reader)
+ * instead of zlib threads; a file that is not BGZF (plain gzip, plain text) is read exactly as c3_reader_open reads it.
+ * C3_E_NO_DEVICE without a usable GPU: asking for the device never falls back to zlib. */
+int c3_reader_open_inflate(const char* path, int n_sets, int device, c3_reader** out);
+/* seconds the parser has waited for inflated bytes of a BGZF file so far, with either inflater (C3_STREAM_STATS); 0 for other files */
+double c3_reader_inflate_wait(const c3_reader* r);
 /* c3_write_group / c3_write_consensus_fastq with each file's text of the call (all records, in record order) compressed
  * through z and appended (compressed size reserved as in c3_write_group) to the paths, which name the .gz files.  The
  * caller appends the 28-byte BGZF EOF member once the last writer of a file is done. */
