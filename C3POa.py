@@ -56,6 +56,10 @@ def parse_args(argv=None):
                         help="Where a BGZF .gz input is inflated: zlib threads on the host (default), or the GPU (the "
                              "inflater threads' cores go back to the parser and the writers). Any other gzip file is read "
                              "as before.")
+    parser.add_argument("--parse", choices=["host", "gpu"], default="host",
+                        help="Where the records of a BGZF .gz input are found: the reader's parser thread on the host "
+                             "(default), or the GPU, where --inflate gpu has left the text (needs --inflate gpu; strict "
+                             "four-line FASTQ is parsed there, anything else by the host parser as before).")
     parser.add_argument("--consensus-fastq", dest="consensus_fastq", action="store_true", default=False,
                         help="Also write <splint>/R2C2_Consensus.fastq: every consensus with per-base support QVs computed on "
                              "the GPU (not calibrated error probabilities; see DESIGN.md). Off by default.")
@@ -66,6 +70,8 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.bgzf:
         args.compress_output = True
+    if args.parse == "gpu" and args.inflate != "gpu":
+        parser.error("--parse gpu needs --inflate gpu: records are parsed on the GPU only where the text was inflated there")
     return args
 
 

@@ -29,7 +29,8 @@ EXPORTS = ["c3_default_config", "c3_version", "c3_device_count", "c3_warm_device
            "c3_write_consensus_fastq",
            "c3_bgzf_create", "c3_bgzf_destroy", "c3_bgzf_bound", "c3_bgzf_compress", "c3_bgzf_compress_host",
            "c3_write_group_bgzf", "c3_write_consensus_fastq_bgzf",
-           "c3_bgzf_scan", "c3_bgzf_decompress", "c3_bgzf_decompress_host", "c3_reader_open_inflate", "c3_reader_inflate_wait"]
+           "c3_bgzf_scan", "c3_bgzf_decompress", "c3_bgzf_decompress_host", "c3_reader_open_inflate", "c3_reader_inflate_wait",
+           "c3_fastq_parse", "c3_fastq_parse_host", "c3_reader_parse_on_device", "c3_reader_parse_stats"]
 
 
 ZERO_MAX_CELLS = 16777216       # c3_default_config's zero_max_cells: largest front * tail the zero-repeat rescue takes
@@ -69,6 +70,13 @@ class Timing(C.Structure):
 
 class QvTiming(C.Structure):
     _fields_ = [("ms_qv", C.c_float)] + [(n, C.c_int64) for n in ("n_reads", "n_pieces", "n_skipped", "band_cells", "edge_hits")]
+
+
+class FastqInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_records", "n_kept", "n_short", "consumed", "name_bytes", "base_bytes")] + [("departed", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _t in self._fields_}
 
 
 class HostBatchStruct(C.Structure):
@@ -169,6 +177,11 @@ def load():
     lib.c3_reader_open_inflate.argtypes = [cp, C.c_int, C.c_int, C.POINTER(vp)]
     lib.c3_reader_inflate_wait.argtypes = [vp]
     lib.c3_reader_inflate_wait.restype = C.c_double
+    fq = [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(FastqInfo)]
+    lib.c3_fastq_parse.argtypes = [vp] + fq
+    lib.c3_fastq_parse_host.argtypes = fq
+    lib.c3_reader_parse_on_device.argtypes = [vp, C.c_int]
+    lib.c3_reader_parse_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _lib = lib
     return lib
 
@@ -178,6 +191,7 @@ class C3Error(RuntimeError):
 
 
 E_ARG, E_DATA = -3, -7          # include/c3poa.h c3_err
+E_STATE, E_LIMIT = -5, -6
 
 
 def default_config(**kw):
@@ -738,9 +752,11 @@ class HostBatch:
 class Reader:
     """native streaming FASTA/FASTQ(.gz) reader (c3_reader_*): mm.fastx_read replacement that yields SoA groups"""
 
-    def __init__(self, path, n_sets=3, names_only=False, byte_range=None, inflate_device=None):
+    def __init__(self, path, n_sets=3, names_only=False, byte_range=None, inflate_device=None, parse_device=False):
         """byte_range = (beg, end): only the records that START inside [beg, end) (plain files; c3_reader_open_range)
-        inflate_device = d: a BGZF file is inflated by k_inflate on device d (c3_reader_open_inflate; whole-file readers)"""
+        inflate_device = d: a BGZF file is inflated by k_inflate on device d (c3_reader_open_inflate; whole-file readers)
+        parse_device: ... and its records are parsed there too (k_fastq; c3_reader_parse_on_device).  C3Error with code
+        E_STATE when the reader is not one of a BGZF file with inflate_device"""
         self.lib = load()
         self.r = C.c_void_p()
         if inflate_device is not None:
@@ -757,6 +773,13 @@ class Reader:
             raise OSError("cannot open %s" % path)
         if names_only:
             self.lib.c3_reader_names_only(self.r, 1)
+        if parse_device:
+            rc = self.lib.c3_reader_parse_on_device(self.r, 1)
+            if rc != 0:
+                e = C3Error("c3_reader_parse_on_device failed (%d): %s" % (rc, self.lib.c3_reader_error(self.r).decode()))
+                e.code = rc
+                self.close()
+                raise e
 
     def next(self, max_reads, min_len=0, max_bases=0, set_index=None):
         """next group; set_index names the buffer set to fill (caller-managed free list), None = round-robin"""
@@ -781,6 +804,13 @@ class Reader:
     def inflate_wait(self):
         """seconds the parser waited for inflated bytes of a BGZF file (either inflater); 0 for other files"""
         return float(self.lib.c3_reader_inflate_wait(self.r))
+
+    def parse_stats(self):
+        """(stretches parsed on the device, stretches parsed on the host, records delivered from the device) of a
+        parse_device reader: c3_reader_parse_stats"""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self.lib.c3_reader_parse_stats(self.r, C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value, c.value
 
     def range_lost(self):
         """a byte-range reader whose range holds bytes but no record start (multi-line FASTQ): read the file with one reader"""
@@ -940,6 +970,66 @@ def bgzf_decompress_host(data):
     return _bgzf_inflate(load().c3_bgzf_decompress_host, (), data)
 
 
+# ---- FASTQ records on the GPU (--parse gpu; include/c3poa.h "FASTQ records on the GPU") ----
+FASTQ_GUARD = 64                # bytes of 0xA5 either side of every output array of a fastq_parse call
+
+
+class FastqParse:
+    """result of c3_fastq_parse / c3_fastq_parse_host: info (dict), names / seqs / quals (bytes), name_off / off (int64
+    arrays of n_kept + 1), guards_intact (the FASTQ_GUARD bytes either side of every output array are untouched)"""
+
+    def records(self):
+        no, o = self.name_off, self.off
+        return [(self.names[no[i]:no[i + 1]], self.seqs[o[i]:o[i + 1]], self.quals[o[i]:o[i + 1]]) for i in range(len(o) - 1)]
+
+
+def _fastq_call(fn, first, text, at_eof, min_len, text_offset=0, caps=None):
+    src = _bytes(text)
+    n = len(src)
+    # the text at byte `text_offset` (0..3) of a dword
+    raw = np.zeros(n + 16, dtype=np.uint8)
+    at = (-raw.ctypes.data) % 4 + int(text_offset)
+    raw[at:at + n] = np.frombuffer(src, dtype=np.uint8)
+    names_cap, bases_cap, max_records = caps if caps is not None else (n, n // 2 + 1, n // 7 + 1)
+    g = FASTQ_GUARD
+
+    def arr(nbytes):
+        a = np.full(nbytes + 2 * g, 0xA5, dtype=np.uint8)
+        return a
+
+    bufs = {"names": arr(names_cap), "seqs": arr(bases_cap), "quals": arr(bases_cap),
+            "name_off": arr(8 * (max_records + 1)), "off": arr(8 * (max_records + 1))}
+    ptr = {k: v.ctypes.data + g for k, v in bufs.items()}
+    info = FastqInfo()
+    rc = fn(*(first + (raw.ctypes.data + at if n else None, n, int(bool(at_eof)), int(min_len), ptr["names"], names_cap, ptr["name_off"],
+                       ptr["seqs"], ptr["quals"], bases_cap, ptr["off"], max_records, C.byref(info))))
+    out = FastqParse()
+    out.info = info.as_dict()
+    used = {"names": 0, "seqs": 0, "quals": 0, "name_off": 0, "off": 0}
+    if rc == 0:
+        nk = out.info["n_kept"]
+        used = {"names": out.info["name_bytes"], "seqs": out.info["base_bytes"], "quals": out.info["base_bytes"],
+                "name_off": 8 * (nk + 1), "off": 8 * (nk + 1)}
+    # guards, and on a refused call every byte of the arrays: nothing half written
+    out.guards_intact = all(bool((v[:g] == 0xA5).all()) and bool((v[len(v) - g:] == 0xA5).all()) for v in bufs.values())
+    out.untouched_beyond_results = all(bool((v[g + used[k]:] == 0xA5).all()) for k, v in bufs.items())
+    if rc != 0:
+        e = _c3_fail(rc)
+        e.info, e.guards_intact, e.untouched = out.info, out.guards_intact, out.untouched_beyond_results
+        raise e
+    for k in ("names", "seqs", "quals"):
+        setattr(out, k, bufs[k][g:g + used[k]].tobytes())
+    for k in ("name_off", "off"):
+        setattr(out, k, bufs[k][g:g + used[k]].view(np.int64).copy())
+    return out
+
+
+def fastq_parse_host(text, at_eof=False, min_len=0, text_offset=0, caps=None):
+    """c3_fastq_parse_host: the longest prefix of whole strict records of `text`; the host statement of Bgzf.fastq_parse.
+    caps = (names_cap, bases_cap, max_records) instead of sizes that always fit; C3Error (code E_LIMIT, .info) when too small"""
+    return _fastq_call(load().c3_fastq_parse_host, (), text, at_eof, min_len, text_offset, caps)
+
+
 class Bgzf:
     """c3_bgzf: k_bgzf on one device (device buffers and a stream of its own; one per thread)"""
 
@@ -956,6 +1046,11 @@ class Bgzf:
     def decompress(self, data):
         """c3_bgzf_decompress: the text of the BGZF members `data` (k_inflate); C3Error with code E_DATA on a damaged member"""
         return _bgzf_inflate(self.lib.c3_bgzf_decompress, (self.z,), data)
+
+    def fastq_parse(self, text, at_eof=False, min_len=0, text_offset=0, caps=None):
+        """c3_fastq_parse: the strict FASTQ records of `text` found and gathered by k_fastq (a FastqParse); text_offset
+        0..3 = where the text starts inside a dword, which the device copy keeps"""
+        return _fastq_call(self.lib.c3_fastq_parse, (self.z,), text, at_eof, min_len, text_offset, caps)
 
     def close(self):
         if self.z:

@@ -3,6 +3,7 @@
 #include "c3_dev.h"
 #include "c3_args.h"
 #include "c3_bgzf.h"
+#include "c3_fastq.h"
 #include "c3_inflate.h"
 #include <algorithm>
 #include <cstddef>
@@ -30,6 +31,11 @@ extern "C" void c3k_launch_qv(const QvArgs*, int, hipStream_t);
 extern "C" int c3k_qv_lds_max(void);
 extern "C" void c3k_launch_bgzf(const uint8_t*, long long, int, uint8_t*, int*, uint8_t*, hipStream_t);
 extern "C" void c3k_launch_inflate(const uint8_t*, const C3BgzfMember*, int, uint8_t*, int2*, hipStream_t);
+extern "C" void c3k_launch_fastq_count(const uint8_t*, uint32_t, uint32_t, int32_t*, int, C3FqHdr*, hipStream_t);
+extern "C" void c3k_launch_fastq_lines(const uint8_t*, uint32_t, uint32_t, const int32_t*, int32_t*, hipStream_t);
+extern "C" void c3k_launch_fastq_records(const uint8_t*, uint32_t, uint32_t, const int32_t*, int, int, int, int, int32_t*, int32_t*, long long*,
+                                         C3FqHdr*, int64_t*, int64_t*, int4*, hipStream_t);
+extern "C" void c3k_launch_fastq_gather(const uint8_t*, const int4*, const int64_t*, const int64_t*, long long, uint8_t*, uint8_t*, uint8_t*, hipStream_t);
 
 // ---- small kernels ----------------------------------------------------------------------
 __device__ __forceinline__ uint32_t pack_code(uint32_t b) {
@@ -1501,6 +1507,16 @@ struct c3_bgzf {
   DBuf d_in, d_slots, d_sizes, d_packed;
   C3BgzfMember* h_mem = nullptr; int2* h_res = nullptr;         // k_inflate: descriptors in, (status, CRC) out; first use
   DBuf d_mem, d_res, d_out;
+  // k_fastq (first use): scratch of one parse, and two slots of text + finished records (the reader parses one stretch while
+  // the groups of the other are copied out on copy_stream; the stand-alone call uses slot 0)
+  struct FqSlot {
+    DBuf text, names, seqs, quals, off, name_off, src;
+    int64_t text_n = 0, n_rec = 0;
+    int64_t* h_off = nullptr; int64_t* h_name_off = nullptr; size_t h_cap = 0;       // page-locked copies of off / name_off
+  } fq[2];
+  DBuf d_cnt, d_nl, d_slen, d_nlen, d_bsum, d_hdr;
+  C3FqHdr* h_hdr = nullptr;
+  hipStream_t copy_stream = nullptr;
 };
 
 extern "C" int c3_bgzf_create(int device, c3_bgzf** out) {
@@ -1526,6 +1542,9 @@ extern "C" void c3_bgzf_destroy(c3_bgzf* z) {
   if (z->h_sizes) (void)hipHostFree(z->h_sizes);
   if (z->h_mem) (void)hipHostFree(z->h_mem);
   if (z->h_res) (void)hipHostFree(z->h_res);
+  if (z->copy_stream) { (void)hipStreamSynchronize(z->copy_stream); (void)hipStreamDestroy(z->copy_stream); }
+  if (z->h_hdr) (void)hipHostFree(z->h_hdr);
+  for (auto& f : z->fq) { if (f.h_off) (void)hipHostFree(f.h_off); if (f.h_name_off) (void)hipHostFree(f.h_name_off); }
   delete z;
 }
 
@@ -1603,14 +1622,9 @@ static int inflate_chunk() {                                          // C3_INFL
 }
 int c3_bgzf_data_error(const char* who, int64_t member, int st);      // c3_inflate.cpp
 
-extern "C" int c3_bgzf_decompress(c3_bgzf* z, const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len) {
-  if (!z || !out_len || n < 0 || (n > 0 && !src)) { g_create_err = "c3_bgzf_decompress: bad arguments"; return C3_E_ARG; }
-  *out_len = 0;
-  int64_t nm = 0, ob = 0;
-  const int rc = c3_bgzf_scan(src, n, &nm, &ob);
-  if (rc) return rc;
-  if (cap < ob || (ob > 0 && !dst)) { g_create_err = "c3_bgzf_decompress: cap < inflated size (c3_bgzf_scan)"; return C3_E_ARG; }
-  if (nm == 0) return C3_E_OK;
+// nm members of src (all accepted by c3_bgzf_scan) inflated into the caller's dst, or -- d_dst != null -- left on the device
+// at d_dst (the reader's device parse); either way every member's CRC is compared here before the call returns
+static int bgzf_inflate_members(c3_bgzf* z, const char* src, int64_t n, int64_t nm, uint8_t* d_dst, char* dst, int64_t* out_len) {
   hipError_t e = hipSetDevice(z->device);
   if (e != hipSuccess) return bgzf_fail(e, "hipSetDevice");
   const int CH = inflate_chunk();
@@ -1632,11 +1646,11 @@ extern "C" int c3_bgzf_decompress(c3_bgzf* z, const char* src, int64_t n, char* 
     }
     const int64_t cn = at - c0;
     if ((e = z->d_in.ensure((size_t)cn + 256)) != hipSuccess) return bgzf_fail(e, "input buffer");
-    if ((e = z->d_out.ensure((size_t)oo + 256)) != hipSuccess) return bgzf_fail(e, "output buffer");
+    if (!d_dst && (e = z->d_out.ensure((size_t)oo + 256)) != hipSuccess) return bgzf_fail(e, "output buffer");
     e = hipMemcpyAsync(z->d_in.p, src + c0, (size_t)cn, hipMemcpyHostToDevice, z->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(z->d_mem.p, z->h_mem, (size_t)k * sizeof(C3BgzfMember), hipMemcpyHostToDevice, z->stream);
     if (e != hipSuccess) return bgzf_fail(e, "copy in");
-    c3k_launch_inflate(z->d_in.as<uint8_t>(), z->d_mem.as<C3BgzfMember>(), k, z->d_out.as<uint8_t>(), z->d_res.as<int2>(), z->stream);
+    c3k_launch_inflate(z->d_in.as<uint8_t>(), z->d_mem.as<C3BgzfMember>(), k, d_dst ? d_dst + o : z->d_out.as<uint8_t>(), z->d_res.as<int2>(), z->stream);
     if ((e = hipGetLastError()) != hipSuccess) return bgzf_fail(e, "k_inflate launch");
     e = hipMemcpyAsync(z->h_res, z->d_res.p, (size_t)k * sizeof(int2), hipMemcpyDeviceToHost, z->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(z->stream);
@@ -1646,7 +1660,7 @@ extern "C" int c3_bgzf_decompress(c3_bgzf* z, const char* src, int64_t n, char* 
       if (st == C3_INF_OK && (uint32_t)z->h_res[i].y != z->h_mem[i].crc) st = C3_INF_CRC;
       if (st != C3_INF_OK) return c3_bgzf_data_error("c3_bgzf_decompress", done + i, st);
     }
-    if (oo) {
+    if (oo && !d_dst) {
       e = hipMemcpyAsync(dst + o, z->d_out.p, (size_t)oo, hipMemcpyDeviceToHost, z->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(z->stream);
       if (e != hipSuccess) return bgzf_fail(e, "copy out");
@@ -1654,5 +1668,213 @@ extern "C" int c3_bgzf_decompress(c3_bgzf* z, const char* src, int64_t n, char* 
     o += oo; done += k;
   }
   *out_len = o;
+  return C3_E_OK;
+}
+
+extern "C" int c3_bgzf_decompress(c3_bgzf* z, const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len) {
+  if (!z || !out_len || n < 0 || (n > 0 && !src)) { g_create_err = "c3_bgzf_decompress: bad arguments"; return C3_E_ARG; }
+  *out_len = 0;
+  int64_t nm = 0, ob = 0;
+  const int rc = c3_bgzf_scan(src, n, &nm, &ob);
+  if (rc) return rc;
+  if (cap < ob || (ob > 0 && !dst)) { g_create_err = "c3_bgzf_decompress: cap < inflated size (c3_bgzf_scan)"; return C3_E_ARG; }
+  if (nm == 0) return C3_E_OK;
+  return bgzf_inflate_members(z, src, n, nm, nullptr, dst, out_len);
+}
+
+// ---- FASTQ records on the GPU (k_fastq.hip; host statement c3_fastq.cpp) -------------------
+// One parse = three waits: the line count (sizes nl[] and the record tables), the header (sizes the outputs, answers the
+// capacity question before any byte is gathered), the finished arrays.
+int c3_fastq_check_args(const char* who, const char* text, int64_t n, const char* names, int64_t names_cap, const int64_t* name_off,
+                        const char* seqs, const char* quals, int64_t bases_cap, const int64_t* off, int64_t max_records,
+                        c3_fastq_info* info);                         // c3_fastq.cpp
+
+static int fq_prepare(c3_bgzf* z) {
+  hipError_t e = hipSetDevice(z->device);
+  if (e != hipSuccess) return bgzf_fail(e, "hipSetDevice");
+  if (!z->h_hdr) e = hipHostMalloc((void**)&z->h_hdr, sizeof(C3FqHdr), hipHostMallocDefault);
+  if (e == hipSuccess && !z->copy_stream) e = hipStreamCreateWithFlags(&z->copy_stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = z->d_hdr.ensure(sizeof(C3FqHdr));
+  if (e != hipSuccess) return bgzf_fail(e, "k_fastq buffers");
+  return C3_E_OK;
+}
+
+// the text [lo, lo + n) of sl.text parsed: tables and header on the device, *info filled; no byte gathered yet
+static int fq_parse_device(c3_bgzf* z, c3_bgzf::FqSlot& sl, uint32_t lo, int64_t n, int at_eof, int min_len, c3_fastq_info* info) {
+  memset(info, 0, sizeof *info);
+  sl.n_rec = 0;
+  if (n == 0) return C3_E_OK;
+  hipError_t e;
+  const uint32_t hi = lo + (uint32_t)n;
+  const size_t tiles = ((size_t)hi + 65535) / 65536;
+  const uint8_t* buf = sl.text.as<uint8_t>();
+  C3FqHdr* hdr = z->d_hdr.as<C3FqHdr>();
+  if ((e = z->d_cnt.ensure(tiles * 4 * sizeof(int32_t))) != hipSuccess) return bgzf_fail(e, "k_fastq counts");
+  c3k_launch_fastq_count(buf, lo, hi, z->d_cnt.as<int32_t>(), at_eof, hdr, z->stream);
+  if ((e = hipGetLastError()) != hipSuccess) return bgzf_fail(e, "k_fastq_count launch");
+  e = hipMemcpyAsync(z->h_hdr, hdr, sizeof(C3FqHdr), hipMemcpyDeviceToHost, z->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(z->stream);
+  if (e != hipSuccess) return bgzf_fail(e, "k_fastq_count");
+  const int L = z->h_hdr->n_lines, Lv = z->h_hdr->n_lines_v;
+  if (L < 0 || (int64_t)L > n || Lv < L || Lv > L + 1) { g_create_err = "k_fastq: line count out of range"; return C3_E_HIP; }
+  const int n_full = Lv / 4, partial = (at_eof && (Lv & 3)) ? 1 : 0;
+  if (n_full == 0 && !partial) return C3_E_OK;                        // no whole record yet: everything stays unconsumed
+  const size_t nr = (size_t)n_full + 1, nb = ((size_t)n_full + 255) / 256;
+  if ((e = z->d_nl.ensure(((size_t)L + 4) * sizeof(int32_t))) != hipSuccess) return bgzf_fail(e, "k_fastq lines");
+  if ((e = z->d_slen.ensure(nr * sizeof(int32_t))) != hipSuccess) return bgzf_fail(e, "k_fastq records");
+  if ((e = z->d_nlen.ensure(nr * sizeof(int32_t))) != hipSuccess) return bgzf_fail(e, "k_fastq records");
+  if ((e = z->d_bsum.ensure((nb + 1) * 3 * sizeof(long long))) != hipSuccess) return bgzf_fail(e, "k_fastq sums");
+  if ((e = sl.off.ensure(nr * sizeof(int64_t))) != hipSuccess) return bgzf_fail(e, "k_fastq offsets");
+  if ((e = sl.name_off.ensure(nr * sizeof(int64_t))) != hipSuccess) return bgzf_fail(e, "k_fastq offsets");
+  if ((e = sl.src.ensure(nr * sizeof(int4))) != hipSuccess) return bgzf_fail(e, "k_fastq sources");
+  c3k_launch_fastq_lines(buf, lo, hi, z->d_cnt.as<int32_t>(), z->d_nl.as<int32_t>(), z->stream);
+  c3k_launch_fastq_records(buf, lo, hi, z->d_nl.as<int32_t>(), L, n_full, partial, min_len, z->d_slen.as<int32_t>(), z->d_nlen.as<int32_t>(),
+                           z->d_bsum.as<long long>(), hdr, sl.off.as<int64_t>(), sl.name_off.as<int64_t>(), sl.src.as<int4>(), z->stream);
+  if ((e = hipGetLastError()) != hipSuccess) return bgzf_fail(e, "k_fastq_records launch");
+  e = hipMemcpyAsync(z->h_hdr, hdr, sizeof(C3FqHdr), hipMemcpyDeviceToHost, z->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(z->stream);
+  if (e != hipSuccess) return bgzf_fail(e, "k_fastq_records");
+  const C3FqHdr& h = *z->h_hdr;
+  if (h.n_records < 0 || h.n_records > n_full || h.n_kept < 0 || h.n_kept > h.n_records || h.consumed < 0 || h.consumed > n ||
+      h.base_bytes < 0 || h.base_bytes > n || h.name_bytes < 0 || h.name_bytes > n) { g_create_err = "k_fastq: header out of range"; return C3_E_HIP; }
+  info->n_records = h.n_records; info->n_kept = h.n_kept; info->n_short = h.n_short; info->consumed = h.consumed;
+  info->name_bytes = h.name_bytes; info->base_bytes = h.base_bytes; info->departed = h.departed;
+  sl.n_rec = h.n_kept;
+  return C3_E_OK;
+}
+
+// the kept records of the parse that fq_parse_device just made, gathered into sl.names / sl.seqs / sl.quals (queued, not waited for)
+static int fq_gather_device(c3_bgzf* z, c3_bgzf::FqSlot& sl, const c3_fastq_info& info) {
+  if (info.n_kept == 0) return C3_E_OK;
+  hipError_t e;
+  if ((e = sl.names.ensure((size_t)info.name_bytes + 256)) != hipSuccess) return bgzf_fail(e, "k_fastq names");
+  if ((e = sl.seqs.ensure((size_t)info.base_bytes + 256)) != hipSuccess) return bgzf_fail(e, "k_fastq bases");
+  if ((e = sl.quals.ensure((size_t)info.base_bytes + 256)) != hipSuccess) return bgzf_fail(e, "k_fastq qualities");
+  c3k_launch_fastq_gather(sl.text.as<uint8_t>(), sl.src.as<int4>(), sl.off.as<int64_t>(), sl.name_off.as<int64_t>(), (long long)info.n_kept,
+                          sl.names.as<uint8_t>(), sl.seqs.as<uint8_t>(), sl.quals.as<uint8_t>(), z->stream);
+  if ((e = hipGetLastError()) != hipSuccess) return bgzf_fail(e, "k_fastq_gather launch");
+  return C3_E_OK;
+}
+
+extern "C" int c3_fastq_parse(c3_bgzf* z, const char* text, int64_t n, int at_eof, int min_len, char* names, int64_t names_cap,
+                              int64_t* name_off, char* seqs, char* quals, int64_t bases_cap, int64_t* off, int64_t max_records,
+                              c3_fastq_info* info) {
+  int rc = c3_fastq_check_args("c3_fastq_parse", text, n, names, names_cap, name_off, seqs, quals, bases_cap, off, max_records, info);
+  if (rc) return rc;
+  if (!z) { g_create_err = "c3_fastq_parse: null handle"; return C3_E_ARG; }
+  if (n == 0) { name_off[0] = 0; off[0] = 0; return C3_E_OK; }
+  if ((rc = fq_prepare(z)) != C3_E_OK) return rc;
+  c3_bgzf::FqSlot& sl = z->fq[0];
+  const uint32_t lo = (uint32_t)((uintptr_t)text & 3u);               // the text keeps its place inside a dword: the kernels see the caller's misalignment
+  hipError_t e;
+  if ((e = sl.text.ensure((size_t)lo + (size_t)n + 256)) != hipSuccess) return bgzf_fail(e, "k_fastq text");
+  e = hipMemcpyAsync(sl.text.as<char>() + lo, text, (size_t)n, hipMemcpyHostToDevice, z->stream);
+  if (e != hipSuccess) return bgzf_fail(e, "copy in");
+  if ((rc = fq_parse_device(z, sl, lo, n, at_eof, min_len, info)) != C3_E_OK) return rc;
+  if (info->n_kept > max_records || info->name_bytes > names_cap || info->base_bytes > bases_cap) {
+    g_create_err = "c3_fastq_parse: capacity too small (needed sizes in info)";
+    return C3_E_LIMIT;
+  }
+  if (info->n_kept == 0) { name_off[0] = 0; off[0] = 0; return C3_E_OK; }
+  if ((rc = fq_gather_device(z, sl, *info)) != C3_E_OK) return rc;
+  const size_t nt = ((size_t)info->n_kept + 1) * sizeof(int64_t);
+  e = hipMemcpyAsync(off, sl.off.p, nt, hipMemcpyDeviceToHost, z->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(name_off, sl.name_off.p, nt, hipMemcpyDeviceToHost, z->stream);
+  if (e == hipSuccess && info->name_bytes) e = hipMemcpyAsync(names, sl.names.p, (size_t)info->name_bytes, hipMemcpyDeviceToHost, z->stream);
+  if (e == hipSuccess && info->base_bytes) e = hipMemcpyAsync(seqs, sl.seqs.p, (size_t)info->base_bytes, hipMemcpyDeviceToHost, z->stream);
+  if (e == hipSuccess && info->base_bytes) e = hipMemcpyAsync(quals, sl.quals.p, (size_t)info->base_bytes, hipMemcpyDeviceToHost, z->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(z->stream);
+  if (e != hipSuccess) return bgzf_fail(e, "k_fastq_gather");
+  return C3_E_OK;
+}
+
+// ---- the reader's device stretches (c3_io.cpp; not part of the public interface) ----------
+// Stretch = `carry_len` bytes of the other slot's text from `carry_from` on (the record its end cut), then the inflated
+// members of comp; it stays on the device, is parsed there with min_len 0 (the group rule, min_len included, is the
+// reader's), and the record tables come back.  On return the slot holds the finished records until it is loaded again.
+struct c3_fq_stretch { c3_fastq_info info; const int64_t* off; const int64_t* name_off; int64_t text_bytes; };
+
+extern "C" int c3_bgzf_stretch_parse(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, int64_t carry_from, int64_t carry_len,
+                                     int at_eof, c3_fq_stretch* out) {
+  if (!z || !out || slot < 0 || slot > 1 || ncomp < 0 || (ncomp > 0 && !comp) || carry_len < 0) { g_create_err = "c3_bgzf_stretch_parse: bad arguments"; return C3_E_ARG; }
+  memset(out, 0, sizeof *out);
+  int64_t nm = 0, ob = 0;
+  int rc = c3_bgzf_scan(comp, ncomp, &nm, &ob);
+  if (rc) return rc;
+  const int64_t total = carry_len + ob;
+  if (total > C3_FASTQ_MAX_TEXT) { g_create_err = "c3_bgzf_stretch_parse: stretch longer than C3_FASTQ_MAX_TEXT"; return C3_E_LIMIT; }
+  if ((rc = fq_prepare(z)) != C3_E_OK) return rc;
+  c3_bgzf::FqSlot& sl = z->fq[slot];
+  const c3_bgzf::FqSlot& other = z->fq[slot ^ 1];
+  if (carry_len > 0 && (carry_from < 0 || carry_from + carry_len > other.text_n)) { g_create_err = "c3_bgzf_stretch_parse: carry outside the other stretch"; return C3_E_ARG; }
+  hipError_t e;
+  if ((e = sl.text.ensure((size_t)total + 256)) != hipSuccess) return bgzf_fail(e, "stretch text");
+  sl.text_n = 0;
+  if (carry_len > 0) {
+    e = hipMemcpyAsync(sl.text.p, other.text.as<char>() + carry_from, (size_t)carry_len, hipMemcpyDeviceToDevice, z->stream);
+    if (e != hipSuccess) return bgzf_fail(e, "carry");
+  }
+  if (nm > 0) {
+    int64_t got = 0;
+    rc = bgzf_inflate_members(z, comp, ncomp, nm, sl.text.as<uint8_t>() + carry_len, nullptr, &got);
+    if (rc) return rc;
+    if (got != ob) { g_create_err = "c3_bgzf_stretch_parse: inflated size differs from the headers"; return C3_E_DATA; }
+  }
+  sl.text_n = total;
+  out->text_bytes = total;
+  if ((rc = fq_parse_device(z, sl, 0, total, at_eof, 0, &out->info)) != C3_E_OK) return rc;
+  const int64_t nk = out->info.n_kept;
+  if (nk > 0) {
+    if ((rc = fq_gather_device(z, sl, out->info)) != C3_E_OK) return rc;
+    if (sl.h_cap < (size_t)nk + 1) {
+      if (sl.h_off) (void)hipHostFree(sl.h_off);
+      if (sl.h_name_off) (void)hipHostFree(sl.h_name_off);
+      sl.h_off = sl.h_name_off = nullptr; sl.h_cap = 0;
+      const size_t want = (size_t)nk + 1 + (size_t)nk / 8 + 1024;
+      e = hipHostMalloc((void**)&sl.h_off, want * sizeof(int64_t), hipHostMallocDefault);
+      if (e == hipSuccess) e = hipHostMalloc((void**)&sl.h_name_off, want * sizeof(int64_t), hipHostMallocDefault);
+      if (e != hipSuccess) return bgzf_fail(e, "stretch tables");
+      sl.h_cap = want;
+    }
+    e = hipMemcpyAsync(sl.h_off, sl.off.p, ((size_t)nk + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, z->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(sl.h_name_off, sl.name_off.p, ((size_t)nk + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, z->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(z->stream);
+    if (e != hipSuccess) return bgzf_fail(e, "k_fastq_gather");
+    if (sl.h_off[0] != 0 || sl.h_name_off[0] != 0 || sl.h_off[nk] != out->info.base_bytes || sl.h_name_off[nk] != out->info.name_bytes) {
+      g_create_err = "k_fastq: offsets do not match the header"; return C3_E_HIP;
+    }
+    out->off = sl.h_off; out->name_off = sl.h_name_off;
+  }
+  return C3_E_OK;
+}
+
+// records [r0, r1) of the slot's stretch copied to the host (names / seqs / quals point at the place of record r0; seqs and
+// quals may be null: names only).  Runs on copy_stream: the other slot may be being loaded on another thread meanwhile.
+extern "C" int c3_bgzf_stretch_fetch(c3_bgzf* z, int slot, int64_t r0, int64_t r1, char* names, char* seqs, char* quals) {
+  if (!z || slot < 0 || slot > 1 || !names) { g_create_err = "c3_bgzf_stretch_fetch: bad arguments"; return C3_E_ARG; }
+  const c3_bgzf::FqSlot& sl = z->fq[slot];
+  if (r0 < 0 || r1 < r0 || r1 > sl.n_rec) { g_create_err = "c3_bgzf_stretch_fetch: records outside the stretch"; return C3_E_ARG; }
+  if (r0 == r1) return C3_E_OK;
+  hipError_t e = hipSetDevice(z->device);
+  if (e != hipSuccess) return bgzf_fail(e, "hipSetDevice");
+  const int64_t nb = sl.h_name_off[r0], ne = sl.h_name_off[r1], sb = sl.h_off[r0], se = sl.h_off[r1];
+  if (ne > nb) e = hipMemcpyAsync(names, sl.names.as<char>() + nb, (size_t)(ne - nb), hipMemcpyDeviceToHost, z->copy_stream);
+  if (e == hipSuccess && seqs && se > sb) e = hipMemcpyAsync(seqs, sl.seqs.as<char>() + sb, (size_t)(se - sb), hipMemcpyDeviceToHost, z->copy_stream);
+  if (e == hipSuccess && quals && se > sb) e = hipMemcpyAsync(quals, sl.quals.as<char>() + sb, (size_t)(se - sb), hipMemcpyDeviceToHost, z->copy_stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(z->copy_stream);
+  if (e != hipSuccess) return bgzf_fail(e, "stretch fetch");
+  return C3_E_OK;
+}
+
+// text [from, from + len) of the slot's stretch copied to the host (a departure: the host parser takes over from there)
+extern "C" int c3_bgzf_stretch_text(c3_bgzf* z, int slot, int64_t from, int64_t len, char* dst) {
+  if (!z || slot < 0 || slot > 1 || from < 0 || len < 0 || (len > 0 && !dst)) { g_create_err = "c3_bgzf_stretch_text: bad arguments"; return C3_E_ARG; }
+  const c3_bgzf::FqSlot& sl = z->fq[slot];
+  if (from + len > sl.text_n) { g_create_err = "c3_bgzf_stretch_text: bytes outside the stretch"; return C3_E_ARG; }
+  if (len == 0) return C3_E_OK;
+  hipError_t e = hipSetDevice(z->device);
+  if (e == hipSuccess) e = hipMemcpyAsync(dst, sl.text.as<char>() + from, (size_t)len, hipMemcpyDeviceToHost, z->copy_stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(z->copy_stream);
+  if (e != hipSuccess) return bgzf_fail(e, "stretch text");
   return C3_E_OK;
 }

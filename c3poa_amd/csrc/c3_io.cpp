@@ -71,11 +71,22 @@ struct BatchSet {
 // (extra subfield 'B','C'), so the members of a stretch of the file can be located WITHOUT inflating them and inflated by several
 // threads at once -- a plain gzip stream is one zlib state and inflates at ~275 MB/s whatever the machine (27 k reads/s:
 // profiles/r04_host_ceiling_gz.txt).  Plain gzip stays on gzread.
+// a stretch that stays on the device (c3_reader_parse_on_device): c3_api.hip inflates it behind the record the previous
+// stretch's end cut, parses it with k_fastq and keeps the finished records until the slot is loaded again
+struct c3_fq_stretch { c3_fastq_info info; const int64_t* off; const int64_t* name_off; int64_t text_bytes; };
+extern "C" int c3_bgzf_stretch_parse(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, int64_t carry_from, int64_t carry_len,
+                                     int at_eof, c3_fq_stretch* out);
+extern "C" int c3_bgzf_stretch_fetch(c3_bgzf* z, int slot, int64_t r0, int64_t r1, char* names, char* seqs, char* quals);
+extern "C" int c3_bgzf_stretch_text(c3_bgzf* z, int slot, int64_t from, int64_t len, char* dst);
+
 struct BgzfStretch {
   std::vector<unsigned char> comp;          // compressed members of the stretch, back to back
   std::vector<size_t> coff, csz, doff;      // per member: offset / size in comp, offset of its data in dec
   std::vector<char> dec;                    // inflated stretch
   size_t dend = 0;
+  bool on_dev = false;                      // parsed on the device: fq describes its records, next_rec is the first not yet in a group
+  c3_fq_stretch fq{};
+  int64_t next_rec = 0;
 };
 struct Bgzf {
   FILE* fp = nullptr;
@@ -88,6 +99,12 @@ struct Bgzf {
   c3_bgzf* dev = nullptr;                   // c3_reader_open_inflate: stretches are inflated by k_inflate, not by zlib threads
   std::string why;                          // the device call's error text (written before bad is set)
   double wait_s = 0;                        // the parser waiting for a stretch (c3_reader_inflate_wait)
+  size_t stretch_members = 4096;            // members per device stretch (C3_INFLATE_STRETCH_MEMBERS)
+  // c3_reader_parse_on_device: parse_req = asked for; parse_on = stretches are still loaded for the device parser (cleared at
+  // the first departure, before the next load starts); dev_active = the reader thread still has device records to hand out
+  bool parse_req = false, parse_on = false, dev_active = false;
+  int64_t carry_from = 0, carry_len = 0;    // the next load starts with these bytes of the current stretch's text
+  std::atomic<int64_t> n_dev{0}, n_host{0}, rec_dev{0};
 };
 
 struct c3_reader {
@@ -98,6 +115,7 @@ struct c3_reader {
   bool have_line = false; const char* lp = nullptr; size_t ll = 0;   // one line of look-ahead
   int64_t n_records = 0, n_noqual = 0;
   bool names_only = false;
+  bool started = false;         // c3_reader_next has been called
   bool range_lost = false;      // a byte range with bytes in it held no recognisable record start (e.g. multi-line FASTQ)
   size_t file_bytes = 0, hint_bases = 0;
   int64_t buf_off = 0;          // file offset of buf[0] (plain files)
@@ -139,7 +157,7 @@ bool bgzf_inflate(const unsigned char* m, size_t msz, char* out, size_t osz) {
 
 // next stretch of the file: up to `max_members` members read, located by their headers, inflated by b->threads threads
 bool bgzf_next_stretch(Bgzf* bz, BgzfStretch* b, size_t max_members = 512) {
-  if (bz->dev) max_members = 4096;                              // one k_inflate launch: a wave per member
+  if (bz->dev) max_members = bz->stretch_members;               // one k_inflate launch: a wave per member
   b->comp.clear(); b->coff.clear(); b->csz.clear(); b->doff.clear();
   b->dend = 0;
   size_t dtot = 0;
@@ -176,6 +194,16 @@ bool bgzf_next_stretch(Bgzf* bz, BgzfStretch* b, size_t max_members = 512) {
     dtot += isz;
   }
   if (b->coff.empty()) return false;
+  b->on_dev = false;
+  if (bz->dev && bz->parse_on) {                                // inflated and parsed on the device; only the record tables come back
+    const int rc = c3_bgzf_stretch_parse(bz->dev, (int)(b - bz->st), (const char*)b->comp.data(), (int64_t)b->comp.size(),
+                                         bz->carry_from, bz->carry_len, bz->eof ? 1 : 0, &b->fq);
+    if (rc != C3_E_OK) { bz->why = c3_last_error(nullptr); bz->bad = true; return false; }
+    b->on_dev = true; b->next_rec = 0; b->dend = 0;
+    ++bz->n_dev;
+    return true;
+  }
+  if (bz->parse_req) ++bz->n_host;                              // (after a departure: this stretch goes through the host parser)
   b->dec.resize(dtot);
   const size_t nm = b->coff.size();
   if (bz->dev) {                                                // one device call for the stretch; never zlib when the device was asked for
@@ -324,7 +352,10 @@ extern "C" int c3_reader_open_inflate(const char* path, int n_sets, int device, 
   c3_reader* r = nullptr;
   rc = c3_reader_open(path, n_sets, &r);
   if (rc != C3_E_OK) { c3_bgzf_destroy(z); return rc; }
-  if (r->bz) r->bz->dev = z; else c3_bgzf_destroy(z);           // plain gzip / plain text: read as c3_reader_open reads it
+  if (r->bz) {
+    r->bz->dev = z;
+    if (const char* e = getenv("C3_INFLATE_STRETCH_MEMBERS")) { const int v = atoi(e); if (v >= 1 && v <= 4096) r->bz->stretch_members = (size_t)v; }
+  } else c3_bgzf_destroy(z);                                    // plain gzip / plain text: read as c3_reader_open reads it
   *out = r;
   return C3_E_OK;
 }
@@ -415,6 +446,23 @@ extern "C" void c3_reader_close(c3_reader* r) {
 // stored -- the first pass of C3POa.py:200-207 only needs names
 extern "C" void c3_reader_names_only(c3_reader* r, int names_only) { if (r) r->names_only = names_only != 0; }
 
+extern "C" int c3_reader_parse_on_device(c3_reader* r, int on) {
+  if (!r) return C3_E_ARG;
+  if (!r->bz || !r->bz->dev) { r->err = "c3_reader_parse_on_device: not a BGZF file opened by c3_reader_open_inflate"; return C3_E_STATE; }
+  if (r->started) { r->err = "c3_reader_parse_on_device: after the first c3_reader_next"; return C3_E_STATE; }
+  r->bz->parse_req = r->bz->parse_on = r->bz->dev_active = on != 0;
+  return C3_E_OK;
+}
+
+extern "C" int c3_reader_parse_stats(const c3_reader* r, int64_t* stretches_device, int64_t* stretches_host, int64_t* records_device) {
+  if (!r) return C3_E_ARG;
+  const Bgzf* b = r->bz;
+  if (stretches_device) *stretches_device = b ? b->n_dev.load() : 0;
+  if (stretches_host) *stretches_host = b ? b->n_host.load() : 0;
+  if (records_device) *records_device = b ? b->rec_dev.load() : 0;
+  return C3_E_OK;
+}
+
 extern "C" double c3_reader_inflate_wait(const c3_reader* r) { return r && r->bz ? r->bz->wait_s : 0.0; }
 
 extern "C" const char* c3_reader_error(const c3_reader* r) { return r ? r->err.c_str() : "null reader"; }
@@ -432,6 +480,95 @@ extern "C" int64_t c3_reader_reserved_bytes(const c3_reader* r) {
 // 1 when c3_reader_open_range found bytes but no record start in its range (multi-line FASTQ cannot be entered in the middle):
 // the records of that range would be lost, so the caller has to read the file with ONE reader instead
 extern "C" int c3_reader_range_lost(const c3_reader* r) { return r && r->range_lost ? 1 : 0; }
+
+namespace {
+
+// the next stretch becomes the current one (what bgzf_read does between two stretches), and the one after it starts loading.
+// false: nothing more was loaded (end of file, or b->bad)
+bool dev_advance(Bgzf* b) {
+  struct Wait { Bgzf* b; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+                ~Wait() { b->wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } wait{b};
+  bool loaded;
+  if (b->pre_on) { b->pre.join(); b->pre_on = false; loaded = b->pre_ok; if (loaded) b->cur ^= 1; }
+  else { if (b->bad) return false; b->carry_from = b->carry_len = 0; loaded = bgzf_next_stretch(b, &b->st[b->cur]); }
+  if (b->bad || !loaded) return false;
+  BgzfStretch& c = b->st[b->cur];
+  if (c.fq.info.departed) b->parse_on = false;                  // from here on the host parser (the load below already goes its way)
+  b->carry_from = c.fq.info.consumed; b->carry_len = c.fq.text_bytes - c.fq.info.consumed;
+  if (!b->eof) { BgzfStretch* nx = &b->st[b->cur ^ 1]; b->pre_on = true; b->pre = std::thread([b, nx]() { b->pre_ok = bgzf_next_stretch(b, nx); }); }
+  return true;
+}
+
+// the device parser's side of c3_reader_next_set: records of the device stretches enter the group under the group rule of the
+// host loop below (same tests in the same order), their bytes copied from the device straight to the set's fill offsets.
+// Returns with the group full, at the end of the file, or with the rest of the text handed to the host parser (a departure).
+int device_fill(c3_reader* r, BatchSet& s, int max_reads, int64_t max_bases, int min_len, int* pn, size_t* pnn, size_t* pnb, int64_t* pshort) {
+  Bgzf* b = r->bz;
+  int n = *pn; size_t nn = *pnn, nb = *pnb; int64_t n_short = *pshort;
+  int rc = C3_E_OK;
+  while (n < max_reads && (max_bases <= 0 || (int64_t)nb < max_bases)) {
+    BgzfStretch* c = &b->st[b->cur];
+    if (!c->on_dev || c->next_rec == c->fq.info.n_kept) {
+      const bool departed = c->on_dev && c->fq.info.departed;
+      if (!departed && dev_advance(b)) continue;
+      if (b->bad) { b->dev_active = false; break; }             // (the caller reports it)
+      // a departure, or the end of the file with a record the last stretch's end cut: the text from there on goes to the
+      // host parser, through the buffer bgzf_read serves
+      c = &b->st[b->cur];
+      const int64_t from = c->on_dev ? c->fq.info.consumed : 0;
+      int64_t len = c->on_dev ? c->fq.text_bytes - from : 0;
+      c->dec.resize((size_t)len);
+      if (len > 0) {
+        if (c3_bgzf_stretch_text(b->dev, b->cur, from, len, c->dec.data()) != C3_E_OK) { b->why = c3_last_error(nullptr); b->bad = true; len = 0; }
+        else ++b->n_host;
+      }
+      c->on_dev = false; c->dend = (size_t)len; b->dpos = 0;
+      b->parse_on = false; b->dev_active = false;
+      if (len == 0 && !b->pre_on) r->eof = true;                // nothing left at all
+      break;
+    }
+    const int64_t* off = c->fq.off; const int64_t* noff = c->fq.name_off;
+    const int64_t nk = c->fq.info.n_kept;
+    int64_t j = c->next_rec;
+    if (off[j + 1] - off[j] < (int64_t)min_len) { ++n_short; ++r->n_records; ++b->rec_dev; c->next_rec = j + 1; continue; }
+    // a run of records that all enter the group: one copy per array
+    const int64_t j0 = j, sl0 = off[j + 1] - off[j];
+    const size_t nn0 = nn, nb0 = nb; const int n0 = n;
+    while (j < nk && n < max_reads && (max_bases <= 0 || (int64_t)nb < max_bases) && off[j + 1] - off[j] >= (int64_t)min_len) {
+      nn += (size_t)(noff[j + 1] - noff[j]); nb += (size_t)(off[j + 1] - off[j]); ++n; ++j;
+      s.name_off.push_back((int64_t)nn); s.off.push_back((int64_t)nb);
+    }
+    if (!s.names.reserve(nn + 16, nn0)) return C3_E_NOMEM;
+    if (!r->names_only) {
+      size_t want = nb + 16;
+      if (n0 == 0 && !r->hint_bases) {
+        // first kept record of the very first group: one page-locked allocation for max_reads records of this length, never
+        // more than the file can deliver, and the other sets right away (the sizing of the host loop below, for the same reasons)
+        size_t est = (size_t)max_reads * (size_t)(sl0 + sl0 / 4) + 4096;
+        if (max_bases > 0) est = std::min(est, (size_t)max_bases + (size_t)sl0 + 4096);
+        est = std::min(est, (size_t)2 << 30);
+        const size_t deliver = r->file_bytes ? r->file_bytes * 16 + (size_t)sl0 + 4096 : (size_t)-1;
+        want = std::max(want, std::min(est, deliver));
+        size_t left = deliver > want ? deliver - want : 0;
+        for (BatchSet& o : r->sets) if (&o != &s) {
+          if (left == 0) break;
+          const size_t w2 = std::min(want, left + 4096);
+          if (!o.seqs.reserve(w2, 0) || !o.quals.reserve(w2, 0)) return C3_E_NOMEM;
+          left -= std::min(left, w2);
+        }
+      }
+      if (!s.seqs.reserve(want, nb0) || !s.quals.reserve(want, nb0)) return C3_E_NOMEM;
+    }
+    rc = c3_bgzf_stretch_fetch(b->dev, b->cur, j0, j, s.names.p + nn0, r->names_only ? nullptr : s.seqs.p + nb0, r->names_only ? nullptr : s.quals.p + nb0);
+    if (rc != C3_E_OK) { b->why = c3_last_error(nullptr); b->bad = true; b->dev_active = false; break; }
+    r->n_records += j - j0; b->rec_dev += j - j0;
+    c->next_rec = j;
+  }
+  *pn = n; *pnn = nn; *pnb = nb; *pshort = n_short;
+  return C3_E_OK;
+}
+
+}  // namespace
 
 // One group of reads.  Records shorter than min_len are skipped and counted in out->n_short (C3POa.py:202-204,240-241).
 // Stops after max_reads kept reads or once max_bases kept bases are exceeded (0 = no limit).  out->n == 0 at end of file.
@@ -454,6 +591,11 @@ extern "C" int c3_reader_next_set(c3_reader* r, int set, int max_reads, int64_t 
   }
   size_t nn = 0, nb = 0; int n = 0; int64_t n_short = 0;
   const char* p; size_t l;
+  r->started = true;
+  if (r->bz && r->bz->dev_active) {                               // c3_reader_parse_on_device: the device parser fills the group ...
+    const int rc = device_fill(r, s, max_reads, max_bases, min_len, &n, &nn, &nb, &n_short);
+    if (rc != C3_E_OK) return rc;
+  }                                                               // ... and after a departure the loop below goes on with the same group
   while (n < max_reads && (max_bases <= 0 || (int64_t)nb < max_bases)) {
     if (!next_line(r, &p, &l)) break;
     if (l == 0) continue;

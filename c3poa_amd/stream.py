@@ -147,21 +147,23 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
 
     # --inflate gpu: the (single, whole-file) reader of a .gz input inflates its BGZF stretches with k_inflate on worker 0's
     # device instead of zlib threads; any other gzip file has no member sizes to split on and is read as before
-    inflate_dev = None
+    inflate_dev, parse_dev = None, False
     if getattr(args, "inflate", "host") == "gpu" and str(args.reads).endswith(".gz"):
         if _is_bgzf(args.reads):
             inflate_dev = worker_device(0)
+            # --parse gpu: ... and its records are found there too (k_fastq); only the finished arrays come to the host
+            parse_dev = getattr(args, "parse", "host") == "gpu"
         else:
             print("C3POa: --inflate gpu: %s is gzip but not BGZF (no member size in front); only BGZF can be inflated on the GPU, the file is read as before" % args.reads, file=sys.stderr)
     readers = [_lib.Reader(args.reads, n_sets=N_SETS, byte_range=(cuts[k], cuts[k + 1])) if n_ranges > 1
-               else _lib.Reader(args.reads, n_sets=N_SETS, inflate_device=inflate_dev) for k in range(n_ranges)]
+               else _lib.Reader(args.reads, n_sets=N_SETS, inflate_device=inflate_dev, parse_device=parse_dev) for k in range(n_ranges)]
     if n_ranges > 1 and any(r.range_lost() for r in readers):
         # a range with bytes but no 4-line record start (multi-line FASTQ, which mm.fastx_read accepts): such a file cannot be
         # entered in the middle -- its records would be dropped silently -- so ONE reader takes the whole file
         for r in readers:
             r.close()
         n_ranges, cuts = 1, [0, -1]
-        readers = [_lib.Reader(args.reads, n_sets=N_SETS, inflate_device=inflate_dev)]
+        readers = [_lib.Reader(args.reads, n_sets=N_SETS, inflate_device=inflate_dev, parse_device=parse_dev)]
     free_sets = [queue.Queue() for _ in range(n_ranges)]
     for fs in free_sets:
         for j in range(N_SETS):
@@ -410,6 +412,8 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
     for th in rthreads:
         th.join()
     t["inflate_wait"] = sum(r.inflate_wait() for r in readers)         # BGZF input: the parser waiting for inflated bytes
+    if parse_dev:                                                       # --parse gpu: stretches parsed on the device / host, records from the device
+        t["parse_stretches_device"], t["parse_stretches_host"], t["parse_records_device"] = (sum(x) for x in zip(*(r.parse_stats() for r in readers)))
     if keep_pinned:                                 # one-shot process (the CLI): process teardown releases the page-locked buffers
         _KEPT.extend(readers)
     else:

@@ -425,6 +425,43 @@ int c3_write_consensus_fastq_bgzf(c3_bgzf* z, const c3_host_batch* b, const c3_r
                                   const int64_t* cons_off, const char* qv, const int16_t* splint_id, int n_splints,
                                   const char* const* fq_paths, int zero);
 
+/* ---- FASTQ records on the GPU (--parse gpu) ----
+ * A text is STRICT when, from its first byte, it is a sequence of records of exactly four lines: line 0 begins with '@';
+ * line 1 is not empty and does not begin with '@', '>' or '+'; line 2 begins with '+'; line 3 is as long as line 1.  A line
+ * ends at '\n'; one '\r' directly before it is not part of the line (all four lines).  The name is line 0 after the '@', up
+ * to the first blank or tab (what c3_reader_next_set does).  With at_eof != 0 the last line of the last record may lack its
+ * '\n' (a '\r' at its end is dropped all the same).
+ * The call parses the longest prefix of whole strict records: info->consumed is its byte length.  A record that is merely
+ * incomplete at the end of the text (at_eof == 0) is left unconsumed; that is no error.  The first record that is not
+ * strict is a DEPARTURE (a blank line, a FASTA record, multi-line sequence or quality, unequal lengths, a missing '+', an
+ * incomplete record with at_eof set): parsing stops in front of it, consumed ends there, departed = 1, and the records
+ * before it are delivered as usual.  Records with a sequence shorter than min_len are counted in n_short and not stored;
+ * n_records = n_kept + n_short.  names / name_off[n_kept + 1], seqs / quals / off[n_kept + 1] of the kept records mean what
+ * they mean in c3_host_batch.
+ * c3_fastq_parse runs k_fastq on the device of a c3_bgzf; c3_fastq_parse_host is its host statement.  n_kept > max_records,
+ * name_bytes > names_cap or base_bytes > bases_cap return C3_E_LIMIT with the needed sizes in info and nothing written to
+ * the arrays; n > C3_FASTQ_MAX_TEXT returns C3_E_LIMIT (line positions are 32-bit on the device); null arguments and a null
+ * handle return C3_E_ARG before anything is launched (text may be null when n == 0); n == 0 is success with all counts
+ * zero.  Errors through c3_last_error(NULL). */
+#define C3_FASTQ_MAX_TEXT 0x7FF00000
+typedef struct { int64_t n_records, n_kept, n_short, consumed, name_bytes, base_bytes; int32_t departed; } c3_fastq_info;
+int c3_fastq_parse(c3_bgzf* z, const char* text, int64_t n, int at_eof, int min_len,
+                   char* names, int64_t names_cap, int64_t* name_off, char* seqs, char* quals, int64_t bases_cap,
+                   int64_t* off, int64_t max_records, c3_fastq_info* info);
+int c3_fastq_parse_host(const char* text, int64_t n, int at_eof, int min_len,
+                        char* names, int64_t names_cap, int64_t* name_off, char* seqs, char* quals, int64_t bases_cap,
+                        int64_t* off, int64_t max_records, c3_fastq_info* info);
+/* on != 0: a reader opened by c3_reader_open_inflate on a BGZF file keeps every inflated stretch on the device, parses it
+ * there (k_fastq) and copies only the finished names / bases / qualities of each group into its buffer sets; the groups are
+ * the ones the host parser delivers.  From the first departure on the rest of the file is parsed on the host (the existing
+ * parser, so multi-line records, blank lines, FASTA records and every error text are as ever).  C3_E_STATE on any other
+ * reader and after the first c3_reader_next.  Environment: C3_INFLATE_STRETCH_MEMBERS = BGZF members per device stretch
+ * (default 4096; read when the reader is opened). */
+int c3_reader_parse_on_device(c3_reader* r, int on);
+/* stretches parsed on the device / on the host since c3_reader_parse_on_device(r, 1), and records that entered groups (or
+ * were counted short) from the device: proof that the device path ran and nothing fell back silently */
+int c3_reader_parse_stats(const c3_reader* r, int64_t* stretches_device, int64_t* stretches_host, int64_t* records_device);
+
 #ifdef __cplusplus
 }
 #endif
