@@ -234,7 +234,9 @@ class Handle:
 
     def _chk(self, rc):
         if rc < 0:
-            raise C3Error("c3 error %d: %s" % (rc, self.lib.c3_last_error(self.h).decode()))
+            e = C3Error("c3 error %d: %s" % (rc, self.lib.c3_last_error(self.h).decode()))
+            e.code = rc
+            raise e
         return rc
 
     def set_splints(self, splints):

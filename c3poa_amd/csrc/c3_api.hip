@@ -304,8 +304,9 @@ extern "C" int c3_set_splints(c3_handle* h, int n, const char* cat, const int64_
   for (int i = 0; i < n; ++i) {
     int S = (int)(off[i + 1] - off[i]);
     if (S <= 0 || S > C3_SPLINT_MAX) return c3_fail(h, C3_E_LIMIT, "splint length must be 1..512");
-    if ((long long)std::max(h->cfg.conk_match, 0) * S > 32000 || h->cfg.conk_penalty < 0 || h->cfg.conk_penalty > 32000)
-      return c3_fail(h, C3_E_LIMIT, "conk_match * splint length and conk_penalty must stay below 32000 (16-bit score cells in k_conk)");
+    // a cell grows by the larger of the two substitution scores per splint row, whichever of them it is
+    if ((long long)std::max({h->cfg.conk_match, h->cfg.conk_mismatch, 0}) * S > 32000 || h->cfg.conk_penalty < 0 || h->cfg.conk_penalty > 32000)
+      return c3_fail(h, C3_E_LIMIT, "max(conk_match, conk_mismatch) * splint length and conk_penalty must stay within 32000 (16-bit score cells in k_conk)");
     h->sp_len[i] = S; h->max_spl = std::max(h->max_spl, S);
     for (int k = 0; k < S; ++k) {
       int c = code_of(cat[off[i] + k]);
@@ -456,11 +457,13 @@ static int run_conk(c3_handle* h) {
   return 0;
 }
 
-// closed-form Savitzky-Golay coefficients: the same expression as the oracle, evaluated on the host
+// closed-form Savitzky-Golay coefficients: the same expression as the oracle, evaluated on the host.  The filter is symmetric and
+// k_peaks adds mirrored taps first, so only c[0 .. half] is written: PeaksArgs::coef holds 64 doubles, enough for half <= 63
+// (sg_window <= 127); all 2 * half + 1 coefficients would not fit it from window 65 on
 static void savgol_coeffs(int window, double* c) {
   int m = (window - 1) / 2;
   double den = (double)(2 * m - 1) * (double)(2 * m + 1) * (double)(2 * m + 3);
-  for (int k = -m; k <= m; ++k) c[k + m] = 3.0 * (double)(3 * m * m + 3 * m - 1 - 5 * k * k) / den;
+  for (int k = -m; k <= 0; ++k) c[k + m] = 3.0 * (double)(3 * m * m + 3 * m - 1 - 5 * k * k) / den;
 }
 
 static int run_peaks(c3_handle* h) {
@@ -1423,6 +1426,13 @@ extern "C" int c3_call_peaks(c3_handle* h, const int32_t* scores, int n, int min
   if (rc) return rc;
   int np = c3_fetch_raw_peaks(h, 0, peaks, cap);
   if (np < 0) return np;
+  if (np == 0) {
+    // k_peaks keeps at most C3_MAX_PEAKS - 1 peaks: beyond that it drops them all and marks the read, and 0 here would read as
+    // "gated" (a read over the subread limit carries the same status, but its peaks are all there)
+    int32_t status = C3_ST_OK;
+    HIPCHK(hipMemcpy(&status, (const char*)h->d_info.p + offsetof(C3Info, status), sizeof(status), hipMemcpyDeviceToHost));
+    if (status == C3_ST_LIMIT) return c3_fail(h, C3_E_LIMIT, "c3_call_peaks: more than 255 peaks (C3_MAX_PEAKS - 1)");
+  }
   if (smoothed) { int r2 = c3_fetch_smoothed(h, 0, smoothed, n); if (r2 < 0) return r2; }
   return np;
 }

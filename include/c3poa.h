@@ -114,6 +114,8 @@ const char* c3_last_error(const c3_handle* h);
 
 /* splint table (C3POa.py:231-234: splint_dict[name] = [seq, revcomp(seq)]); the library makes the
  * reverse complements itself.  cat = concatenated ASCII, off[n+1]. */
+/* k_conk keeps its score cells in 16 bits: max(conk_match, conk_mismatch, 0) * splint length must not exceed 32000 and
+ * conk_penalty must lie in 0..32000, for every splint; otherwise C3_E_LIMIT with a c3_last_error text. */
 int c3_set_splints(c3_handle* h, int n, const char* cat, const int64_t* off);
 
 /* batch = the `reads` argument of analyze_reads (C3POa.py:110) in SoA form.
@@ -180,7 +182,13 @@ int c3_fetch_msa2(c3_handle* h, int read, char* rowA, char* rowB, int cap);
  * arguments, runs the corresponding kernels and returns the result. */
 /* call_peaks(scores, min_dist, iters, window, order) (bin/call_peaks.py:8-16; iters/window/order are the
  * handle's sg_* settings): returns the number of peaks written to `peaks` (0 = gated / none);
- * smoothed (optional, n doubles) receives the smoothed track. */
+ * smoothed (optional, n doubles) receives the smoothed track.
+ * Capacity: a track keeps at most C3_MAX_PEAKS - 1 = 255 peaks.  With more, the call fails with C3_E_LIMIT and a
+ * c3_last_error text instead of returning a count (in a batch such a read gets C3_ST_LIMIT and n_peaks = 0); the reference
+ * has no such limit.
+ * Too short: a track of fewer than (sg_window - 1) / 2 + 1 points (or of 1 point) is not smoothed: 0 peaks here,
+ * C3_ST_TOO_SHORT in a batch.  The reference has no defined answer there: its padding slices (bin/savitzky_golay.py:33-34)
+ * come up short, and the filtered track it returns has another length than the input (18 points for 20 at window 41). */
 int c3_call_peaks(c3_handle* h, const int32_t* scores, int n, int min_dist, int32_t* peaks, int cap, double* smoothed);
 /* pyabpoa.msa_aligner(match=5).msa(seqs, out_cons, out_msa) (determine_consensus.py:30,34,43):
  * msa receives n rows of *msa_len chars (row-major).  quals may be NULL. */
