@@ -252,6 +252,7 @@ extern "C" int c3_create(const c3_config* cfg, c3_handle** out) {
   if (cfg->conk_match < -127 || cfg->conk_match > 127 || cfg->conk_mismatch < -127 || cfg->conk_mismatch > 127) {
     g_create_err = "conk_match / conk_mismatch must fit a signed byte"; return C3_E_ARG;                 // k_conk keeps them in byte tables
   }
+  if (cfg->dang_band > 255) { g_create_err = "dang_band must be at most 255 (k_prep holds 512 band offsets per wave)"; return C3_E_LIMIT; }
   if (cfg->sg_order != 2 && cfg->sg_order != 3) { g_create_err = "sg_order must be 2 or 3"; return C3_E_ARG; }
   if (cfg->sg_window < 5 || cfg->sg_window > 127 || !(cfg->sg_window & 1)) { g_create_err = "sg_window must be odd, 5..127"; return C3_E_ARG; }
   if (cfg->zero_max_cells < 1 || cfg->zero_max_cells > INT32_MAX) { g_create_err = "zero_max_cells must be 1..2147483647"; return C3_E_ARG; }
@@ -732,7 +733,9 @@ static int run_polish(c3_handle* h, float* ms_prep, float* ms_win, float* ms_st)
     wcap += (2 * h->sum[i].max_sub + WL - 1) / WL + 1;
   }
   const int NLcap = max_ns + 2, NWcap = (2 * max_q + WL - 1) / WL + 1;
-  const int64_t ecap = (int64_t)(max_dang + 2) * 512;          // direction bytes: 512 per piece row
+  // direction tags of one piece: one dword per lane and three rows, or two rows for a band that needs the wide rows (k_polish.hip:
+  // ext_dir_bytes; 5 or 8 band offsets per lane; c3_create refuses a band beyond 64 * 8 offsets)
+  const int64_t ecap = (int64_t)(max_dang / (2 * h->cfg.dang_band + 1 > 320 ? 2 : 3) + 2) * 256;
   const size_t per_slot_prep = (size_t)ecap + (size_t)NLcap * NWcap * 8;
   const int slots_p = auto_slots(h, h->cfg.slots_poa, per_slot_prep, nw, getenv("C3_DEBUG_PREP_WPC") ? atoi(getenv("C3_DEBUG_PREP_WPC")) : 20);
   HIPCHK(h->s_eD.ensure((size_t)ecap * slots_p));
@@ -747,6 +750,10 @@ static int run_polish(c3_handle* h, float* ms_prep, float* ms_win, float* ms_st)
   p.lw_first = h->s_lw.as<int>(); p.lw_last = p.lw_first + (size_t)NLcap * NWcap * slots_p; p.NLcap = NLcap; p.NWcap = NWcap;
   p.wrec = h->d_wrec.as<WinRec>(); p.wlay = h->d_wlay.as<WLayer>(); p.win_base = h->d_wbase.as<int>();
   p.wcap = (int)std::min<long long>(wcap, 0x7fffffff);
+  const int bonus4 = 4 * (h->cfg.pol_match - h->cfg.pol_mismatch);
+  p.sub_shift = -1;
+  for (int b = 2; b <= 12; ++b) if (bonus4 == 1 << b) p.sub_shift = b;
+  if (const char* e = getenv("C3_DEBUG_PREP_ROWS")) p.rows_old = !strcmp(e, "old");      // test hook (tests/test_gpu_prep_rows.py)
   HIPCHK(zero_counters(h));
   HIPCHK(hipEventRecord(h->ev[5], h->stream));
   DBG("prep: slots=%d ecap=%lld NL=%d NW=%d wcap=%lld\n", slots_p, (long long)ecap, NLcap, NWcap, (long long)wcap);

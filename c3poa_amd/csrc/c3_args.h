@@ -72,6 +72,8 @@ struct PrepArgs {
   C3Batch b; C3Info* info; C3Params p; C3Counters* cnt; const int* work; int n_work;
   const uint8_t* draft; int32_t* tpos; int wcap; uint8_t* eD; int64_t ecap; int* lw_first; int* lw_last; int NLcap, NWcap;
   WinRec* wrec; WLayer* wlay; int* win_base;
+  int sub_shift;                          // log2(4 * (pol_match - pol_mismatch)) when that is a power of two (the rows' one-and match flags), else -1
+  int rows_old;                           // test hook C3_DEBUG_PREP_ROWS=old: every extension row takes the masked body
 };
 struct WinArgs {
   C3Batch b; C3Params p; C3Counters* cnt; int n_win; const WinRec* wrec_in; WinRec* wrec; const WLayer* wlay; int NLcap;

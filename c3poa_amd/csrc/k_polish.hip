@@ -17,6 +17,7 @@
 #include "c3_dev.h"
 #include "c3_args.h"
 #include <algorithm>
+#include <type_traits>
 
 #define WSYNC() __syncthreads()
 // adjacency slot k of node v.  Slot-major (all first edges, then all second edges, ...): nearly every node has one or two
@@ -35,16 +36,22 @@
 // Lane owns EC consecutive band offsets (bb = lane*EC + cc; cell (i, j = i - W + bb)); the previous
 // row lives in registers (diagonal = same offset, up = offset+1), the left gap is an in-lane prefix
 // plus one DPP max-scan, cells are KEY = score*4 + tag (3 diag, 2 up, 1 left) so one v_max per
-// candidate keeps the oracle's tie order.  Only the direction bytes go to memory (8 per lane per row);
-// the draft sits in LDS and the piece bases arrive 64 rows at a time, so the row loop has no loads.
+// candidate keeps the oracle's tie order.  Only the direction tags go to memory, packed: a lane's five
+// cells of a row are 10 bits, three rows share a dword -- D32[(i / 3) * 64 + lane], row i % 3 at bit
+// 10 * (i % 3), cell cc at 2 * cc (tag 0: invalid cell) -- so a row costs a third of a store.  The
+// draft sits in LDS and the piece bases arrive 64 rows at a time, so the row loop has no loads.
 #ifndef C3_PREP_WAVES
 #define C3_PREP_WAVES 5
 #endif
 #define EC 5
 #define EXT_DCAP 4096        // draft bases kept in LDS; longer drafts read the global copy
+#define EXT_STATIC (-(1 << 27))   // horizontal addend of the offsets beyond the band in the mask-free rows (see there)
+#define EXT_ECW 8            // band offsets per lane of the wide rows (bands of more than 64 * EC offsets: dang_band 160 .. 255)
+// direction words of rows 0..n of one piece: a lane's tags of a row are 2 * ec bits, rpw = 32 / (2 * ec) rows share a dword
+__device__ inline long long ext_dir_bytes(long long n, int rpw) { return (n / rpw + 1) * 256; }
 // DL: the draft fits the LDS copy.  A template parameter, not a run-time flag: `dl ? ldraft[i] : draft[i]` makes the
 // compiler select between an LDS and a global pointer and emit flat loads, whose vmcnt wait drains every outstanding
-// direction-byte store -- once per row.
+// direction store.
 template <bool DL>
 __device__ long long extend_align(const PrepArgs& a, const uint32_t* pk, const uint8_t* draft, const uint8_t* ldraft, int C,
                                   int pb, int n, int dir_, int32_t* tpos, uint8_t* D, int lane) {
@@ -53,7 +60,11 @@ __device__ long long extend_align(const PrepArgs& a, const uint32_t* pk, const u
   const int db = dir_ > 0 ? 0 : C - 1;
   const int NEGK = -(1 << 28);
   for (int k = lane; k < n; k += 64) tpos[pb + dir_ * k] = -1;
-  if (bw > 64 * EC || (long long)(n + 1) * 512 > a.ecap) return -1;
+  // cells per lane: EC, or EXT_ECW in the WIDE rows of a band that 64 * EC offsets do not hold (the general row below with more
+  // cells per lane; 16 tag bits per lane and row, two rows per dword).  A band beyond 64 * EXT_ECW is refused by the host.
+  const int ect = bw > 64 * EC ? EXT_ECW : EC, rpw = 16 / ect;
+  if (bw > 64 * EXT_ECW || ext_dir_bytes(n, rpw) > a.ecap) return -1;
+  unsigned* D32 = (unsigned*)D;
   int hprev[EC];
 #pragma unroll
   for (int cc = 0; cc < EC; ++cc) {           // row 0: H[0][j] = j*g for 0 <= j <= min(C, W)
@@ -62,73 +73,180 @@ __device__ long long extend_align(const PrepArgs& a, const uint32_t* pk, const u
   }
   int best = 0, bi = 0, bj = 0;
   long long cells = lane == 0 ? min(C, W) + 1 : 0;          // row 0
-#ifndef C3_EXT_OLD
-  if (DL) {
-    // BRANCH-FREE ROWS (the draft is in LDS).  An invalid cell -- left of column 0, right of column C, beyond the band -- always
-    // holds NEGK, so every candidate that comes from one loses by itself: no masks on the diagonal / up / left candidates, ONE
-    // select per cell (valid ? key : NEGK) before the key is split into score and tag.  The draft codes of the lane's five
-    // columns travel in one register (a nibble each, shifted by one column per row; the new nibble is the row's only LDS read),
-    // the first maximum is tracked per band offset (compare, max, select), the cell count is closed-form per row on the scalar
-    // unit.  (The masked version compiled into two EXEC-mask branches per cell: ~450 instructions per row; this is ~140.)
-    const int bb0 = lane * EC;
-    int g4bb1[EC], bestc[EC], bic[EC];
+  // direction tags of up to three rows, newest on top: v_alignbit shifts a cell's two tag bits in from the left (one
+  // instruction per cell), so after row i the rows of its group sit at bit 32 - 10 * (rows seen) upwards.  Row 0 has no tags.
+  unsigned acc = 0;
+  // GENERAL ROWS (the oracle's row, cell by cell): drafts beyond the LDS copy, and every piece of a wide band.  E band offsets
+  // per lane; B = 2 * E tag bits per lane and row enter `acc` from the top, so row i % RPW ends at bit B * (i % RPW) of its word.
+  auto general_rows = [&](auto e_) {
+    constexpr int E = decltype(e_)::value, B = 2 * E, RPW = 32 / B;
+    int hp[E];
 #pragma unroll
-    for (int cc = 0; cc < EC; ++cc) { g4bb1[cc] = g4 * (bb0 + cc) + 1; bestc[cc] = 0; bic[cc] = 0; }
-    auto code_at = [&](int q) { return (unsigned)ldraft[db + dir_ * min(max(q, 0), C - 1)]; };
-    unsigned dcp = 0;                                                      // nibble cc = draft code of column j - 1 = i - W + bb - 1
-#pragma unroll
-    for (int cc = 0; cc < EC; ++cc) dcp |= code_at(1 - W + bb0 + cc - 1) << (4 * cc);
-    long long cells_s = 0;
+    for (int cc = 0; cc < E; ++cc) {
+      const int bb = lane * E + cc, j = bb - W;
+      hp[cc] = (bb < bw && j >= 0 && j <= C) ? j * g4 : NEGK;
+    }
     for (int ib = 1; ib <= n; ib += 64) {
-      int pcs = 0;
+      int pcs = 0;                              // piece base of row ib+lane
       if (ib + lane <= n) pcs = c3_code_at(pk, pb + dir_ * (ib + lane - 1));
       asm volatile("" : "+v"(pcs));
       const int cnt = min(64, n - ib + 1);
       for (int li = 0; li < cnt; ++li) {
         const int i = ib + li;
         const int pc = __builtin_amdgcn_readlane(pcs, li);
-        const unsigned nxt_code = code_at(i - W + bb0 + EC - 1);          // nibble EC-1 of row i + 1 (consumed at the end of the row)
-        const int vlo = W - i;                                             // valid offsets: max(0, vlo) .. vhi
-        const int vhi = min(bw - 1, C - i + W);
-        const unsigned span = (unsigned)(vhi - vlo);                      // (vhi >= vlo whenever a valid cell exists; else every compare below fails)
-        cells_s += max(0, vhi - max(0, vlo) + 1);
-        const int nxt0 = __builtin_amdgcn_update_dpp(NEGK, hprev[0], 0x130, 0xf, 0xf, false);   // wave_shl:1
-        int key[EC], y[EC];
+        const int jlo = max(0, i - W);
+        // up neighbour of the last owned offset = first offset of the next lane
+        const int nxt0 = __builtin_amdgcn_update_dpp(NEGK, hp[0], 0x130, 0xf, 0xf, false);   // wave_shl:1
+        int key[E], y[E];
         int run = NEGK;
 #pragma unroll
-        for (int cc = 0; cc < EC; ++cc) {
-          const int dcode = (int)((dcp >> (4 * cc)) & 15u);
-          const int kd = hprev[cc] + ((pc == dcode) ? mt4 + 3 : mm4 + 3);
-          const int up = (cc + 1 < EC) ? hprev[cc + 1 < EC ? cc + 1 : cc] : nxt0;
-          const int k = max(kd, up + (g4 + 2));
-          const bool val = (unsigned)(bb0 + cc - vlo) <= span && vhi >= vlo && bb0 + cc >= 0;
+        for (int cc = 0; cc < E; ++cc) {
+          const int bb = lane * E + cc, j = i - W + bb;
+          const bool val = bb < bw && j >= 0 && j <= C;
+          int k = INT32_MIN;
+          if (val) {
+            if (j > 0) {
+              const int dcode = DL ? (int)ldraft[db + dir_ * (j - 1)] : (int)draft[db + dir_ * (j - 1)];
+              k = hp[cc] + ((pc == dcode) ? mt4 : mm4) + 3;
+            }
+            const int up = (cc + 1 < E) ? hp[cc + 1 < E ? cc + 1 : cc] : nxt0;
+            if (bb + 1 < bw) k = max(k, up + g4 + 2);
+          }
           key[cc] = val ? k : NEGK;
-          y[cc] = (key[cc] & ~3) - (g4bb1[cc] - 1);
+          y[cc] = val ? (k & ~3) - g4 * bb : NEGK;
           run = max(run, y[cc]);
         }
         const int s = wave_scan_max(run);
         int ex = wave_shr1(s, NEGK);
-        unsigned d0 = 0, d1 = 0;
+        unsigned w = 0;
 #pragma unroll
-        for (int cc = 0; cc < EC; ++cc) {
-          // (no test for the row's first column: everything to its left is NEGK, so the left candidate loses by itself;
-          // an invalid cell is re-masked because ex can be a real score)
-          int k2 = max(key[cc], ex + g4bb1[cc]);
+        for (int cc = 0; cc < E; ++cc) {
+          const int bb = lane * E + cc, j = i - W + bb;
+          const bool val = bb < bw && j >= 0 && j <= C;
+          int k2 = key[cc];
+          if (val && j > jlo) k2 = max(k2, ex + g4 * bb + 1);
           ex = max(ex, y[cc]);
-          k2 = key[cc] == NEGK ? NEGK : k2;
           const int hh = k2 & ~3;
-          hprev[cc] = hh;
-          const unsigned tag = (unsigned)k2 & 3u;                           // 3 diag, 2 up, 1 left, 0 invalid
-          if (cc < 4) d0 |= tag << (8 * cc); else d1 |= tag;
-          const bool up_ = hh > bestc[cc];                                 // (column 0 and invalid cells are <= 0: never)
-          bestc[cc] = max(bestc[cc], hh);
-          bic[cc] = up_ ? i : bic[cc];
+          hp[cc] = val ? hh : NEGK;
+          const unsigned tag = val ? (unsigned)(k2 & 3) : 0u;            // 3 diag, 2 up, 1 left
+          w |= tag << (2 * cc);
+          if (val) { ++cells; if (j > 0 && hh > best) { best = hh; bi = i; bj = j; } }
         }
-        unsigned* drow = (unsigned*)(D + (size_t)i * 512) + lane * 2;
-        drow[0] = 0x03030303u - d0; drow[1] = 3u - d1;                     // bytes: 0 diag, 1 up, 2 left, 3 none
-        dcp = (dcp >> 4) | (nxt_code << (4 * (EC - 1)));
+        acc = (acc >> B) | (w << (32 - B));
+        if (i % RPW == RPW - 1) D32[(i / RPW) * 64 + lane] = acc >> (32 - B * RPW);
       }
     }
+  };
+  if (ect != EC) general_rows(std::integral_constant<int, EXT_ECW>());
+  else
+#ifndef C3_EXT_OLD
+  if (DL) {
+    // BRANCH-FREE ROWS (the draft is in LDS).  The draft codes of the lane's five columns travel in one register (a one-hot
+    // nibble each, N = 0, shifted by one column per row; the new nibble is the row's only LDS read), the first maximum is
+    // tracked per band offset (compare, max, select), the cell count is closed-form per row on the scalar unit.
+    //
+    // MASKED rows (today's form; every row under C3_DEBUG_PREP_ROWS=old): an invalid cell -- left of column 0, right of
+    // column C, beyond the band -- always holds NEGK, so every candidate that comes from one loses by itself: no masks on
+    // the diagonal / up / left candidates, ONE select per cell (valid ? key : NEGK) and a second one after the horizontal
+    // candidate, because the carry `ex` can be a real score.
+    //
+    // MASK-FREE rows: rows 1 <= i <= C - W have no cell right of column C (j <= i + W <= C), so the only invalid cells are
+    //   (a) left of column 0 (bb < W - i, rows i < W).  Their diagonal, up and left neighbours are invalid cells of kind (a)
+    //       too, so they start at NEGK in row 0 and gain at most mt4 (diagonal) per row: <= NEGK + 12 * W with the default
+    //       scoring.  A valid cell always has a valid candidate (column 0 takes `up` from column 0 of the row above, every
+    //       other column a valid diagonal), and valid keys are some 2^28 above: an (a) cell never wins or ties a
+    //       candidate, never exceeds `best` (0 at the start, strict compare), and the traceback -- which only follows
+    //       winning candidates and tests j >= 1 before it believes a diagonal run -- never reads its tag.
+    //   (b) static cells bb >= bw, right of every valid cell.  They must not take the carry, which is a real score there:
+    //       their addend g4bb1 is EXT_STATIC instead of g4 * bb, so the left candidate is -2^27 + (a real y).  From then on
+    //       a static cell holds -2^27 + X, X growing by at most one key step per row; its y is X, which flows only to the
+    //       right, into other static cells.  A piece takes these rows only if (largest key step) * (n + bw) < 2^24: every
+    //       valid key and every y is then inside +-2^24 and X < 2^25, so a static cell stays 2^26 below every valid key, no
+    //       sum leaves int32 (the lowest is NEGK + EXT_STATIC - 2^24), and the only valid cell that sees one -- `up` of
+    //       offset bw - 1 -- has a valid diagonal that wins.
+    //   A masked row that follows resets every invalid cell to NEGK (its selects do not look at the old value).
+    // Substitution: when mt4 - mm4 is a power of two (a.sub_shift; 32 with the default scoring) the match flags of the five
+    // columns come from ONE and + shift per row (one-hot piece base replicated over the nibbles), and a cell's bonus is a
+    // shift + and of that word; other scorings compare the nibble with the one-hot piece base.  Chosen per piece.
+    const int bb0 = lane * EC;
+    int g4bb1[EC], bestc[EC], bic[EC];
+#pragma unroll
+    for (int cc = 0; cc < EC; ++cc) { g4bb1[cc] = bb0 + cc < bw ? g4 * (bb0 + cc) + 1 : EXT_STATIC + 1; bestc[cc] = 0; bic[cc] = 0; }
+    auto code_at = [&](int q) { return (1u << ldraft[db + dir_ * min(max(q, 0), C - 1)]) & 15u; };
+    unsigned dcp = 0;                                                      // nibble cc = one-hot draft code of column j - 1 = i - W + bb - 1
+#pragma unroll
+    for (int cc = 0; cc < EC; ++cc) dcp |= code_at(1 - W + bb0 + cc - 1) << (4 * cc);
+    long long cells_s = 0;
+#ifdef C3_EXP_PREP_NOFLAGS
+    const int sh = -1;                                                     // marginal-cost build: every scoring takes the nibble compare
+#else
+    const int sh = a.sub_shift;
+#endif
+    const int c1 = mm4 + 3, bon = mt4 - mm4;
+    unsigned* dgrp = D32;                                                  // words of the current group of three rows (uniform: a scalar base)
+    int ph = 1;                                                            // i % 3
+    auto rows = [&](auto masked_, auto pow2_, int i0, int i1) {
+      constexpr bool MASKED = decltype(masked_)::value, POW2 = decltype(pow2_)::value;
+      for (int ib = i0; ib <= i1; ib += 64) {
+        int pcs = 0;
+        if (ib + lane <= i1) pcs = c3_code_at(pk, pb + dir_ * (ib + lane - 1));
+        asm volatile("" : "+v"(pcs));
+        const int cnt = min(64, i1 - ib + 1);
+        for (int li = 0; li < cnt; ++li) {
+          const int i = ib + li;
+          const int pc = __builtin_amdgcn_readlane(pcs, li);
+          const unsigned pcoh = 1u << pc;
+          const unsigned nxt_code = code_at(i - W + bb0 + EC - 1);        // nibble EC-1 of row i + 1 (consumed at the end of the row)
+          const int vlo = W - i;                                           // valid offsets: max(0, vlo) .. vhi
+          const int vhi = min(bw - 1, C - i + W);
+          const unsigned span = (unsigned)(vhi - vlo);                    // (vhi >= vlo whenever a valid cell exists; else every compare below fails)
+          cells_s += max(0, vhi - max(0, vlo) + 1);
+          const int nxt0 = __builtin_amdgcn_update_dpp(NEGK, hprev[0], 0x130, 0xf, 0xf, false);   // wave_shl:1
+          unsigned m2 = 0;                                                 // nibble cc: bonus bit `bon` if column cc matches
+          if (POW2) m2 = ((dcp & (pcoh * 0x11111u)) >> pc) << sh;
+          int key[EC], y[EC];
+          int run = NEGK;
+#pragma unroll
+          for (int cc = 0; cc < EC; ++cc) {
+            int kd;
+            if (POW2) kd = hprev[cc] + (int)((m2 >> (4 * cc)) & (unsigned)bon) + c1;
+            else kd = hprev[cc] + ((((dcp >> (4 * cc)) & 15u) == pcoh) ? mt4 + 3 : c1);
+            const int up = (cc + 1 < EC) ? hprev[cc + 1 < EC ? cc + 1 : cc] : nxt0;
+            const int k = max(kd, up + (g4 + 2));
+            if (MASKED) {
+              const bool val = (unsigned)(bb0 + cc - vlo) <= span && vhi >= vlo && bb0 + cc >= 0;
+              key[cc] = val ? k : NEGK;
+            } else key[cc] = k;
+            y[cc] = ((key[cc] & ~3) | 1) - g4bb1[cc];                        // = score * 4 - g4 * bb (one v_and_or + one sub)
+            run = max(run, y[cc]);
+          }
+          const int s = wave_scan_max(run);
+          int ex = wave_shr1(s, NEGK);
+#pragma unroll
+          for (int cc = 0; cc < EC; ++cc) {
+            // (no test for the row's first column: everything to its left is at NEGK, so the left candidate loses by itself)
+            int k2 = max(key[cc], ex + g4bb1[cc]);
+            ex = max(ex, y[cc]);
+            if (MASKED) k2 = key[cc] == NEGK ? NEGK : k2;
+            const int hh = k2 & ~3;
+            hprev[cc] = hh;
+            acc = __builtin_amdgcn_alignbit((unsigned)k2, acc, 2);          // tag: 3 diag, 2 up, 1 left, 0 invalid
+            const bool up_ = hh > bestc[cc];                                 // (column 0 and invalid cells are <= 0: never)
+            bestc[cc] = max(bestc[cc], hh);
+            bic[cc] = up_ ? i : bic[cc];
+          }
+          if (ph == 2) { dgrp[lane] = acc >> 2; dgrp += 64; ph = 0; } else ++ph;
+          dcp = (dcp >> 4) | (nxt_code << (4 * (EC - 1)));
+        }
+      }
+    };
+    const long long kstep = max(max(abs(mt4), abs(mm4)), abs(g4)) + 3;
+    const int nfree = (a.rows_old || kstep * (n + bw) >= (1 << 24)) ? 0 : min(n, C - W);       // rows 1 .. nfree: mask-free
+    if (nfree >= 1) {
+      if (sh >= 0) rows(std::false_type(), std::true_type(), 1, nfree);
+      else rows(std::false_type(), std::false_type(), 1, nfree);
+    }
+    if (nfree < n) rows(std::true_type(), std::false_type(), max(nfree, 0) + 1, n);
     // the lane's first maximum in row-major order: smallest row, then smallest offset
 #pragma unroll
     for (int cc = 0; cc < EC; ++cc) {
@@ -138,56 +256,9 @@ __device__ long long extend_align(const PrepArgs& a, const uint32_t* pk, const u
     cells += lane == 0 ? cells_s : 0;
   } else
 #endif
-  for (int ib = 1; ib <= n; ib += 64) {
-    int pcs = 0;                              // piece base of row ib+lane
-    if (ib + lane <= n) pcs = c3_code_at(pk, pb + dir_ * (ib + lane - 1));
-    asm volatile("" : "+v"(pcs));
-    const int cnt = min(64, n - ib + 1);
-    for (int li = 0; li < cnt; ++li) {
-      const int i = ib + li;
-      const int pc = __builtin_amdgcn_readlane(pcs, li);
-      const int jlo = max(0, i - W);
-      // up neighbour of the last owned offset = first offset of the next lane
-      const int nxt0 = __builtin_amdgcn_update_dpp(NEGK, hprev[0], 0x130, 0xf, 0xf, false);   // wave_shl:1
-      int key[EC], y[EC];
-      int run = NEGK;
-#pragma unroll
-      for (int cc = 0; cc < EC; ++cc) {
-        const int bb = lane * EC + cc, j = i - W + bb;
-        const bool val = bb < bw && j >= 0 && j <= C;
-        int k = INT32_MIN;
-        if (val) {
-          if (j > 0) {
-            const int dcode = DL ? (int)ldraft[db + dir_ * (j - 1)] : (int)draft[db + dir_ * (j - 1)];
-            k = hprev[cc] + ((pc == dcode) ? mt4 : mm4) + 3;
-          }
-          const int up = (cc + 1 < EC) ? hprev[cc + 1 < EC ? cc + 1 : cc] : nxt0;
-          if (bb + 1 < bw) k = max(k, up + g4 + 2);
-        }
-        key[cc] = val ? k : NEGK;
-        y[cc] = val ? (k & ~3) - g4 * bb : NEGK;
-        run = max(run, y[cc]);
-      }
-      const int s = wave_scan_max(run);
-      int ex = wave_shr1(s, NEGK);
-      unsigned d0 = 0, d1 = 0;
-#pragma unroll
-      for (int cc = 0; cc < EC; ++cc) {
-        const int bb = lane * EC + cc, j = i - W + bb;
-        const bool val = bb < bw && j >= 0 && j <= C;
-        int k2 = key[cc];
-        if (val && j > jlo) k2 = max(k2, ex + g4 * bb + 1);
-        ex = max(ex, y[cc]);
-        const int hh = k2 & ~3;
-        hprev[cc] = val ? hh : NEGK;
-        const unsigned dir = val ? (unsigned)(3 - (k2 & 3)) : 3u;      // 0 diag, 1 up, 2 left
-        if (cc < 4) d0 |= dir << (8 * cc); else d1 |= dir;
-        if (val) { ++cells; if (j > 0 && hh > best) { best = hh; bi = i; bj = j; } }
-      }
-      unsigned* drow = (unsigned*)(D + (size_t)i * 512) + lane * 2;
-      drow[0] = d0; drow[1] = d1;
-    }
-  }
+  general_rows(std::integral_constant<int, EC>());
+  // the partial last group: its rows sit on top of acc
+  if (n % rpw != rpw - 1) D32[(n / rpw) * 64 + lane] = acc >> (32 - 2 * ect * (n % rpw + 1));
   WSYNC();
   // first maximum in row-major order
   const int gb = wave_max(best);
@@ -200,15 +271,18 @@ __device__ long long extend_align(const PrepArgs& a, const uint32_t* pk, const u
       if (i == 0) break;                                   // row 0: only left moves, nothing to record
       const int bb = j - i + W;
       const int ik = i - lane;
-      int d = 3;
-      if (ik >= 1) d = D[(size_t)ik * 512 + (bb / EC) * 8 + bb % EC];
-      const unsigned long long bal = __ballot(ik >= 1 && d == 0 && j - lane >= 1);
+      unsigned d = 0;
+      if (ik >= 1) {
+        if (ect == EC) d = (D32[(ik / 3) * 64 + bb / EC] >> (10 * (ik % 3) + 2 * (bb % EC))) & 3u;
+        else d = (D32[(ik / 2) * 64 + bb / EXT_ECW] >> (16 * (ik % 2) + 2 * (bb % EXT_ECW))) & 3u;
+      }
+      const unsigned long long bal = __ballot(ik >= 1 && d == 3 && j - lane >= 1);
       const int m = (~bal) ? __builtin_ctzll(~bal) : 64;
       if (lane < m) tpos[pb + dir_ * (ik - 1)] = db + dir_ * (j - lane - 1);
       i -= m; j -= m;
       if (m < 64 && i > 0) {
-        const int dbk = wave_bcast(d, m);
-        if (dbk == 1) --i; else if (dbk == 2) --j; else break;       // 0 here would mean j == 0: cannot happen
+        const int dbk = wave_bcast((int)d, m);
+        if (dbk == 2) --i; else if (dbk == 1) --j; else break;       // 3 here would mean j == 0: cannot happen
       }
     }
   }
