@@ -3,7 +3,7 @@
 
 Same flags, inputs and output files as rvolden/C3POa v2.2.3 (/root/reference/C3POa_postprocessing.py:17-62, 400-434):
     python3 C3POa_postprocessing.py -i R2C2_Consensus.fasta -a adapters.fasta -o out [-x indexes.fasta] [-u] [-t] [-b]
-                                    [-n N] [-g 1000] [-bt] [-co] [-c config]
+                                    [-n N] [-g 1000] [-bt] [-co] [-c config] [--emit gpu [--keep-quals]]
 The adapter-to-read alignment that upstream delegates to blat runs on the GPU (c3_scan_adapters); the PSL file
 <out>/adapter_to_consensus_alignment.psl is written and reused exactly as upstream reuses it.
 """
@@ -36,11 +36,19 @@ def parse_args(argv=None):
     p.add_argument("--blatThreads", "-bt", action="store_true", default=False, help="Accepted for compatibility.")
     p.add_argument("--compress_output", "-co", action="store_true", default=False, help="gzip the output files (with -n > 1, as upstream).")
     p.add_argument("--adapter-finder", dest="adapter_finder", choices=["gpu"], default="gpu", help="How adapters are located (GPU local alignment).")
+    p.add_argument("--emit", choices=["host", "gpu"], default="host",
+                   help="gpu: classify, trim, orient, demultiplex and format the records on the GPU (k_post); host (default): as before.")
+    p.add_argument("--keep-quals", dest="keep_quals", action="store_true", default=False,
+                   help="Carry the qualities of a FASTQ input through: the three read files become .fastq (needs --emit gpu).")
+    p.add_argument("--post-batch", dest="post_batch", type=int, default=200000, help=argparse.SUPPRESS)
     p.add_argument("--version", "-v", action="version", version=VERSION, help="Prints the C3POa version.")
     if argv is None and len(sys.argv) == 1:
         p.print_help()
         sys.exit(0)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.keep_quals and args.emit != "gpu":
+        p.error("--keep-quals needs --emit gpu")
+    return args
 
 
 def main(args):

@@ -30,7 +30,8 @@ EXPORTS = ["c3_default_config", "c3_version", "c3_device_count", "c3_warm_device
            "c3_bgzf_create", "c3_bgzf_destroy", "c3_bgzf_bound", "c3_bgzf_compress", "c3_bgzf_compress_host",
            "c3_write_group_bgzf", "c3_write_consensus_fastq_bgzf",
            "c3_bgzf_scan", "c3_bgzf_decompress", "c3_bgzf_decompress_host", "c3_reader_open_inflate", "c3_reader_inflate_wait",
-           "c3_fastq_parse", "c3_fastq_parse_host", "c3_reader_parse_on_device", "c3_reader_parse_stats"]
+           "c3_fastq_parse", "c3_fastq_parse_host", "c3_reader_parse_on_device", "c3_reader_parse_stats",
+           "c3_post_emit", "c3_post_emit_host", "c3_post_emit_timing"]
 
 
 ZERO_MAX_CELLS = 16777216       # c3_default_config's zero_max_cells: largest front * tail the zero-repeat rescue takes
@@ -77,6 +78,20 @@ class FastqInfo(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _t in self._fields_}
+
+
+class PostArgs(C.Structure):
+    """c3_post_args of include/c3poa.h"""
+    _fields_ = [("n", C.c_int32), ("names", C.c_void_p), ("name_off", C.c_void_p), ("seqs", C.c_void_p), ("quals", C.c_void_p),
+                ("off", C.c_void_p), ("table", C.c_void_p), ("n_ad", C.c_int32), ("ad_len", C.c_void_p), ("ad_class", C.c_void_p),
+                ("class5", C.c_int32), ("ad_names", C.c_void_p), ("ad_name_off", C.c_void_p), ("has_index", C.c_int32),
+                ("n_idx", C.c_int32), ("idx_cat", C.c_void_p), ("idx_off", C.c_void_p), ("idx_dest", C.c_void_p),
+                ("n_dest", C.c_int32), ("undirectional", C.c_int32), ("trim", C.c_int32), ("barcoded", C.c_int32)]
+
+
+class PostTiming(C.Structure):
+    _fields_ = [(k, C.c_float) for k in ("ms_classify", "ms_scan", "ms_emit", "ms_call")] + \
+               [(k, C.c_int64) for k in ("n_reads", "n_kept", "in_bytes", "out_bytes")]
 
 
 class HostBatchStruct(C.Structure):
@@ -182,6 +197,9 @@ def load():
     lib.c3_fastq_parse_host.argtypes = fq
     lib.c3_reader_parse_on_device.argtypes = [vp, C.c_int]
     lib.c3_reader_parse_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.c3_post_emit.argtypes = [vp, C.POINTER(PostArgs), vp, C.c_int64, vp, vp]
+    lib.c3_post_emit_host.argtypes = [C.POINTER(PostArgs), vp, C.c_int64, vp, vp]
+    lib.c3_post_emit_timing.argtypes = [vp, C.POINTER(PostTiming)]
     _lib = lib
     return lib
 
@@ -476,6 +494,17 @@ class Handle:
         self._chk(self.lib.c3_match_index_batch(self.h, n, buf.ctypes.data, lens.ctypes.data, len(bs), b"".join(bs), off.ctypes.data, out.ctypes.data))
         return out
 
+    def post_emit(self, plan, batch, table):
+        """c3_post_emit (k_post): the finished file bytes of one batch.  plan: a PostPlan; batch: a PostBatch; table: what
+        scan_adapters returned for the batch.  Returns (arena uint8 array, stream_off[S + 1], kept reads)."""
+        return _post_call(lambda *a: self.lib.c3_post_emit(self.h, *a), lambda: self.lib.c3_last_error(self.h), plan, batch, table)
+
+    def post_emit_timing(self):
+        """c3_post_emit_timing: event times of the three passes of the last post_emit and the call with its copies"""
+        t = PostTiming()
+        self._chk(self.lib.c3_post_emit_timing(self.h, C.byref(t)))
+        return {f[0]: getattr(t, f[0]) for f in PostTiming._fields_}
+
     def demux_indexes(self, heads, set_a, set_b, return_dist=False):
         """c3_demux_indexes (k_demux): winners (n, 2) int32 of index sets A and B (index number or -1) for every head
         (300 bytes each, see _demux_args), and with return_dist the (n, len(A) + len(B)) uint8 minimum distances"""
@@ -531,6 +560,101 @@ def match_index(seq, index_seqs):
     np.cumsum([len(b) for b in bs], out=off[1:])
     sq = _b(seq)
     return int(load().c3_match_index(sq, len(sq), len(bs), b"".join(bs), off.ctypes.data))
+
+
+class PostPlan:
+    """what c3_post_emit needs besides the batch: adapters (name, sequence) in file order, the index set as
+    postprocess.read_fasta(path, True) returns it (idx_to_seq, seq_to_idx) or None, and the options.  dests = the destination
+    directory names in stream order ([""] without an index set; no_index_found is the last one)."""
+
+    def __init__(self, adapters, index=None, undirectional=False, trim=False, barcoded=False):
+        self.ad_names = [_b(a[0]) for a in adapters]
+        self.ad_len = np.array([len(a[1]) for a in adapters], dtype=np.int32)
+        cls = {}
+        self.ad_class = np.array([cls.setdefault(n, len(cls)) for n in self.ad_names], dtype=np.int32)
+        self.class5 = cls.get(b"5Prime_adapter", -1)
+        self.ad_name_off = np.zeros(len(adapters) + 1, dtype=np.int64)
+        np.cumsum([len(n) for n in self.ad_names], out=self.ad_name_off[1:])
+        self.ad_name_cat = b"".join(self.ad_names)
+        self.has_index = bool(index and index[1])
+        self.dests, self.idx_seqs = [""], []
+        if self.has_index:
+            seq_to_idx = index[1]
+            self.idx_seqs = [_b(s) for s in seq_to_idx]
+            names = [x for x in dict.fromkeys(seq_to_idx.values()) if x != "no_index_found"] + ["no_index_found"]
+            self.dests = names
+            self.idx_dest = np.array([names.index(v) for v in seq_to_idx.values()], dtype=np.int32)
+        else:
+            self.idx_dest = np.zeros(0, dtype=np.int32)
+        self.idx_off = np.zeros(len(self.idx_seqs) + 1, dtype=np.int64)
+        np.cumsum([len(s) for s in self.idx_seqs], out=self.idx_off[1:])
+        self.idx_cat = b"".join(self.idx_seqs)
+        self.undirectional, self.trim, self.barcoded = bool(undirectional), bool(trim), bool(barcoded)
+        self.n_streams = 3 * len(self.dests) + 3
+
+
+class PostBatch:
+    """one batch for c3_post_emit in structure-of-arrays form: pointers (int) or numpy arrays; quals may be None.  `keep`
+    holds whatever owns the memory."""
+
+    def __init__(self, n, names, name_off, seqs, quals, off, keep=None):
+        self.n, self.names, self.name_off, self.seqs, self.quals, self.off, self.keep = n, names, name_off, seqs, quals, off, keep
+
+    @classmethod
+    def from_lists(cls, names, seqs, quals=None):
+        nb, sb = [_b(x) for x in names], [_b(x) for x in seqs]
+        no, so = np.zeros(len(nb) + 1, dtype=np.int64), np.zeros(len(sb) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in nb], out=no[1:])
+        np.cumsum([len(x) for x in sb], out=so[1:])
+        arr = [np.frombuffer(b"".join(nb) + b"\0", dtype=np.uint8), np.frombuffer(b"".join(sb) + b"\0", dtype=np.uint8)]
+        q = None
+        if quals is not None:
+            q = np.frombuffer(b"".join(_b(x) for x in quals) + b"\0", dtype=np.uint8)
+            assert len(q) == len(arr[1])
+        return cls(len(nb), arr[0], no, arr[1], q, so)
+
+    @classmethod
+    def from_host(cls, hb, quals=False):
+        return cls(hb.n, hb.c.names, hb.name_off, hb.c.seqs, hb.c.quals if quals else None, hb.off, keep=hb)
+
+
+def _ptr(x):
+    return None if x is None else (x.ctypes.data if isinstance(x, np.ndarray) else x)
+
+
+def _post_call(fn, err, plan, batch, table):
+    tab = np.ascontiguousarray(table, dtype=np.int32)
+    n_ad = len(plan.ad_len)
+    assert tab.size == batch.n * n_ad * 24
+    a = PostArgs(batch.n, _ptr(batch.names), _ptr(batch.name_off), _ptr(batch.seqs), _ptr(batch.quals), _ptr(batch.off),
+                 tab.ctypes.data, n_ad, plan.ad_len.ctypes.data, plan.ad_class.ctypes.data, plan.class5,
+                 C.cast(C.c_char_p(plan.ad_name_cat), C.c_void_p).value, plan.ad_name_off.ctypes.data,
+                 int(plan.has_index), len(plan.idx_seqs), C.cast(C.c_char_p(plan.idx_cat), C.c_void_p).value,
+                 plan.idx_off.ctypes.data, plan.idx_dest.ctypes.data, len(plan.dests),
+                 int(plan.undirectional), int(plan.trim), int(plan.barcoded))
+    S = plan.n_streams
+    so = np.zeros(S + 1, dtype=np.int64)
+    kept = C.c_int64(0)
+    total = int(batch.off[-1]) if batch.n else 0
+    cap = 3 * total * (2 if batch.quals is not None else 1) + 512 * batch.n + 4096      # a guess: the call says what it needs
+    for _try in range(2):
+        arena = np.empty(cap, dtype=np.uint8)
+        rc = fn(C.byref(a), arena.ctypes.data, cap, so.ctypes.data, C.byref(kept))
+        if rc == E_LIMIT and so[S] > cap:
+            cap = int(so[S])
+            continue
+        break
+    if rc < 0:
+        e = C3Error("c3 error %d: %s" % (rc, err().decode()))
+        e.code = rc
+        raise e
+    return arena, so, int(kept.value)
+
+
+def post_emit_host(plan, batch, table):
+    """c3_post_emit_host: the host statement of Handle.post_emit (same arguments and results)"""
+    lib = load()
+    return _post_call(lib.c3_post_emit_host, lambda: lib.c3_last_error(None), plan, batch, table)
 
 
 DEMUX_HEAD = 300        # C3_DEMUX_HEAD

@@ -16,6 +16,9 @@
 extern "C" void c3k_launch_conk(const ConkArgs*, int, int, int, hipStream_t);
 extern "C" void c3k_launch_adapter(const AdapterArgs*, int, hipStream_t);
 extern "C" void c3k_launch_pairwise(const uint8_t*, int, const uint8_t*, int, const uint8_t*, int, uint8_t*, uint8_t*, int*, hipStream_t);
+extern "C" void c3k_launch_post_classify(const PostArgs*, hipStream_t);
+extern "C" void c3k_launch_post_scan(const PostArgs*, hipStream_t);
+extern "C" void c3k_launch_post_emit(const PostArgs*, hipStream_t);
 extern "C" void c3k_launch_match_index(const char*, const int*, int, int, const char*, const long long*, int*, hipStream_t);
 extern "C" void c3k_launch_demux(const uint8_t*, int, const uint8_t*, int, int, int, int32_t*, uint8_t*, hipStream_t);
 extern "C" void c3k_launch_peaks(const PeaksArgs*, int, hipStream_t);
@@ -192,6 +195,7 @@ struct c3_handle {
   DBuf d_dmx_heads, d_dmx_meta, d_dmx_out;                            // demultiplexer: heads, Peq / lengths / byte codes, winners + distances
   DBuf d_qv, s_qv_dirs, s_qv_g, d_qv_cnt, d_gather_qv;                // QV stage: QV arena (like d_cons), direction slots, long-consensus slots, counters, snapshot
   hipEvent_t ev_qv[2] = {nullptr, nullptr}; c3_qv_timing qtm = {}; bool snap_qv = false;
+  DBuf d_post[16]; hipEvent_t ev_post[5] = {}; c3_post_timing ptm = {};       // k_post: inputs, descriptors, pass buffers, arena; event times of the last call
   std::vector<Summary> sum; std::vector<int> work;
   int res_prefix = 0;            // entries of peaks[] / sub_beg[] / sub_end[] that any read of the resident batch uses (0: unknown)
   int peaks_grid = 0; bool debug_msa = false; bool injected = false;
@@ -289,6 +293,7 @@ extern "C" void c3_destroy(c3_handle* h) {
   for (hipStream_t s : {h->stream, h->stream_up, h->stream_dn}) if (s) (void)hipStreamDestroy(s);
   for (hipEvent_t ev : {h->ev_dn, h->ev_up[0], h->ev_up[1], h->ev_qv[0], h->ev_qv[1]}) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : h->ev) if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : h->ev_post) if (ev) (void)hipEventDestroy(ev);
   if (h->h_tot) (void)hipHostFree(h->h_tot);
   delete h;
 }
@@ -1288,6 +1293,82 @@ extern "C" int c3_match_index_batch(c3_handle* h, int n, const char* pieces, con
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, dout.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  return C3_E_OK;
+}
+
+// post-processing records (C3POa_postprocessing.py:238-398 and the PSL text): k_post over one batch.  The host statement is
+// c3_post_emit_host (c3_post.cpp), which also holds the checks both share (c3_post_check_args).  Three steps on the
+// handle's stream: upload + classify + scans, the stream sizes read back (the arena is sized from them), emit + download.
+extern "C" int c3_post_emit(c3_handle* h, const c3_post_args* a, char* arena, int64_t cap, int64_t* stream_off, int64_t* n_kept) {
+  if (!h) return C3_E_ARG;
+  const double t_call = dbg_now_ms();
+  const int rc = c3_post_check_args("c3_post_emit", a, arena, cap, stream_off, n_kept);
+  if (rc != C3_E_OK) return c3_fail(h, rc, c3_last_error(nullptr));
+  HIPCHK(hipSetDevice(h->cfg.device));
+  for (hipEvent_t& ev : h->ev_post) if (!ev) HIPCHK(hipEventCreate(&ev));
+  PostArgs p; memset(&p, 0, sizeof(p));
+  p.n = a->n; p.S = 3 * a->n_dest + 3;
+  p.o.n_ad = a->n_ad; p.o.class5 = a->class5; p.o.undirectional = a->undirectional != 0; p.o.trim = a->trim != 0; p.o.barcoded = a->barcoded != 0;
+  p.o.quals = a->quals != nullptr; p.o.has_index = a->has_index != 0; p.o.n_idx = a->has_index ? a->n_idx : 0; p.o.n_dest = a->n_dest;
+  const int S = p.S, n = a->n, nb = (n + 255) / 256;
+  const size_t sb = n ? (size_t)a->off[n] : 0, nmb = n ? (size_t)a->name_off[n] : 0, tb = sizeof(int32_t) * 24 * (size_t)n * a->n_ad;
+  const size_t anb = a->n_ad ? (size_t)a->ad_name_off[a->n_ad] : 0, ib = p.o.n_idx ? (size_t)a->idx_off[p.o.n_idx] : 0;
+  // every input buffer keeps 16 bytes of slack: the dword copies of k_post_emit read whole aligned dwords
+  struct Up { const void* src; size_t bytes; } up[13] = {
+    {a->names, nmb}, {a->name_off, sizeof(int64_t) * (n + 1)}, {a->seqs, sb}, {a->quals, a->quals ? sb : 0}, {a->off, sizeof(int64_t) * (n + 1)},
+    {a->table, tb}, {a->ad_len, sizeof(int32_t) * a->n_ad}, {a->ad_class, sizeof(int32_t) * a->n_ad}, {a->ad_names, anb},
+    {a->ad_name_off, a->n_ad ? sizeof(int64_t) * (a->n_ad + 1) : 0}, {a->idx_cat, ib}, {a->idx_off, p.o.n_idx ? sizeof(int64_t) * (p.o.n_idx + 1) : 0},
+    {a->idx_dest, sizeof(int32_t) * p.o.n_idx}};
+  DBuf* d = h->d_post;
+  for (int k = 0; k < 13; ++k) {
+    HIPCHK(d[k].ensure(up[k].bytes + 16));
+    if (n > 0 && up[k].bytes) HIPCHK(hipMemcpyAsync(d[k].p, up[k].src, up[k].bytes, hipMemcpyHostToDevice, h->stream));
+  }
+  DBuf& work = d[13]; DBuf& offs = d[14]; DBuf& out = d[15];
+  // work = dec [n] | len [n][6] | roff [n][6] | bsum [nb][S + 1]
+  const size_t w_dec = 0, w_len = w_dec + sizeof(C3PostDec) * n, w_roff = w_len + sizeof(int64_t) * C3_POST_REC * n, w_bsum = w_roff + sizeof(int64_t) * C3_POST_REC * n;
+  HIPCHK(work.ensure(w_bsum + sizeof(long long) * (size_t)(nb + 1) * (S + 1)));
+  HIPCHK(offs.ensure(sizeof(int64_t) * (S + 2)));
+  p.names = d[0].as<uint8_t>(); p.name_off = d[1].as<int64_t>(); p.seqs = d[2].as<uint8_t>(); p.quals = a->quals ? d[3].as<uint8_t>() : nullptr;
+  p.off = d[4].as<int64_t>(); p.table = d[5].as<int32_t>(); p.ad_len = d[6].as<int32_t>(); p.ad_class = d[7].as<int32_t>();
+  p.ad_names = d[8].as<uint8_t>(); p.ad_name_off = d[9].as<int64_t>(); p.idx_cat = d[10].as<uint8_t>(); p.idx_off = d[11].as<int64_t>();
+  p.idx_dest = d[12].as<int32_t>();
+  p.dec = (C3PostDec*)(work.as<uint8_t>() + w_dec); p.len = (int64_t*)(work.as<uint8_t>() + w_len); p.roff = (int64_t*)(work.as<uint8_t>() + w_roff);
+  p.bsum = (long long*)(work.as<uint8_t>() + w_bsum); p.stream_off = offs.as<int64_t>();
+  HIPCHK(hipEventRecord(h->ev_post[0], h->stream));
+  c3k_launch_post_classify(&p, h->stream);
+  HIPCHK(hipEventRecord(h->ev_post[1], h->stream));
+  c3k_launch_post_scan(&p, h->stream);
+  HIPCHK(hipEventRecord(h->ev_post[2], h->stream));
+  HIPCHK(hipGetLastError());
+  std::vector<int64_t> so((size_t)S + 2);
+  HIPCHK(hipMemcpyAsync(so.data(), offs.p, sizeof(int64_t) * (S + 2), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  int64_t need = 0;                                              // the sums come from lengths the rule bounds: anything else is a kernel fault
+  for (int s = 0; s <= S; ++s) { if (so[s] < need) return c3_fail(h, C3_E_HIP, "k_post: stream offsets out of order"); need = so[s]; }
+  if (so[0] != 0 || so[S + 1] < 0 || so[S + 1] > n) return c3_fail(h, C3_E_HIP, "k_post: header out of range");
+  memcpy(stream_off, so.data(), sizeof(int64_t) * (S + 1));
+  *n_kept = so[S + 1];
+  h->ptm = c3_post_timing{};
+  if (need > cap) return c3_fail(h, C3_E_LIMIT, "c3_post_emit: arena too small (bytes needed in stream_off[S])");
+  HIPCHK(out.ensure((size_t)need + 16));
+  p.arena = out.as<uint8_t>();
+  HIPCHK(hipEventRecord(h->ev_post[3], h->stream));
+  c3k_launch_post_emit(&p, h->stream);
+  HIPCHK(hipEventRecord(h->ev_post[4], h->stream));
+  HIPCHK(hipGetLastError());
+  if (need) HIPCHK(hipMemcpyAsync(arena, out.p, (size_t)need, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipEventElapsedTime(&h->ptm.ms_classify, h->ev_post[0], h->ev_post[1]));
+  HIPCHK(hipEventElapsedTime(&h->ptm.ms_scan, h->ev_post[1], h->ev_post[2]));
+  HIPCHK(hipEventElapsedTime(&h->ptm.ms_emit, h->ev_post[3], h->ev_post[4]));
+  h->ptm.n_reads = n; h->ptm.n_kept = so[S + 1]; h->ptm.in_bytes = (int64_t)(nmb + sb * (a->quals ? 2 : 1) + tb); h->ptm.out_bytes = need;
+  h->ptm.ms_call = (float)(dbg_now_ms() - t_call);
+  return C3_E_OK;
+}
+extern "C" int c3_post_emit_timing(c3_handle* h, c3_post_timing* t) {
+  if (!h || !t) return C3_E_ARG;
+  *t = h->ptm;
   return C3_E_OK;
 }
 

@@ -223,12 +223,20 @@ def run(args):
     if args.undirectional and args.barcoded:
         print("Error: undirectional and barcoded are mutually exclusive.")
         sys.exit(1)
-    reads = read_fasta(args.input_fasta_file, False)
     if args.index_file:
         idx_to_seq, seq_to_idx = read_fasta(args.index_file, True)
     else:
         idx_to_seq, seq_to_idx = {}, {}
     psl = args.output_path + PSL_NAME
+    keep_quals = bool(getattr(args, "keep_quals", False))
+    if getattr(args, "emit", "host") == "gpu":
+        n = run_emit_gpu(args, idx_to_seq, seq_to_idx, psl, keep_quals)
+        if n is not None:
+            _multiprocess_conventions(args, idx_to_seq, ".fastq" if keep_quals else ".fasta")
+            return n
+        if keep_quals:
+            sys.exit("--keep-quals needs the device path (--emit gpu), which this run cannot take (see the note above)")
+    reads = read_fasta(args.input_fasta_file, False)
     if not os.path.exists(psl) or os.stat(psl).st_size == 0:
         if getattr(args, "adapter_finder", "gpu") == "gpu":
             find_adapters_gpu(reads, args.adapter_file, psl)
@@ -238,8 +246,15 @@ def run(args):
         print("Reading existing psl file", file=sys.stderr)
     adapter_dict = parse_blat(psl, reads)
     n = write_fasta_file(args, args.output_path, adapter_dict, reads, seq_to_idx, idx_to_seq)
+    _multiprocess_conventions(args, idx_to_seq, ".fasta")
+    return n
+
+
+def _multiprocess_conventions(args, idx_to_seq, suffix):
+    """the end of main() with -n > 1 (:165-214): every destination holds every file, -co compresses them.  suffix: .fasta, or
+    .fastq for the three read files under --keep-quals"""
     if args.threads > 1:
-        names = [FLC, FLC_LEFT, FLC_RIGHT]
+        names = [nm[:-len(".fasta")] + suffix for nm in (FLC, FLC_LEFT, FLC_RIGHT)]
         dirs = [args.output_path]
         if idx_to_seq:
             dirs = [args.output_path + idx + "/" for idx in list(idx_to_seq) + ["no_index_found"]]
@@ -252,4 +267,112 @@ def run(args):
                     open(d + nm, "w").close()
                 if args.compress_output:
                     _gzip_in_place(d + nm)
-    return n
+
+
+def _np_bytes(ptr, nbytes):
+    """a copy of nbytes at ptr as a uint8 array with slack behind it"""
+    import ctypes as C
+    out = np.zeros(nbytes + 16, dtype=np.uint8)
+    if nbytes:
+        C.memmove(out.ctypes.data, ptr, nbytes)
+    return out
+
+
+def _name_hashes(names, name_off):
+    """one 64-bit hash per name, without a Python loop over reads (equal names give equal hashes; a collision of different
+    names only sends the run to the host path)"""
+    n = len(name_off) - 1
+    lens = np.diff(name_off)
+    total = int(name_off[-1])
+    h = np.zeros(n, dtype=np.uint64)
+    if total:
+        pos = np.arange(total, dtype=np.int64) - np.repeat(name_off[:-1], lens)
+        w = (pos.astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(0xD1B54A32D192ED03)) | np.uint64(1)
+        v = (names[:total].astype(np.uint64) + np.uint64(1)) * w
+        v ^= v >> np.uint64(29)
+        v *= np.uint64(0xBF58476D1CE4E5B9)
+        nz = lens > 0
+        h[nz] = np.add.reduceat(v, name_off[:-1][nz])
+    return h ^ (lens.astype(np.uint64) * np.uint64(0x94D049BB133111EB))
+
+
+def run_emit_gpu(args, idx_to_seq, seq_to_idx, psl, keep_quals):
+    """--emit gpu: classification, trimming, orientation, demultiplexing, record formatting and the PSL text on the device
+    (c3_post_emit); only finished file bytes come back.  Returns the number of reads written, or None after a one-line note on
+    stderr when the run has to take the host path (which gives the same files): a PSL to reuse, two records with one name
+    (the host's dict collapses them), a byte >= 0x80 (Python cuts characters, the device bytes), or index sets beyond the
+    device limits."""
+    def fallback(why):
+        print("--emit gpu: %s; using the host path" % why, file=sys.stderr)
+
+    path = args.output_path
+    if os.path.exists(psl) and os.stat(psl).st_size > 0:
+        return fallback("%s exists and is reused" % PSL_NAME)
+    adapters = [(r[0], r[1]) for r in fastx_read(args.adapter_file)]
+    if any(a[0] == "-" for a in adapters) or "-" in idx_to_seq:
+        return fallback("an adapter or index is named '-' (the host path's placeholder)")
+    plan = _lib.PostPlan(adapters, (idx_to_seq, seq_to_idx) if seq_to_idx else None, undirectional=args.undirectional,
+                         trim=args.trim, barcoded=args.barcoded)
+    try:                                                    # an empty batch: the library's own verdict on the index set
+        _lib.post_emit_host(plan, _lib.PostBatch.from_lists([], []), np.zeros(0, dtype=np.int32))
+    except _lib.C3Error as e:
+        if e.code != _lib.E_LIMIT:
+            raise
+        return fallback(str(e).split(": ", 2)[-1])
+    # the input, once, in structure-of-arrays batches (the host path holds every read as well)
+    per = max(1, int(getattr(args, "post_batch", 200000) or 200000))
+    rd = _lib.Reader(args.input_fasta_file, n_sets=1)
+    batches, hashes, high = [], [], False
+    while True:
+        hb = rd.next(per, min_len=0)
+        if hb.n == 0:
+            break
+        nb, sb = int(hb.name_off[-1]), int(hb.off[-1])
+        b = (hb.n, _np_bytes(hb.c.names, nb), hb.name_off, _np_bytes(hb.c.seqs, sb), _np_bytes(hb.c.quals, sb), hb.off)
+        high = high or bool((b[1] & 0x80).any()) or bool((b[3] & 0x80).any())
+        hashes.append(_name_hashes(b[1], b[2]))
+        batches.append(b)
+    noqual = rd.noqual()
+    rd.close()
+    if keep_quals and noqual:
+        sys.exit("--keep-quals: %d records of %s have no quality line" % (noqual, args.input_fasta_file))
+    if high:
+        return fallback("the input holds a byte >= 0x80")
+    if hashes and len(np.unique(np.concatenate(hashes))) < sum(b[0] for b in batches):
+        return fallback("two records share a name")
+    # the files as write_fasta_file opens them
+    suffix = ".fastq" if keep_quals else ".fasta"
+    files = [nm[:-len(".fasta")] + suffix for nm in (FLC, FLC_LEFT, FLC_RIGHT)]
+    if plan.has_index:
+        for idx in idx_to_seq:
+            if os.path.exists(path + idx):
+                shutil.rmtree(path + idx)
+        open(path + MUX_TSV, "w").close()
+    else:
+        for nm in files:
+            open(path + nm, "w").close()
+    if args.barcoded:
+        open(path + FLC_10X, "w").close()
+    targets = [path + (d + "/" if plan.has_index else "") + nm for d in plan.dests for nm in files] + [path + FLC_10X, path + MUX_TSV, psl + ".part"]
+    open(psl + ".part", "w").close()
+    h = _lib.Handle()
+    h.set_splints([a[1] for a in adapters])
+    kept = 0
+    for n, names, name_off, seqs, quals, off in batches:
+        lens = np.diff(off)
+        full = lens > 0
+        tab = np.zeros((n, len(adapters), 2, 12), dtype=np.int32)
+        if full.any():                                      # empty reads are not aligned (find_adapters_gpu): their rows stay zero
+            off_up = off if full.all() else np.concatenate([off[:-1][full], off[-1:]])
+            h.upload_flat(seqs[:int(off[-1])], quals[:int(off[-1])], off_up, b"?" * int(full.sum()))
+            tab[full] = h.scan_adapters()
+        arena, so, k = h.post_emit(plan, _lib.PostBatch(n, names, name_off, seqs, quals if keep_quals else None, off), tab)
+        kept += k
+        for s, target in enumerate(targets):
+            if so[s + 1] > so[s]:
+                os.makedirs(os.path.dirname(target), exist_ok=True)
+                with open(target, "ab") as fh:
+                    fh.write(arena[int(so[s]):int(so[s + 1])].data)
+    h.close()
+    os.replace(psl + ".part", psl)
+    return kept

@@ -470,6 +470,40 @@ int c3_reader_parse_on_device(c3_reader* r, int on);
  * were counted short) from the device: proof that the device path ran and nothing fell back silently */
 int c3_reader_parse_stats(const c3_reader* r, int64_t* stretches_device, int64_t* stretches_host, int64_t* records_device);
 
+/* ---- Post-processing on the GPU (C3POa_postprocessing.py --emit gpu) ----
+ * One batch of consensus reads and its adapter table in, finished file bytes out: classification (parse_blat), trimming,
+ * orientation, oligo-dT demultiplexing and record formatting of write_fasta_file (C3POa_postprocessing.py:238-398), and the
+ * PSL text find_adapters_gpu writes.  The per-read rule is c3poa_amd/csrc/c3_post.h.
+ *   names / name_off[n+1], seqs / off[n+1]: as in c3_host_batch; quals (same offsets) or NULL.  With quals the main, left and
+ *       right records are FASTQ (@name_len, SEQ, +, QUAL; QUAL reversed wherever SEQ is reverse-complemented)
+ *   table[n][n_ad][2][12]: as c3_scan_adapters returns it; taken as data, whatever its values
+ *   ad_len[n_ad]; ad_class[n_ad] >= 0: equal names share a class; class5 = class of "5Prime_adapter" or -1; ad_names /
+ *       ad_name_off[n_ad+1]: the names for the PSL rows
+ *   has_index: an index set is given (-x); idx_cat / idx_off[n_idx+1]: its distinct sequences in file order (at most 16 of at
+ *       most 32 bases, else C3_E_LIMIT); idx_dest[n_idx]: destination of each (same name = same destination); n_dest
+ *       destinations, no_index_found being the last (n_dest = 1 without an index set)
+ * Output: S = 3 * n_dest + 3 streams back to back in arena, stream s at [stream_off[s], stream_off[s+1]): per destination d
+ * main, left, right = 3d, 3d+1, 3d+2; then the 10x file, the oligo-dT TSV, the PSL.  Records within a stream are in input
+ * order.  *n_kept = reads written.  When the streams need more than cap bytes: C3_E_LIMIT, stream_off is filled all the same
+ * (stream_off[S] = bytes needed) and the arena is left alone.  The total of seqs must stay below 2^31 bytes (C3_E_LIMIT).
+ * c3_post_emit runs k_post on the handle's device; c3_post_emit_host is its host statement, byte for byte (errors through
+ * c3_last_error(NULL)). */
+typedef struct c3_post_args {
+  int32_t n;
+  const char* names; const int64_t* name_off;
+  const char* seqs; const char* quals; const int64_t* off;
+  const int32_t* table;
+  int32_t n_ad; const int32_t* ad_len; const int32_t* ad_class; int32_t class5;
+  const char* ad_names; const int64_t* ad_name_off;
+  int32_t has_index, n_idx; const char* idx_cat; const int64_t* idx_off; const int32_t* idx_dest; int32_t n_dest;
+  int32_t undirectional, trim, barcoded;
+} c3_post_args;
+/* kernel time of the last c3_post_emit on the handle (hipEvents on its stream) and of the call with its copies */
+typedef struct { float ms_classify, ms_scan, ms_emit, ms_call; int64_t n_reads, n_kept, in_bytes, out_bytes; } c3_post_timing;
+int c3_post_emit(c3_handle* h, const c3_post_args* a, char* arena, int64_t cap, int64_t* stream_off, int64_t* n_kept);
+int c3_post_emit_host(const c3_post_args* a, char* arena, int64_t cap, int64_t* stream_off, int64_t* n_kept);
+int c3_post_emit_timing(c3_handle* h, c3_post_timing* t);
+
 #ifdef __cplusplus
 }
 #endif
