@@ -1,9 +1,10 @@
-// c3_args.h -- kernel argument blocks shared by the launchers (c3_api.hip) and the kernels.
+// c3_args.h -- kernel argument blocks shared by the host units (c3_host.h) and the kernels;
+// PostArgs lives with its rule in c3_post.h.
 #pragma once
 #include "c3_dev.h"
 #include <cstddef>
 
-// Device counter block of a handle (c3_api.hip: d_counter).  Every field has one purpose; the host zeroes a stage's fields
+// Device counter block of a handle (c3_host.h: d_counter).  Every field has one purpose; the host zeroes a stage's fields
 // before its launch and reads them by name.
 struct C3Counters {
   int queue;                            // work queue of k_conk, k_adapter, k_poa, k_prep and the first k_window launch
@@ -141,20 +142,4 @@ struct QvArgs {
   int* gS; uint8_t* gcodes; long long gcap;        // [grid][gcap]: S and codes of a consensus longer than lds_n
   int lds_n;                                       // consensus columns held in LDS (S int32 + code byte each)
   unsigned long long* cnt;                         // [0] reads, [1] pieces, [2] skipped, [3] band cells, [4] edge hits
-};
-
-// k_post (k_post.hip): post-processing records.  One batch in structure-of-arrays form, its adapter table, the adapter and
-// index descriptors (c3_post_args of c3poa.h, on the device), the rule's options, and what the passes hand each other.
-#include "c3_post.h"
-struct PostArgs {
-  int n, S; C3PostOpt o;
-  const uint8_t* names; const int64_t* name_off; const uint8_t* seqs; const uint8_t* quals; const int64_t* off;
-  const int32_t* table; const int32_t* ad_len; const int32_t* ad_class; const uint8_t* ad_names; const int64_t* ad_name_off;
-  const uint8_t* idx_cat; const int64_t* idx_off; const int32_t* idx_dest;
-  C3PostDec* dec;                       // [n] decisions
-  int64_t* len;                         // [n][C3_POST_REC] record lengths: main, left, right, 10x, TSV line, PSL rows
-  long long* bsum;                      // [workgroups of 256 reads][S + 1] sums, then exclusive prefix sums; column S = kept reads
-  int64_t* stream_off;                  // [S + 2]: stream starts, total, kept reads
-  int64_t* roff;                        // [n][C3_POST_REC] arena offset of every record
-  uint8_t* arena;
 };

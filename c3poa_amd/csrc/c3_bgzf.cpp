@@ -3,11 +3,10 @@
 // histogram, the bit packing, the stored fallback and the CRC are written out here independently of the kernel.
 #include "../../include/c3poa.h"
 #include "c3_bgzf.h"
+#include "c3_checks.h"
 #include <zlib.h>
 #include <algorithm>
 #include <cstring>
-
-void c3_set_host_error(const char* msg);          // c3_api.hip
 
 namespace {
 

@@ -1,0 +1,24 @@
+// c3_checks.h -- what the host statements (*.cpp, plain C++) and the HIP host units (c3_host.h) share: the handle-free error
+// text, the argument checks that a device call and its host statement both apply, and the reader's private calls into the
+// stream unit.  No hip_runtime.h here.
+#pragma once
+#include <stdint.h>
+#include "../../include/c3poa.h"
+
+void c3_set_host_error(const char* msg);        // c3_handle.hip: the text of c3_last_error(NULL)
+
+int c3_demux_prepare(int n_a, const char* a_cat, const int64_t* a_off, int n_b, const char* b_cat, const int64_t* b_off,
+                     uint8_t* tab, int* n_codes, const char** msg);                                                  // c3_io.cpp
+int c3_qv_check(const char* cons, int n, int n_pieces, const char* seq_cat, const char* qual_cat, const int64_t* piece_off,
+                const int32_t* modes, const char* qv_out, const char** msg);                                          // c3_qv.cpp
+int c3_fastq_check_args(const char* who, const char* text, int64_t n, const char* names, int64_t names_cap, const int64_t* name_off,
+                        const char* seqs, const char* quals, int64_t bases_cap, const int64_t* off, int64_t max_records,
+                        c3_fastq_info* info);                                                                         // c3_fastq.cpp
+int c3_bgzf_data_error(const char* who, int64_t member, int st);                                                      // c3_inflate.cpp
+
+// the reader's device stretches (c3_stream.hip, called by c3_io.cpp; not part of the public interface)
+struct c3_fq_stretch { c3_fastq_info info; const int64_t* off; const int64_t* name_off; int64_t text_bytes; };
+extern "C" int c3_bgzf_stretch_parse(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, int64_t carry_from, int64_t carry_len,
+                                     int at_eof, c3_fq_stretch* out);
+extern "C" int c3_bgzf_stretch_fetch(c3_bgzf* z, int slot, int64_t r0, int64_t r1, char* names, char* seqs, char* quals);
+extern "C" int c3_bgzf_stretch_text(c3_bgzf* z, int slot, int64_t from, int64_t len, char* dst);

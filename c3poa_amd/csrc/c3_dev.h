@@ -109,5 +109,3 @@ __device__ __forceinline__ int wave_scan_add(int x) {
 #define PH_MARK(i)
 #define PH_FLUSH(p)
 #endif
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return c3_hip_fail(h, e_, #x, __LINE__); } while (0)

@@ -4,11 +4,10 @@
 // sanitizer on the CPU.
 #include "../../include/c3poa.h"
 #include "c3_fastq.h"
+#include "c3_checks.h"
 #include <cstring>
 
-void c3_set_host_error(const char* msg);          // c3_api.hip
-
-// argument rules shared with c3_fastq_parse (c3_api.hip); 0 = go on
+// argument rules shared with c3_fastq_parse (c3_stream.hip); 0 = go on
 int c3_fastq_check_args(const char* who, const char* text, int64_t n, const char* names, int64_t names_cap, const int64_t* name_off,
                         const char* seqs, const char* quals, int64_t bases_cap, const int64_t* off, int64_t max_records,
                         c3_fastq_info* info) {

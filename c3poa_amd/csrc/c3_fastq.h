@@ -33,7 +33,7 @@ template <class I> C3_FQ_HD inline I c3_fastq_name_len(const char* t, I b, I e) 
   return k - (b + 1);
 }
 
-// what k_fastq leaves for the host after its scans (c3_api.hip reads it back; consumed is relative to the text's start)
+// what k_fastq leaves for the host after its scans (c3_stream.hip reads it back; consumed is relative to the text's start)
 struct C3FqHdr {
   int32_t n_lines;                // '\n' in the text
   int32_t n_lines_v;              // ... plus one when at_eof and the text does not end in '\n' (the unterminated last line)

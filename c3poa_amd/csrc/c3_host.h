@@ -1,0 +1,170 @@
+// c3_host.h -- what the HIP host units share (c3_handle.hip, c3_stages.hip, c3_calls.hip, c3_scans.hip, c3_stream.hip): the two
+// handles, the owned device buffer, the error idioms and the few helpers that cross units.  Host only; no kernel includes it.
+#pragma once
+#include "c3_dev.h"
+#include "c3_args.h"
+#include "c3_launch.h"
+#include "c3_checks.h"
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstddef>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+struct c3_handle;
+namespace c3h {                                  // defined once, used by several units (mangled: not part of the C ABI)
+extern thread_local double g_alloc_ms;           // host time spent growing device buffers (hipFree synchronises the device); c3_handle.hip
+int qv_scratch(c3_handle* h, long long max_m, long long max_n, int n_items, QvArgs& a, int* grid);      // c3_stages.hip
+int fetch_msa_rows(c3_handle* h, int read, int nrows, char* out, int64_t cap, int* msa_len);           // c3_handle.hip
+}
+
+static inline double dbg_now_ms() { using namespace std::chrono; return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count(); }
+// C3_DEBUG=1: progress lines on stderr, each stamped with the host clock (ms) -- shows the host gaps between the stages
+#define DBG(...) do { if (getenv("C3_DEBUG")) { fprintf(stderr, "[c3 %.3f] ", dbg_now_ms()); fprintf(stderr, __VA_ARGS__); fflush(stderr); } } while (0)
+
+// ---- handle -----------------------------------------------------------------------------
+struct DBuf {                                   // owns one device allocation (move-only)
+  void* p = nullptr; size_t cap = 0;
+  DBuf() = default;
+  DBuf(DBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DBuf& operator=(DBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+  DBuf(const DBuf&) = delete;
+  DBuf& operator=(const DBuf&) = delete;
+  ~DBuf() { if (p) (void)hipFree(p); }
+  hipError_t ensure(size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    const double t0 = dbg_now_ms();
+    if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
+    size_t want = bytes + bytes / 8 + 256;
+    hipError_t e = hipMalloc(&p, want);
+    if (e == hipSuccess) cap = want;
+    // test hook: fresh device memory usually reads as zero, which hides reads of cells nobody wrote; C3_DEBUG_POISON fills every
+    // new buffer with a pattern instead (tests/test_gpu_band.py runs the pipeline that way)
+    if (e == hipSuccess && getenv("C3_DEBUG_POISON")) e = hipMemset(p, 0xA5, want);
+    c3h::g_alloc_ms += dbg_now_ms() - t0;
+    return e;
+  }
+  // ensure(bytes + slack), then queue the upload of `bytes` from src on s
+  hipError_t put(const void* src, size_t bytes, hipStream_t s, size_t slack = 0) {
+    const hipError_t e = ensure(bytes + slack);
+    return e != hipSuccess ? e : hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s);
+  }
+  template <class T> T* as() const { return (T*)p; }
+};
+
+struct Summary { int status, n_sub, max_sub, sum_sub, max_dang, front, tail, n_peaks; };
+enum { EV_N = 10 };
+struct c3_handle {
+  c3_config cfg; std::string err; hipStream_t stream = nullptr; int n_cus = 256; size_t mem_total = 0;
+  // staged (next) batch: copied on its own stream while the resident batch is being processed
+  hipStream_t stream_up = nullptr; hipEvent_t ev_up[2] = {nullptr, nullptr};
+  // results in flight (c3_batch_results_snapshot .. _fetch): snapshot of the records + compact consensus bytes, copied on a third stream
+  hipStream_t stream_dn = nullptr; hipEvent_t ev_dn = nullptr; long long* h_tot = nullptr;
+  std::atomic<bool> snap_pending{false}; int snap_n = 0, snap_kp = 0; long long snap_tot = 0; bool snap_cons = false;
+  DBuf d_info_snap, d_coff_part;
+  struct Staged { DBuf d_ascii, d_pk, d_woff, d_qual, d_off, d_strand, d_sid; std::vector<int64_t> off, woff; std::vector<int16_t> sid; std::string strand;
+                  int n = 0; int64_t total = 0, words = 0, maxL = 0; bool pending = false; } st;
+  hipEvent_t ev[EV_N] = {};
+  // splints
+  int n_spl = 0, max_spl = 0; std::vector<int> sp_len; DBuf d_sp_codes, d_sp_len;
+  // batch
+  int n = 0; int64_t total = 0, words = 0, maxL = 0; std::vector<int64_t> off, woff;
+  DBuf d_ascii, d_pk, d_woff, d_qual, d_off, d_strand, d_sid, d_info, d_track, d_draft, d_tpos, d_cons, d_counter, d_gather, d_gather_off;
+  DBuf d_raw, d_nraw, d_sum, d_work, d_bufA, d_bufB, d_cand, d_cst, d_msa, d_msa_off, d_msa_len;
+  DBuf s_poa_i, s_poa_nk, s_poa_cells, s_poa_b, s_poa_sc, s_poa_desc, s_poa_jump, s_poa_path, d_overflow;      // POA scratch
+  int n_poa_redo = 0;        // reads of the last run that needed the full-size second POA pass
+  int n_poa_redo16 = 0;      // ... of them: because a score left the 16-bit cells
+  DBuf s_eD, s_lw, d_wrec, d_wlay, d_wbase, d_wout;       // prep / windows
+  DBuf s_win_i, s_win_nk, s_win_h, s_win_d, s_win_b, s_win_sc, s_win_desc, s_win_h2, s_win_d2, d_wovf;
+  DBuf s_zero_d, d_zinfo, d_zflag, d_zwork; std::vector<int> zwork;  // zero-repeat rescue: k_zero direction bytes, per-read records, work list
+  DBuf s_zero_l;                                                      // k_zero_long slots
+  DBuf d_dmx_heads, d_dmx_meta, d_dmx_out;                            // demultiplexer: heads, Peq / lengths / byte codes, winners + distances
+  DBuf d_qv, s_qv_dirs, s_qv_g, d_qv_cnt, d_gather_qv;                // QV stage: QV arena (like d_cons), direction slots, long-consensus slots, counters, snapshot
+  hipEvent_t ev_qv[2] = {nullptr, nullptr}; c3_qv_timing qtm = {}; bool snap_qv = false;
+  DBuf d_post[16]; hipEvent_t ev_post[5] = {}; c3_post_timing ptm = {};       // k_post: inputs, descriptors, pass buffers, arena; event times of the last call
+  std::vector<Summary> sum; std::vector<int> work;
+  int res_prefix = 0;            // entries of peaks[] / sub_beg[] / sub_end[] that any read of the resident batch uses (0: unknown)
+  int peaks_grid = 0; bool debug_msa = false; bool injected = false;
+  int n_windows = 0;
+  c3_timing tm;
+  unsigned long long phase_poa[16] = {0}, phase_win[16] = {0};
+  int stages_done = 0;
+};
+
+// ---- errors: a c3_handle call fails into h->err (HIPCHK, c3_fail); a handle-free or c3_bgzf call into the text of
+// c3_last_error(NULL) (ZCHK, host_fail) ------------------------------------------------------------------------------------
+static inline int c3_hip_fail(c3_handle* h, hipError_t e, const char* what, const char* file, int line) {
+  char buf[512];
+  const char* base = strrchr(file, '/');
+  snprintf(buf, sizeof buf, "HIP error %d (%s) at %s:%d: %s", (int)e, hipGetErrorString(e), base ? base + 1 : file, line, what);
+  if (h) h->err = buf;
+  return C3_E_HIP;
+}
+static inline int c3_fail(c3_handle* h, int code, const char* msg) { if (h) h->err = msg; return code; }
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return c3_hip_fail(h, e_, #x, __FILE__, __LINE__); } while (0)
+static inline int host_fail(int code, const char* msg) { c3_set_host_error(msg); return code; }
+static inline int bgzf_fail(hipError_t e, const char* what) {
+  char buf[256];
+  snprintf(buf, sizeof buf, "HIP error %d (%s): %s", (int)e, hipGetErrorString(e), what);
+  return host_fail(C3_E_HIP, buf);
+}
+#define ZCHK(x, what) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bgzf_fail(e_, what); } while (0)
+
+// a value overridden for the length of a scope: the saved one comes back on every way out
+template <class T> struct Override {
+  T& ref; const T saved;
+  Override(T& r, T v) : ref(r), saved(r) { r = v; }
+  ~Override() { ref = saved; }
+  Override(const Override&) = delete;
+};
+
+// the device counter block (C3Counters, c3_args.h): zeroed and read by field
+static inline C3Counters* dev_cnt(c3_handle* h) { return h->d_counter.as<C3Counters>(); }
+template <class T> static inline hipError_t zero_cnt(c3_handle* h, T* field) { return hipMemsetAsync(field, 0, sizeof(T), h->stream); }
+static inline hipError_t read_counters(c3_handle* h, C3Counters* c) {
+  hipError_t e = hipMemcpyAsync(c, h->d_counter.p, sizeof(*c), hipMemcpyDeviceToHost, h->stream);
+  return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
+}
+
+static inline int code_of(char c) {
+  switch (c) { case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': case 'U': case 'u': return 3; default: return 0; }
+}
+
+static inline C3Batch dev_batch(c3_handle* h) {
+  C3Batch b; b.n = h->n; b.pk = h->d_pk.as<uint32_t>(); b.woff = h->d_woff.as<int64_t>(); b.qual = h->d_qual.as<uint8_t>();
+  b.off = h->d_off.as<int64_t>(); b.strand = h->d_strand.as<uint8_t>(); b.splint_id = h->d_sid.as<int16_t>();
+  return b;
+}
+static inline C3Params dev_params(const c3_config& c) {
+  C3Params p;
+  p.conk_match = c.conk_match; p.conk_mismatch = c.conk_mismatch; p.conk_penalty = c.conk_penalty;
+  p.sg_iters = c.sg_iters; p.sg_window = c.sg_window; p.sg_order = c.sg_order; p.mdist = c.mdistcutoff;
+  p.poa_match = c.poa_match; p.poa_mismatch = c.poa_mismatch; p.o1 = c.poa_o1; p.e1 = c.poa_e1; p.o2 = c.poa_o2; p.e2 = c.poa_e2;
+  p.band_b = c.poa_band_b; p.band_f = c.poa_band_f;
+  p.pol_match = c.pol_match; p.pol_mismatch = c.pol_mismatch; p.pol_gap = c.pol_gap; p.pol_window = c.pol_window; p.pol_q = c.pol_q;
+  p.dang_band = c.dang_band;
+  p.zero = c.zero; p.zr_match = 2; p.zr_mismatch = 4; p.zr_gapo = 4; p.zr_gape = 2; p.zr_min_score = 80; p.zr_max_cells = (int)c.zero_max_cells;
+  return p;
+}
+
+// the stream handle (c3_stream.hip): BGZF compress / inflate, FASTQ parse, the reader's stretches
+struct c3_bgzf {
+  int device = 0; hipStream_t stream = nullptr; int* h_sizes = nullptr;
+  DBuf d_in, d_slots, d_sizes, d_packed;
+  C3BgzfMember* h_mem = nullptr; int2* h_res = nullptr;         // k_inflate: descriptors in, (status, CRC) out; first use
+  DBuf d_mem, d_res, d_out;
+  // k_fastq (first use): scratch of one parse, and two slots of text + finished records (the reader parses one stretch while
+  // the groups of the other are copied out on copy_stream; the stand-alone call uses slot 0)
+  struct FqSlot {
+    DBuf text, names, seqs, quals, off, name_off, src;
+    int64_t text_n = 0, n_rec = 0;
+    int64_t* h_off = nullptr; int64_t* h_name_off = nullptr; size_t h_cap = 0;       // page-locked copies of off / name_off
+  } fq[2];
+  DBuf d_cnt, d_nl, d_slen, d_nlen, d_bsum, d_hdr;
+  C3FqHdr* h_hdr = nullptr;
+  hipStream_t copy_stream = nullptr;
+};

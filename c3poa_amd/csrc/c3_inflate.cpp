@@ -3,10 +3,9 @@
 // the tests hold this against Python's zlib, and damaged input can be thrown at it under a sanitizer on the CPU.
 #include "../../include/c3poa.h"
 #include "c3_inflate.h"
+#include "c3_checks.h"
 #include <cstdio>
 #include <cstring>
-
-void c3_set_host_error(const char* msg);          // c3_api.hip
 
 namespace {
 

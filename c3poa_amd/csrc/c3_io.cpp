@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/c3poa.h"
+#include "c3_checks.h"
 
 namespace {
 
@@ -71,13 +72,9 @@ struct BatchSet {
 // (extra subfield 'B','C'), so the members of a stretch of the file can be located WITHOUT inflating them and inflated by several
 // threads at once -- a plain gzip stream is one zlib state and inflates at ~275 MB/s whatever the machine (27 k reads/s:
 // profiles/r04_host_ceiling_gz.txt).  Plain gzip stays on gzread.
-// a stretch that stays on the device (c3_reader_parse_on_device): c3_api.hip inflates it behind the record the previous
+// a stretch that stays on the device (c3_reader_parse_on_device): c3_stream.hip inflates it behind the record the previous
 // stretch's end cut, parses it with k_fastq and keeps the finished records until the slot is loaded again
-struct c3_fq_stretch { c3_fastq_info info; const int64_t* off; const int64_t* name_off; int64_t text_bytes; };
-extern "C" int c3_bgzf_stretch_parse(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, int64_t carry_from, int64_t carry_len,
-                                     int at_eof, c3_fq_stretch* out);
-extern "C" int c3_bgzf_stretch_fetch(c3_bgzf* z, int slot, int64_t r0, int64_t r1, char* names, char* seqs, char* quals);
-extern "C" int c3_bgzf_stretch_text(c3_bgzf* z, int slot, int64_t from, int64_t len, char* dst);
+// (c3_fq_stretch, c3_bgzf_stretch_*: c3_checks.h)
 
 struct BgzfStretch {
   std::vector<unsigned char> comp;          // compressed members of the stretch, back to back
@@ -1111,8 +1108,6 @@ extern "C" int c3_match_index(const char* seq, int n, int n_idx, const char* idx
 // ---- sample demultiplexer (paper/Demultiplex_R2C2_reads.py, demultiplex) ------------------------------------------
 // c3_demux_prepare checks the two index sets for both entry points and builds the byte -> code table of k_demux: the
 // distinct bytes of all indexes get codes 1..K in byte order, every other byte 0 (which matches no index position).
-void c3_set_host_error(const char* msg);        // c3_api.hip: the text of c3_last_error(NULL)
-
 int c3_demux_prepare(int n_a, const char* a_cat, const int64_t* a_off, int n_b, const char* b_cat, const int64_t* b_off,
                      uint8_t* tab, int* n_codes, const char** msg) {
   const int ns[2] = {n_a, n_b}; const char* cats[2] = {a_cat, b_cat}; const int64_t* offs[2] = {a_off, b_off};

@@ -7,8 +7,7 @@
 #include <vector>
 #include "../../include/c3poa.h"
 #include "c3_post.h"
-
-void c3_set_host_error(const char* msg);        // c3_api.hip: the text of c3_last_error(NULL)
+#include "c3_checks.h"
 
 int c3_post_check_args(const char* who, const c3_post_args* a, char* arena, int64_t cap, int64_t* stream_off, int64_t* n_kept) {
   static thread_local char msg[160];

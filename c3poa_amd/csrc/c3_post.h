@@ -218,6 +218,21 @@ C3_PO_HD inline int64_t c3_post_psl_row(char* out, const int32_t* e, const char*
   return n;
 }
 
+// k_post (k_post.hip): post-processing records.  One batch in structure-of-arrays form, its adapter table, the adapter and
+// index descriptors (c3_post_args of c3poa.h, on the device), the rule's options, and what the passes hand each other.
+struct PostArgs {
+  int n, S; C3PostOpt o;
+  const uint8_t* names; const int64_t* name_off; const uint8_t* seqs; const uint8_t* quals; const int64_t* off;
+  const int32_t* table; const int32_t* ad_len; const int32_t* ad_class; const uint8_t* ad_names; const int64_t* ad_name_off;
+  const uint8_t* idx_cat; const int64_t* idx_off; const int32_t* idx_dest;
+  C3PostDec* dec;                       // [n] decisions
+  int64_t* len;                         // [n][C3_POST_REC] record lengths: main, left, right, 10x, TSV line, PSL rows
+  long long* bsum;                      // [workgroups of 256 reads][S + 1] sums, then exclusive prefix sums; column S = kept reads
+  int64_t* stream_off;                  // [S + 2]: stream starts, total, kept reads
+  int64_t* roff;                        // [n][C3_POST_REC] arena offset of every record
+  uint8_t* arena;
+};
+
 // argument rules shared by c3_post_emit and c3_post_emit_host (c3_post.cpp); C3_E_OK = go on
 struct c3_post_args;
 int c3_post_check_args(const char* who, const c3_post_args* a, char* arena, int64_t cap, int64_t* stream_off, int64_t* n_kept);

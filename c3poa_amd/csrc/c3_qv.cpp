@@ -8,8 +8,7 @@
 #include <vector>
 
 #include "../../include/c3poa.h"
-
-void c3_set_host_error(const char* msg);        // c3_api.hip: the text of c3_last_error(NULL)
+#include "c3_checks.h"
 
 namespace {
 const int NEG = -(1 << 28);                     // a cell outside the band or the matrix

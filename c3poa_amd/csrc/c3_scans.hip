@@ -1,0 +1,198 @@
+// c3_scans.hip -- side stages that borrow the batch handle's stream: splint / adapter finders over the resident batch,
+// match_index, the post-processing records (k_post) and the sample demultiplexer (k_demux).
+#include "c3_host.h"
+#include "c3_post.h"
+
+// splint / strand finder (replaces the blat step of bin/preprocess.py:12-45,61-77): every read of the resident
+// batch is scored against every splint on both strands with the conk kernel; out[i*n_spl*2 + s*2 + rc] =
+// {max of the track, its offset, mean of the track, read length}.  assign_* picks the best candidate and
+// accepts it when max >= 6 * mean (the same contrast test call_peaks applies later, bin/call_peaks.py:13) and
+// max >= match*51*52/2 (a perfect 51-base match: the `matches > 50` filter of bin/preprocess.py:32).
+extern "C" int c3_scan_splints(c3_handle* h, int32_t* out /* [n][n_spl][2][4] */, int16_t* assign_splint, char* assign_strand) {
+  if (!h || h->n <= 0 || h->n_spl <= 0) return C3_E_STATE;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t items = (size_t)h->n * h->n_spl * 2;
+  DBuf scan;
+  HIPCHK(scan.ensure(sizeof(int32_t) * 4 * items));
+  HIPCHK(zero_cnt(h, &dev_cnt(h)->queue));
+  ConkArgs a; memset(&a, 0, sizeof(a));
+  a.b = dev_batch(h); a.sp_codes = h->d_sp_codes.as<uint8_t>(); a.sp_len = h->d_sp_len.as<int>();
+  a.track = nullptr; a.info = h->d_info.as<C3Info>(); a.cnt = dev_cnt(h);
+  a.match = h->cfg.conk_match; a.mismatch = h->cfg.conk_mismatch; a.penalty = h->cfg.conk_penalty;
+  a.n_spl = h->n_spl; a.scan = scan.as<int32_t>();
+  const int waves = (int)std::min<size_t>(items, (size_t)h->n_cus * 32);
+  c3k_launch_conk(&a, h->max_spl, (waves + 3) / 4, 1, h->stream);
+  HIPCHK(hipGetLastError());
+  std::vector<int32_t> tmp(4 * items);
+  HIPCHK(hipMemcpyAsync(tmp.data(), scan.p, sizeof(int32_t) * 4 * items, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (out) memcpy(out, tmp.data(), sizeof(int32_t) * 4 * items);
+  for (int i = 0; i < h->n; ++i) {
+    int best = -1, bs = -1;
+    for (int c = 0; c < h->n_spl * 2; ++c) { const int32_t* e = &tmp[((size_t)i * h->n_spl * 2 + c) * 4]; if (e[0] > bs) { bs = e[0]; best = c; } }
+    // matches > 50 of bin/preprocess.py:32, as the diagonal sum of a perfect 51-base match
+    const long long floor51 = (long long)h->cfg.conk_match * 51 * 52 / 2;
+    bool ok = best >= 0 && bs >= floor51 && (long long)bs >= 6LL * tmp[((size_t)i * h->n_spl * 2 + best) * 4 + 2];
+    if (assign_splint) assign_splint[i] = ok ? (int16_t)(best >> 1) : (int16_t)-1;
+    if (assign_strand) assign_strand[i] = ok ? ((best & 1) ? '-' : '+') : '?';
+  }
+  return C3_E_OK;
+}
+
+// adapter finder of the post-processing step (replaces the blat call of C3POa_postprocessing.py:229-236): best local
+// affine alignment of every read of the resident batch against every entry of the splint table (= the adapters,
+// c3_set_splints) on both strands, traced back.  out[(i*n_ad + a)*2 + rc][12] = score, qStart, qEnd, tStart, tEnd
+// (PSL conventions: query = read, forward coordinates; target = adapter, forward coordinates), matches, mismatches,
+// qBaseInsert, tBaseInsert, qNumInsert, tNumInsert, read length.  score 0 = no alignment.
+extern "C" int c3_scan_adapters(c3_handle* h, int32_t* out) {
+  if (!h || h->n <= 0 || h->n_spl <= 0 || !out) return C3_E_STATE;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const size_t items = (size_t)h->n * h->n_spl * 2;
+  const long long dcap = (long long)(h->maxL + 1) * (h->max_spl + 1) + 64;
+  const int grid = (int)std::min<size_t>(items, (size_t)h->n_cus * 16);
+  DBuf res, dd;
+  HIPCHK(res.ensure(sizeof(int32_t) * 12 * items)); HIPCHK(dd.ensure((size_t)dcap * grid));
+  HIPCHK(zero_cnt(h, &dev_cnt(h)->queue));
+  AdapterArgs a; memset(&a, 0, sizeof(a));
+  a.b = dev_batch(h); a.p = dev_params(h->cfg); a.cnt = dev_cnt(h);
+  a.ad_codes = h->d_sp_codes.as<uint8_t>(); a.ad_len = h->d_sp_len.as<int>(); a.n_ad = h->n_spl;
+  a.D = dd.as<uint8_t>(); a.dcap = dcap; a.out = res.as<int32_t>();
+  c3k_launch_adapter(&a, grid, h->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, res.p, sizeof(int32_t) * 12 * items, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return C3_E_OK;
+}
+
+// match_index for a batch of pieces (C3POa_postprocessing.py:266-285): pieces = n slots of 64 bytes, lens[n] (<= 64);
+// at most 16 indexes of at most 32 bases (idx_off[n_idx+1] into idx_cat); out[i] = winning index number or -1.
+extern "C" int c3_match_index_batch(c3_handle* h, int n, const char* pieces, const int32_t* lens, int n_idx,
+                                    const char* idx_cat, const int64_t* idx_off, int32_t* out) {
+  if (!h || n <= 0 || !pieces || !lens || !idx_cat || !idx_off || !out) return C3_E_ARG;
+  if (n_idx < 2) { for (int i = 0; i < n; ++i) out[i] = -1; return C3_E_OK; }      // the reference needs a runner-up
+  if (n_idx > 16) return c3_fail(h, C3_E_LIMIT, "more than 16 indexes");
+  for (int k = 0; k < n_idx; ++k) if (idx_off[k + 1] - idx_off[k] > 32 || idx_off[k + 1] < idx_off[k]) return c3_fail(h, C3_E_LIMIT, "index longer than 32 bases");
+  for (int i = 0; i < n; ++i) if (lens[i] < 0 || lens[i] > 64) return c3_fail(h, C3_E_ARG, "piece longer than 64 bases");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  DBuf dp, dl, di, doff, dout;
+  const size_t ib = (size_t)idx_off[n_idx];
+  HIPCHK(dout.ensure(sizeof(int) * (size_t)n));
+  HIPCHK(dp.put(pieces, (size_t)n * 64, h->stream)); HIPCHK(dl.put(lens, sizeof(int) * (size_t)n, h->stream));
+  HIPCHK(di.put(idx_cat, ib, h->stream, 16)); HIPCHK(doff.put(idx_off, sizeof(int64_t) * (size_t)(n_idx + 1), h->stream));
+  c3k_launch_match_index(dp.as<char>(), dl.as<int>(), n, n_idx, di.as<char>(), doff.as<long long>(), dout.as<int>(), h->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, dout.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return C3_E_OK;
+}
+
+// post-processing records (C3POa_postprocessing.py:238-398 and the PSL text): k_post over one batch.  The host statement is
+// c3_post_emit_host (c3_post.cpp), which also holds the checks both share (c3_post_check_args).  Three steps on the
+// handle's stream: upload + classify + scans, the stream sizes read back (the arena is sized from them), emit + download.
+extern "C" int c3_post_emit(c3_handle* h, const c3_post_args* a, char* arena, int64_t cap, int64_t* stream_off, int64_t* n_kept) {
+  if (!h) return C3_E_ARG;
+  const double t_call = dbg_now_ms();
+  const int rc = c3_post_check_args("c3_post_emit", a, arena, cap, stream_off, n_kept);
+  if (rc != C3_E_OK) return c3_fail(h, rc, c3_last_error(nullptr));
+  HIPCHK(hipSetDevice(h->cfg.device));
+  for (hipEvent_t& ev : h->ev_post) if (!ev) HIPCHK(hipEventCreate(&ev));
+  PostArgs p; memset(&p, 0, sizeof(p));
+  p.n = a->n; p.S = 3 * a->n_dest + 3;
+  p.o.n_ad = a->n_ad; p.o.class5 = a->class5; p.o.undirectional = a->undirectional != 0; p.o.trim = a->trim != 0; p.o.barcoded = a->barcoded != 0;
+  p.o.quals = a->quals != nullptr; p.o.has_index = a->has_index != 0; p.o.n_idx = a->has_index ? a->n_idx : 0; p.o.n_dest = a->n_dest;
+  const int S = p.S, n = a->n, nb = (n + 255) / 256;
+  const size_t sb = n ? (size_t)a->off[n] : 0, nmb = n ? (size_t)a->name_off[n] : 0, tb = sizeof(int32_t) * 24 * (size_t)n * a->n_ad;
+  const size_t anb = a->n_ad ? (size_t)a->ad_name_off[a->n_ad] : 0, ib = p.o.n_idx ? (size_t)a->idx_off[p.o.n_idx] : 0;
+  // every input buffer keeps 16 bytes of slack: the dword copies of k_post_emit read whole aligned dwords
+  struct Up { const void* src; size_t bytes; } up[13] = {
+    {a->names, nmb}, {a->name_off, sizeof(int64_t) * (n + 1)}, {a->seqs, sb}, {a->quals, a->quals ? sb : 0}, {a->off, sizeof(int64_t) * (n + 1)},
+    {a->table, tb}, {a->ad_len, sizeof(int32_t) * a->n_ad}, {a->ad_class, sizeof(int32_t) * a->n_ad}, {a->ad_names, anb},
+    {a->ad_name_off, a->n_ad ? sizeof(int64_t) * (a->n_ad + 1) : 0}, {a->idx_cat, ib}, {a->idx_off, p.o.n_idx ? sizeof(int64_t) * (p.o.n_idx + 1) : 0},
+    {a->idx_dest, sizeof(int32_t) * p.o.n_idx}};
+  DBuf* d = h->d_post;
+  for (int k = 0; k < 13; ++k) {
+    HIPCHK(d[k].ensure(up[k].bytes + 16));
+    if (n > 0 && up[k].bytes) HIPCHK(hipMemcpyAsync(d[k].p, up[k].src, up[k].bytes, hipMemcpyHostToDevice, h->stream));
+  }
+  DBuf& work = d[13]; DBuf& offs = d[14]; DBuf& out = d[15];
+  // work = dec [n] | len [n][6] | roff [n][6] | bsum [nb][S + 1]
+  const size_t w_dec = 0, w_len = w_dec + sizeof(C3PostDec) * n, w_roff = w_len + sizeof(int64_t) * C3_POST_REC * n, w_bsum = w_roff + sizeof(int64_t) * C3_POST_REC * n;
+  HIPCHK(work.ensure(w_bsum + sizeof(long long) * (size_t)(nb + 1) * (S + 1)));
+  HIPCHK(offs.ensure(sizeof(int64_t) * (S + 2)));
+  p.names = d[0].as<uint8_t>(); p.name_off = d[1].as<int64_t>(); p.seqs = d[2].as<uint8_t>(); p.quals = a->quals ? d[3].as<uint8_t>() : nullptr;
+  p.off = d[4].as<int64_t>(); p.table = d[5].as<int32_t>(); p.ad_len = d[6].as<int32_t>(); p.ad_class = d[7].as<int32_t>();
+  p.ad_names = d[8].as<uint8_t>(); p.ad_name_off = d[9].as<int64_t>(); p.idx_cat = d[10].as<uint8_t>(); p.idx_off = d[11].as<int64_t>();
+  p.idx_dest = d[12].as<int32_t>();
+  p.dec = (C3PostDec*)(work.as<uint8_t>() + w_dec); p.len = (int64_t*)(work.as<uint8_t>() + w_len); p.roff = (int64_t*)(work.as<uint8_t>() + w_roff);
+  p.bsum = (long long*)(work.as<uint8_t>() + w_bsum); p.stream_off = offs.as<int64_t>();
+  HIPCHK(hipEventRecord(h->ev_post[0], h->stream));
+  c3k_launch_post_classify(&p, h->stream);
+  HIPCHK(hipEventRecord(h->ev_post[1], h->stream));
+  c3k_launch_post_scan(&p, h->stream);
+  HIPCHK(hipEventRecord(h->ev_post[2], h->stream));
+  HIPCHK(hipGetLastError());
+  std::vector<int64_t> so((size_t)S + 2);
+  HIPCHK(hipMemcpyAsync(so.data(), offs.p, sizeof(int64_t) * (S + 2), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  int64_t need = 0;                                              // the sums come from lengths the rule bounds: anything else is a kernel fault
+  for (int s = 0; s <= S; ++s) { if (so[s] < need) return c3_fail(h, C3_E_HIP, "k_post: stream offsets out of order"); need = so[s]; }
+  if (so[0] != 0 || so[S + 1] < 0 || so[S + 1] > n) return c3_fail(h, C3_E_HIP, "k_post: header out of range");
+  memcpy(stream_off, so.data(), sizeof(int64_t) * (S + 1));
+  *n_kept = so[S + 1];
+  h->ptm = c3_post_timing{};
+  if (need > cap) return c3_fail(h, C3_E_LIMIT, "c3_post_emit: arena too small (bytes needed in stream_off[S])");
+  HIPCHK(out.ensure((size_t)need + 16));
+  p.arena = out.as<uint8_t>();
+  HIPCHK(hipEventRecord(h->ev_post[3], h->stream));
+  c3k_launch_post_emit(&p, h->stream);
+  HIPCHK(hipEventRecord(h->ev_post[4], h->stream));
+  HIPCHK(hipGetLastError());
+  if (need) HIPCHK(hipMemcpyAsync(arena, out.p, (size_t)need, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipEventElapsedTime(&h->ptm.ms_classify, h->ev_post[0], h->ev_post[1]));
+  HIPCHK(hipEventElapsedTime(&h->ptm.ms_scan, h->ev_post[1], h->ev_post[2]));
+  HIPCHK(hipEventElapsedTime(&h->ptm.ms_emit, h->ev_post[3], h->ev_post[4]));
+  h->ptm.n_reads = n; h->ptm.n_kept = so[S + 1]; h->ptm.in_bytes = (int64_t)(nmb + sb * (a->quals ? 2 : 1) + tb); h->ptm.out_bytes = need;
+  h->ptm.ms_call = (float)(dbg_now_ms() - t_call);
+  return C3_E_OK;
+}
+extern "C" int c3_post_emit_timing(c3_handle* h, c3_post_timing* t) {
+  if (!h || !t) return C3_E_ARG;
+  *t = h->ptm;
+  return C3_E_OK;
+}
+
+// sample demultiplexer (paper/Demultiplex_R2C2_reads.py, demultiplex): k_demux over n heads of 300 bytes; the host
+// statement is c3_demux_host (c3_io.cpp), which also holds the checks both share (c3_demux_prepare).
+extern "C" int c3_demux_indexes(c3_handle* h, int n, const char* heads, int n_a, const char* a_cat, const int64_t* a_off,
+                                int n_b, const char* b_cat, const int64_t* b_off, int32_t* win, uint8_t* dist) {
+  if (!h) return C3_E_ARG;
+  if (n < 0 || (n > 0 && (!heads || !win))) return c3_fail(h, C3_E_ARG, "heads / win missing");
+  uint8_t tab[256]; int K = 0; const char* msg = "";
+  const int rc = c3_demux_prepare(n_a, a_cat, a_off, n_b, b_cat, b_off, tab, &K, &msg);
+  if (rc != C3_E_OK) return c3_fail(h, rc, msg);
+  if (n == 0) return C3_E_OK;
+  // meta = Peq [I][K+1] words (bit j of Peq[k][c]: byte j of index k has code c), lengths [I] words, byte codes [256]
+  const int I = n_a + n_b, K1 = K + 1;
+  std::vector<uint32_t> meta((size_t)I * K1 + I + 64, 0u);
+  for (int k = 0; k < I; ++k) {
+    const char* cat = k < n_a ? a_cat : b_cat;
+    const int64_t* off = k < n_a ? a_off + k : b_off + (k - n_a);
+    const int m = (int)(off[1] - off[0]);
+    for (int j = 0; j < m; ++j) meta[(size_t)k * K1 + tab[(uint8_t)cat[off[0] + j]]] |= 1u << j;
+    meta[(size_t)I * K1 + k] = (uint32_t)m;
+  }
+  memcpy(&meta[(size_t)I * K1 + I], tab, 256);
+  const size_t hb = (size_t)n * C3_DEMUX_HEAD, wb = sizeof(int32_t) * 2 * (size_t)n, db = dist ? (size_t)n * I : 0;
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(h->d_dmx_out.ensure(wb + db));
+  HIPCHK(h->d_dmx_heads.put(heads, hb, h->stream)); HIPCHK(h->d_dmx_meta.put(meta.data(), sizeof(uint32_t) * meta.size(), h->stream));
+  uint8_t* d_out = h->d_dmx_out.as<uint8_t>();
+  c3k_launch_demux(h->d_dmx_heads.as<uint8_t>(), n, h->d_dmx_meta.as<uint8_t>(), n_a, n_b, K1, (int32_t*)d_out,
+                   dist ? d_out + wb : nullptr, h->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(win, d_out, wb, hipMemcpyDeviceToHost, h->stream));
+  if (dist) HIPCHK(hipMemcpyAsync(dist, d_out + wb, db, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));      // meta is a host vector of this frame
+  return C3_E_OK;
+}

@@ -1,0 +1,329 @@
+// c3_stream.hip -- the stream handle c3_bgzf (include/c3poa.h): BGZF output and input, FASTQ records parsed on the GPU, and the
+// reader's device stretches.  It shares no state with c3_handle; errors go to the text of c3_last_error(NULL) (ZCHK, host_fail).
+#include "c3_host.h"
+#include "c3_bgzf.h"
+#include "c3_fastq.h"
+#include "c3_inflate.h"
+
+// ---- BGZF output (k_bgzf.hip; host statement c3_bgzf.cpp) ---------------------------------
+// Input goes to the device in chunks of BGZF_CHUNK_BLOCKS blocks: copy in (the pieces land back to back), k_bgzf + k_bgzf_pack,
+// the member sizes back, then one copy of the packed members straight into the caller's buffer.
+#define BGZF_CHUNK_BLOCKS 2048
+
+extern "C" int c3_bgzf_create(int device, c3_bgzf** out) {
+  if (!out) return C3_E_ARG;
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return host_fail(C3_E_NO_DEVICE, "no HIP device: the c3poa HIP backend has no CPU fallback"); }
+  if (device < 0 || device >= ndev) return host_fail(C3_E_ARG, "bad device ordinal");
+  c3_bgzf* z = new c3_bgzf();
+  z->device = device;
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&z->h_sizes, BGZF_CHUNK_BLOCKS * sizeof(int), hipHostMallocDefault);
+  if (e != hipSuccess) { c3_bgzf_destroy(z); return host_fail(C3_E_HIP, hipGetErrorString(e)); }
+  *out = z;
+  return C3_E_OK;
+}
+
+extern "C" void c3_bgzf_destroy(c3_bgzf* z) {
+  if (!z) return;
+  (void)hipSetDevice(z->device);
+  if (z->stream) { (void)hipStreamSynchronize(z->stream); (void)hipStreamDestroy(z->stream); }
+  if (z->h_sizes) (void)hipHostFree(z->h_sizes);
+  if (z->h_mem) (void)hipHostFree(z->h_mem);
+  if (z->h_res) (void)hipHostFree(z->h_res);
+  if (z->copy_stream) { (void)hipStreamSynchronize(z->copy_stream); (void)hipStreamDestroy(z->copy_stream); }
+  if (z->h_hdr) (void)hipHostFree(z->h_hdr);
+  for (auto& f : z->fq) { if (f.h_off) (void)hipHostFree(f.h_off); if (f.h_name_off) (void)hipHostFree(f.h_name_off); }
+  delete z;
+}
+
+// the concatenation of pieces p[0..np) compressed as one text (the writers' formatter slices, c3_io.cpp)
+extern "C" int c3_bgzf_compress_pieces(c3_bgzf* z, const char* const* p, const int64_t* len, int np, char* dst, int64_t cap, int64_t* out_len) {
+  if (!z || !out_len || np < 0 || (np > 0 && (!p || !len))) return host_fail(C3_E_ARG, "c3_bgzf_compress: bad arguments");
+  int64_t n = 0;
+  for (int i = 0; i < np; ++i) { if (len[i] < 0 || (len[i] > 0 && !p[i])) return host_fail(C3_E_ARG, "c3_bgzf_compress: bad piece"); n += len[i]; }
+  if (cap < c3_bgzf_bound(n) || (n > 0 && !dst)) return host_fail(C3_E_ARG, "c3_bgzf_compress: cap < c3_bgzf_bound(n)");
+  *out_len = 0;
+  if (n == 0) return C3_E_OK;
+  ZCHK(hipSetDevice(z->device), "hipSetDevice");
+  const int64_t CH = (int64_t)BGZF_CHUNK_BLOCKS * BGZF_BLOCK;
+  const int64_t first = std::min(CH, n);
+  const int nb_max = (int)((first + BGZF_BLOCK - 1) / BGZF_BLOCK);
+  // k_bgzf reads up to 8 bytes past a chunk's end (realigned dword loads): the input buffer has 256 bytes of slack
+  ZCHK(z->d_in.ensure((size_t)first + 256), "input buffer");
+  ZCHK(z->d_slots.ensure((size_t)nb_max * BGZF_SLOT), "slots");
+  ZCHK(z->d_sizes.ensure((size_t)nb_max * sizeof(int)), "sizes");
+  ZCHK(z->d_packed.ensure((size_t)nb_max * BGZF_MAX_MEMBER), "packed members");
+  int64_t o = 0;
+  int pi = 0; int64_t pin = 0;                                  // piece index / bytes of it already sent
+  for (int64_t c0 = 0; c0 < n; c0 += CH) {
+    const int64_t cn = std::min(CH, n - c0);
+    const int nb = (int)((cn + BGZF_BLOCK - 1) / BGZF_BLOCK);
+    int64_t at = 0;
+    while (at < cn) {
+      while (pi < np && pin == len[pi]) { ++pi; pin = 0; }
+      const int64_t k = std::min(len[pi] - pin, cn - at);
+      ZCHK(hipMemcpyAsync(z->d_in.as<char>() + at, p[pi] + pin, (size_t)k, hipMemcpyHostToDevice, z->stream), "copy in");
+      at += k; pin += k;
+    }
+    c3k_launch_bgzf(z->d_in.as<uint8_t>(), (long long)cn, nb, z->d_slots.as<uint8_t>(), z->d_sizes.as<int>(), z->d_packed.as<uint8_t>(), z->stream);
+    ZCHK(hipGetLastError(), "k_bgzf launch");
+    ZCHK(hipMemcpyAsync(z->h_sizes, z->d_sizes.p, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, z->stream), "k_bgzf");
+    ZCHK(hipStreamSynchronize(z->stream), "k_bgzf");
+    int64_t tot = 0;
+    for (int b = 0; b < nb; ++b) {
+      const int s = z->h_sizes[b];
+      if (s < BGZF_HDR + 13 || s > BGZF_MAX_MEMBER) return host_fail(C3_E_HIP, "k_bgzf: member size out of range");
+      tot += s;
+    }
+    ZCHK(hipMemcpyAsync(dst + o, z->d_packed.p, (size_t)tot, hipMemcpyDeviceToHost, z->stream), "copy out");
+    ZCHK(hipStreamSynchronize(z->stream), "copy out");
+    o += tot;
+  }
+  *out_len = o;
+  return C3_E_OK;
+}
+
+extern "C" int c3_bgzf_compress(c3_bgzf* z, const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len) {
+  if (!z || !out_len || n < 0 || (n > 0 && !src)) return host_fail(C3_E_ARG, "c3_bgzf_compress: bad arguments");
+  return c3_bgzf_compress_pieces(z, &src, &n, 1, dst, cap, out_len);
+}
+
+// ---- BGZF input (k_inflate.hip; host statement c3_inflate.cpp) ----------------------------
+// The host walks the member headers (c3_bgzf_member_at); INFLATE_CHUNK_MEMBERS members at a time go to the device: their
+// bytes as they stand in src, the descriptors, k_inflate, (status, CRC) back, and -- only when every member of the chunk
+// was accepted -- the inflated bytes straight into the caller's buffer.
+#define INFLATE_CHUNK_MEMBERS 4096             // measured 1 024 .. 16 384 per launch: 2 048 leaves 2 waves per SIMD
+static int inflate_chunk() {                                          // C3_INFLATE_CHUNK: measurement hook (tools/inflate_throughput.py)
+  static const int v = [] { const char* e = getenv("C3_INFLATE_CHUNK"); const int x = e ? atoi(e) : 0; return x >= 64 && x <= 16384 ? x : INFLATE_CHUNK_MEMBERS; }();
+  return v;
+}
+
+// nm members of src (all accepted by c3_bgzf_scan) inflated into the caller's dst, or -- d_dst != null -- left on the device
+// at d_dst (the reader's device parse); either way every member's CRC is compared here before the call returns
+static int bgzf_inflate_members(c3_bgzf* z, const char* src, int64_t n, int64_t nm, uint8_t* d_dst, char* dst, int64_t* out_len) {
+  ZCHK(hipSetDevice(z->device), "hipSetDevice");
+  const int CH = inflate_chunk();
+  if (!z->h_mem) ZCHK(hipHostMalloc((void**)&z->h_mem, CH * sizeof(C3BgzfMember), hipHostMallocDefault), "descriptor buffers");
+  if (!z->h_res) ZCHK(hipHostMalloc((void**)&z->h_res, CH * sizeof(int2), hipHostMallocDefault), "descriptor buffers");
+  ZCHK(z->d_mem.ensure(CH * sizeof(C3BgzfMember)), "descriptors");
+  ZCHK(z->d_res.ensure(CH * sizeof(int2)), "statuses");
+  int64_t at = 0, o = 0, done = 0;
+  while (done < nm) {
+    const int k = (int)std::min<int64_t>(CH, nm - done);
+    const int64_t c0 = at;
+    uint32_t oo = 0;
+    for (int i = 0; i < k; ++i) {
+      C3BgzfMember& m = z->h_mem[i];
+      const uint32_t size = c3_bgzf_member_at((const unsigned char*)src, n, at, &m);      // (c3_bgzf_scan accepted them all)
+      m.poff += (uint32_t)(at - c0); m.ooff = oo;
+      oo += m.isize; at += size;
+    }
+    const int64_t cn = at - c0;
+    ZCHK(z->d_in.ensure((size_t)cn + 256), "input buffer");
+    if (!d_dst) ZCHK(z->d_out.ensure((size_t)oo + 256), "output buffer");
+    ZCHK(hipMemcpyAsync(z->d_in.p, src + c0, (size_t)cn, hipMemcpyHostToDevice, z->stream), "copy in");
+    ZCHK(hipMemcpyAsync(z->d_mem.p, z->h_mem, (size_t)k * sizeof(C3BgzfMember), hipMemcpyHostToDevice, z->stream), "copy in");
+    c3k_launch_inflate(z->d_in.as<uint8_t>(), z->d_mem.as<C3BgzfMember>(), k, d_dst ? d_dst + o : z->d_out.as<uint8_t>(), z->d_res.as<int2>(), z->stream);
+    ZCHK(hipGetLastError(), "k_inflate launch");
+    ZCHK(hipMemcpyAsync(z->h_res, z->d_res.p, (size_t)k * sizeof(int2), hipMemcpyDeviceToHost, z->stream), "k_inflate");
+    ZCHK(hipStreamSynchronize(z->stream), "k_inflate");
+    for (int i = 0; i < k; ++i) {
+      int st = z->h_res[i].x;
+      if (st == C3_INF_OK && (uint32_t)z->h_res[i].y != z->h_mem[i].crc) st = C3_INF_CRC;
+      if (st != C3_INF_OK) return c3_bgzf_data_error("c3_bgzf_decompress", done + i, st);
+    }
+    if (oo && !d_dst) {
+      ZCHK(hipMemcpyAsync(dst + o, z->d_out.p, (size_t)oo, hipMemcpyDeviceToHost, z->stream), "copy out");
+      ZCHK(hipStreamSynchronize(z->stream), "copy out");
+    }
+    o += oo; done += k;
+  }
+  *out_len = o;
+  return C3_E_OK;
+}
+
+extern "C" int c3_bgzf_decompress(c3_bgzf* z, const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len) {
+  if (!z || !out_len || n < 0 || (n > 0 && !src)) return host_fail(C3_E_ARG, "c3_bgzf_decompress: bad arguments");
+  *out_len = 0;
+  int64_t nm = 0, ob = 0;
+  const int rc = c3_bgzf_scan(src, n, &nm, &ob);
+  if (rc) return rc;
+  if (cap < ob || (ob > 0 && !dst)) return host_fail(C3_E_ARG, "c3_bgzf_decompress: cap < inflated size (c3_bgzf_scan)");
+  if (nm == 0) return C3_E_OK;
+  return bgzf_inflate_members(z, src, n, nm, nullptr, dst, out_len);
+}
+
+// ---- FASTQ records on the GPU (k_fastq.hip; host statement c3_fastq.cpp) -------------------
+// One parse = three waits: the line count (sizes nl[] and the record tables), the header (sizes the outputs, answers the
+// capacity question before any byte is gathered), the finished arrays.
+static int fq_prepare(c3_bgzf* z) {
+  ZCHK(hipSetDevice(z->device), "hipSetDevice");
+  if (!z->h_hdr) ZCHK(hipHostMalloc((void**)&z->h_hdr, sizeof(C3FqHdr), hipHostMallocDefault), "k_fastq buffers");
+  if (!z->copy_stream) ZCHK(hipStreamCreateWithFlags(&z->copy_stream, hipStreamNonBlocking), "k_fastq buffers");
+  ZCHK(z->d_hdr.ensure(sizeof(C3FqHdr)), "k_fastq buffers");
+  return C3_E_OK;
+}
+
+// the text [lo, lo + n) of sl.text parsed: tables and header on the device, *info filled; no byte gathered yet
+static int fq_parse_device(c3_bgzf* z, c3_bgzf::FqSlot& sl, uint32_t lo, int64_t n, int at_eof, int min_len, c3_fastq_info* info) {
+  memset(info, 0, sizeof *info);
+  sl.n_rec = 0;
+  if (n == 0) return C3_E_OK;
+  const uint32_t hi = lo + (uint32_t)n;
+  const size_t tiles = ((size_t)hi + 65535) / 65536;
+  const uint8_t* buf = sl.text.as<uint8_t>();
+  C3FqHdr* hdr = z->d_hdr.as<C3FqHdr>();
+  ZCHK(z->d_cnt.ensure(tiles * 4 * sizeof(int32_t)), "k_fastq counts");
+  c3k_launch_fastq_count(buf, lo, hi, z->d_cnt.as<int32_t>(), at_eof, hdr, z->stream);
+  ZCHK(hipGetLastError(), "k_fastq_count launch");
+  ZCHK(hipMemcpyAsync(z->h_hdr, hdr, sizeof(C3FqHdr), hipMemcpyDeviceToHost, z->stream), "k_fastq_count");
+  ZCHK(hipStreamSynchronize(z->stream), "k_fastq_count");
+  const int L = z->h_hdr->n_lines, Lv = z->h_hdr->n_lines_v;
+  if (L < 0 || (int64_t)L > n || Lv < L || Lv > L + 1) return host_fail(C3_E_HIP, "k_fastq: line count out of range");
+  const int n_full = Lv / 4, partial = (at_eof && (Lv & 3)) ? 1 : 0;
+  if (n_full == 0 && !partial) return C3_E_OK;                        // no whole record yet: everything stays unconsumed
+  const size_t nr = (size_t)n_full + 1, nb = ((size_t)n_full + 255) / 256;
+  ZCHK(z->d_nl.ensure(((size_t)L + 4) * sizeof(int32_t)), "k_fastq lines");
+  ZCHK(z->d_slen.ensure(nr * sizeof(int32_t)), "k_fastq records");
+  ZCHK(z->d_nlen.ensure(nr * sizeof(int32_t)), "k_fastq records");
+  ZCHK(z->d_bsum.ensure((nb + 1) * 3 * sizeof(long long)), "k_fastq sums");
+  ZCHK(sl.off.ensure(nr * sizeof(int64_t)), "k_fastq offsets");
+  ZCHK(sl.name_off.ensure(nr * sizeof(int64_t)), "k_fastq offsets");
+  ZCHK(sl.src.ensure(nr * sizeof(int4)), "k_fastq sources");
+  c3k_launch_fastq_lines(buf, lo, hi, z->d_cnt.as<int32_t>(), z->d_nl.as<int32_t>(), z->stream);
+  c3k_launch_fastq_records(buf, lo, hi, z->d_nl.as<int32_t>(), L, n_full, partial, min_len, z->d_slen.as<int32_t>(), z->d_nlen.as<int32_t>(),
+                           z->d_bsum.as<long long>(), hdr, sl.off.as<int64_t>(), sl.name_off.as<int64_t>(), sl.src.as<int4>(), z->stream);
+  ZCHK(hipGetLastError(), "k_fastq_records launch");
+  ZCHK(hipMemcpyAsync(z->h_hdr, hdr, sizeof(C3FqHdr), hipMemcpyDeviceToHost, z->stream), "k_fastq_records");
+  ZCHK(hipStreamSynchronize(z->stream), "k_fastq_records");
+  const C3FqHdr& h = *z->h_hdr;
+  if (h.n_records < 0 || h.n_records > n_full || h.n_kept < 0 || h.n_kept > h.n_records || h.consumed < 0 || h.consumed > n ||
+      h.base_bytes < 0 || h.base_bytes > n || h.name_bytes < 0 || h.name_bytes > n) return host_fail(C3_E_HIP, "k_fastq: header out of range");
+  info->n_records = h.n_records; info->n_kept = h.n_kept; info->n_short = h.n_short; info->consumed = h.consumed;
+  info->name_bytes = h.name_bytes; info->base_bytes = h.base_bytes; info->departed = h.departed;
+  sl.n_rec = h.n_kept;
+  return C3_E_OK;
+}
+
+// the kept records of the parse that fq_parse_device just made, gathered into sl.names / sl.seqs / sl.quals (queued, not waited for)
+static int fq_gather_device(c3_bgzf* z, c3_bgzf::FqSlot& sl, const c3_fastq_info& info) {
+  if (info.n_kept == 0) return C3_E_OK;
+  ZCHK(sl.names.ensure((size_t)info.name_bytes + 256), "k_fastq names");
+  ZCHK(sl.seqs.ensure((size_t)info.base_bytes + 256), "k_fastq bases");
+  ZCHK(sl.quals.ensure((size_t)info.base_bytes + 256), "k_fastq qualities");
+  c3k_launch_fastq_gather(sl.text.as<uint8_t>(), sl.src.as<int4>(), sl.off.as<int64_t>(), sl.name_off.as<int64_t>(), (long long)info.n_kept,
+                          sl.names.as<uint8_t>(), sl.seqs.as<uint8_t>(), sl.quals.as<uint8_t>(), z->stream);
+  ZCHK(hipGetLastError(), "k_fastq_gather launch");
+  return C3_E_OK;
+}
+
+extern "C" int c3_fastq_parse(c3_bgzf* z, const char* text, int64_t n, int at_eof, int min_len, char* names, int64_t names_cap,
+                              int64_t* name_off, char* seqs, char* quals, int64_t bases_cap, int64_t* off, int64_t max_records,
+                              c3_fastq_info* info) {
+  int rc = c3_fastq_check_args("c3_fastq_parse", text, n, names, names_cap, name_off, seqs, quals, bases_cap, off, max_records, info);
+  if (rc) return rc;
+  if (!z) return host_fail(C3_E_ARG, "c3_fastq_parse: null handle");
+  if (n == 0) { name_off[0] = 0; off[0] = 0; return C3_E_OK; }
+  if ((rc = fq_prepare(z)) != C3_E_OK) return rc;
+  c3_bgzf::FqSlot& sl = z->fq[0];
+  const uint32_t lo = (uint32_t)((uintptr_t)text & 3u);               // the text keeps its place inside a dword: the kernels see the caller's misalignment
+  ZCHK(sl.text.ensure((size_t)lo + (size_t)n + 256), "k_fastq text");
+  ZCHK(hipMemcpyAsync(sl.text.as<char>() + lo, text, (size_t)n, hipMemcpyHostToDevice, z->stream), "copy in");
+  if ((rc = fq_parse_device(z, sl, lo, n, at_eof, min_len, info)) != C3_E_OK) return rc;
+  if (info->n_kept > max_records || info->name_bytes > names_cap || info->base_bytes > bases_cap) {
+    return host_fail(C3_E_LIMIT, "c3_fastq_parse: capacity too small (needed sizes in info)");
+  }
+  if (info->n_kept == 0) { name_off[0] = 0; off[0] = 0; return C3_E_OK; }
+  if ((rc = fq_gather_device(z, sl, *info)) != C3_E_OK) return rc;
+  const size_t nt = ((size_t)info->n_kept + 1) * sizeof(int64_t);
+  ZCHK(hipMemcpyAsync(off, sl.off.p, nt, hipMemcpyDeviceToHost, z->stream), "k_fastq_gather");
+  ZCHK(hipMemcpyAsync(name_off, sl.name_off.p, nt, hipMemcpyDeviceToHost, z->stream), "k_fastq_gather");
+  if (info->name_bytes) ZCHK(hipMemcpyAsync(names, sl.names.p, (size_t)info->name_bytes, hipMemcpyDeviceToHost, z->stream), "k_fastq_gather");
+  if (info->base_bytes) ZCHK(hipMemcpyAsync(seqs, sl.seqs.p, (size_t)info->base_bytes, hipMemcpyDeviceToHost, z->stream), "k_fastq_gather");
+  if (info->base_bytes) ZCHK(hipMemcpyAsync(quals, sl.quals.p, (size_t)info->base_bytes, hipMemcpyDeviceToHost, z->stream), "k_fastq_gather");
+  ZCHK(hipStreamSynchronize(z->stream), "k_fastq_gather");
+  return C3_E_OK;
+}
+
+// ---- the reader's device stretches (c3_io.cpp; not part of the public interface) ----------
+// Stretch = `carry_len` bytes of the other slot's text from `carry_from` on (the record its end cut), then the inflated
+// members of comp; it stays on the device, is parsed there with min_len 0 (the group rule, min_len included, is the
+// reader's), and the record tables come back (c3_fq_stretch, c3_checks.h).  On return the slot holds the finished records
+// until it is loaded again.
+extern "C" int c3_bgzf_stretch_parse(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, int64_t carry_from, int64_t carry_len,
+                                     int at_eof, c3_fq_stretch* out) {
+  if (!z || !out || slot < 0 || slot > 1 || ncomp < 0 || (ncomp > 0 && !comp) || carry_len < 0) return host_fail(C3_E_ARG, "c3_bgzf_stretch_parse: bad arguments");
+  memset(out, 0, sizeof *out);
+  int64_t nm = 0, ob = 0;
+  int rc = c3_bgzf_scan(comp, ncomp, &nm, &ob);
+  if (rc) return rc;
+  const int64_t total = carry_len + ob;
+  if (total > C3_FASTQ_MAX_TEXT) return host_fail(C3_E_LIMIT, "c3_bgzf_stretch_parse: stretch longer than C3_FASTQ_MAX_TEXT");
+  if ((rc = fq_prepare(z)) != C3_E_OK) return rc;
+  c3_bgzf::FqSlot& sl = z->fq[slot];
+  const c3_bgzf::FqSlot& other = z->fq[slot ^ 1];
+  if (carry_len > 0 && (carry_from < 0 || carry_from + carry_len > other.text_n)) return host_fail(C3_E_ARG, "c3_bgzf_stretch_parse: carry outside the other stretch");
+  ZCHK(sl.text.ensure((size_t)total + 256), "stretch text");
+  sl.text_n = 0;
+  if (carry_len > 0) ZCHK(hipMemcpyAsync(sl.text.p, other.text.as<char>() + carry_from, (size_t)carry_len, hipMemcpyDeviceToDevice, z->stream), "carry");
+  if (nm > 0) {
+    int64_t got = 0;
+    rc = bgzf_inflate_members(z, comp, ncomp, nm, sl.text.as<uint8_t>() + carry_len, nullptr, &got);
+    if (rc) return rc;
+    if (got != ob) return host_fail(C3_E_DATA, "c3_bgzf_stretch_parse: inflated size differs from the headers");
+  }
+  sl.text_n = total;
+  out->text_bytes = total;
+  if ((rc = fq_parse_device(z, sl, 0, total, at_eof, 0, &out->info)) != C3_E_OK) return rc;
+  const int64_t nk = out->info.n_kept;
+  if (nk > 0) {
+    if ((rc = fq_gather_device(z, sl, out->info)) != C3_E_OK) return rc;
+    if (sl.h_cap < (size_t)nk + 1) {
+      if (sl.h_off) (void)hipHostFree(sl.h_off);
+      if (sl.h_name_off) (void)hipHostFree(sl.h_name_off);
+      sl.h_off = sl.h_name_off = nullptr; sl.h_cap = 0;
+      const size_t want = (size_t)nk + 1 + (size_t)nk / 8 + 1024;
+      ZCHK(hipHostMalloc((void**)&sl.h_off, want * sizeof(int64_t), hipHostMallocDefault), "stretch tables");
+      ZCHK(hipHostMalloc((void**)&sl.h_name_off, want * sizeof(int64_t), hipHostMallocDefault), "stretch tables");
+      sl.h_cap = want;
+    }
+    ZCHK(hipMemcpyAsync(sl.h_off, sl.off.p, ((size_t)nk + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, z->stream), "k_fastq_gather");
+    ZCHK(hipMemcpyAsync(sl.h_name_off, sl.name_off.p, ((size_t)nk + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, z->stream), "k_fastq_gather");
+    ZCHK(hipStreamSynchronize(z->stream), "k_fastq_gather");
+    if (sl.h_off[0] != 0 || sl.h_name_off[0] != 0 || sl.h_off[nk] != out->info.base_bytes || sl.h_name_off[nk] != out->info.name_bytes)
+      return host_fail(C3_E_HIP, "k_fastq: offsets do not match the header");
+    out->off = sl.h_off; out->name_off = sl.h_name_off;
+  }
+  return C3_E_OK;
+}
+
+// records [r0, r1) of the slot's stretch copied to the host (names / seqs / quals point at the place of record r0; seqs and
+// quals may be null: names only).  Runs on copy_stream: the other slot may be being loaded on another thread meanwhile.
+extern "C" int c3_bgzf_stretch_fetch(c3_bgzf* z, int slot, int64_t r0, int64_t r1, char* names, char* seqs, char* quals) {
+  if (!z || slot < 0 || slot > 1 || !names) return host_fail(C3_E_ARG, "c3_bgzf_stretch_fetch: bad arguments");
+  const c3_bgzf::FqSlot& sl = z->fq[slot];
+  if (r0 < 0 || r1 < r0 || r1 > sl.n_rec) return host_fail(C3_E_ARG, "c3_bgzf_stretch_fetch: records outside the stretch");
+  if (r0 == r1) return C3_E_OK;
+  ZCHK(hipSetDevice(z->device), "hipSetDevice");
+  const int64_t nb = sl.h_name_off[r0], ne = sl.h_name_off[r1], sb = sl.h_off[r0], se = sl.h_off[r1];
+  if (ne > nb) ZCHK(hipMemcpyAsync(names, sl.names.as<char>() + nb, (size_t)(ne - nb), hipMemcpyDeviceToHost, z->copy_stream), "stretch fetch");
+  if (seqs && se > sb) ZCHK(hipMemcpyAsync(seqs, sl.seqs.as<char>() + sb, (size_t)(se - sb), hipMemcpyDeviceToHost, z->copy_stream), "stretch fetch");
+  if (quals && se > sb) ZCHK(hipMemcpyAsync(quals, sl.quals.as<char>() + sb, (size_t)(se - sb), hipMemcpyDeviceToHost, z->copy_stream), "stretch fetch");
+  ZCHK(hipStreamSynchronize(z->copy_stream), "stretch fetch");
+  return C3_E_OK;
+}
+
+// text [from, from + len) of the slot's stretch copied to the host (a departure: the host parser takes over from there)
+extern "C" int c3_bgzf_stretch_text(c3_bgzf* z, int slot, int64_t from, int64_t len, char* dst) {
+  if (!z || slot < 0 || slot > 1 || from < 0 || len < 0 || (len > 0 && !dst)) return host_fail(C3_E_ARG, "c3_bgzf_stretch_text: bad arguments");
+  const c3_bgzf::FqSlot& sl = z->fq[slot];
+  if (from + len > sl.text_n) return host_fail(C3_E_ARG, "c3_bgzf_stretch_text: bytes outside the stretch");
+  if (len == 0) return C3_E_OK;
+  ZCHK(hipSetDevice(z->device), "stretch text");
+  ZCHK(hipMemcpyAsync(dst, sl.text.as<char>() + from, (size_t)len, hipMemcpyDeviceToHost, z->copy_stream), "stretch text");
+  ZCHK(hipStreamSynchronize(z->copy_stream), "stretch text");
+  return C3_E_OK;
+}

@@ -11,6 +11,8 @@
 // memory, uniform scalar traceback that also counts matches / mismatches / inserted bases.
 #include "c3_dev.h"
 #include "c3_args.h"
+#include "c3_post.h"
+#include "c3_launch.h"
 
 #define WSYNC() __syncthreads()
 

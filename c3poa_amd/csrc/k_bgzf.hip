@@ -22,6 +22,7 @@
 // k_bgzf_pack 10 VGPRs, 20 SGPRs, ScratchSize 0, 32 bytes LDS.
 #include "c3_dev.h"
 #include "c3_bgzf.h"
+#include "c3_launch.h"
 
 struct BgzfLds {
   uint32_t img[BGZF_SLOT / 4];                      // the member (header, deflate bits, trailer)

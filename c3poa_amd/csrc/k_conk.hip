@@ -13,6 +13,7 @@
 // arrive 2-bit packed, 16 per dword, re-aligned once per 16 steps with v_alignbit.
 #include "c3_dev.h"
 #include "c3_args.h"
+#include "c3_launch.h"
 
 
 // One anti-diagonal step of the R cells a lane owns.  The substitution score is a signed-byte table per splint row

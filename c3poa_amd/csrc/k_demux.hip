@@ -16,6 +16,7 @@
 // 2 x 128 indexes and K = 31; occupancy 8 waves/SIMD (the 32-waves/CU cap) up to 20 KiB of LDS per workgroup, 3 at 44 KiB.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "c3_launch.h"
 
 #define DMX_HEAD 300    // bases searched per read (C3_DEMUX_HEAD)
 #define DMX_R 8         // reads per workgroup

@@ -24,6 +24,7 @@
 //       (other waves write its neighbours), nothing outside the dwords that hold text bytes is read.
 #include "c3_dev.h"
 #include "c3_fastq.h"
+#include "c3_launch.h"
 
 #define FQ_TILE 65536u
 #define FQ_WAVES 4

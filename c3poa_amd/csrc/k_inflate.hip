@@ -21,6 +21,7 @@
 // its status; nothing outside [out + ooff, out + ooff + isize) is written and nothing outside the member is read.
 #include "c3_dev.h"
 #include "c3_inflate.h"
+#include "c3_launch.h"
 
 #define INF_WAVES 4
 

@@ -14,6 +14,7 @@
 // order-preserving 64-bit keys with an LDS histogram, peak suppression is an argmax loop.
 #include "c3_dev.h"
 #include "c3_args.h"
+#include "c3_launch.h"
 
 #define PK_T 256
 #define SG_T 1024        /* outputs per LDS tile */

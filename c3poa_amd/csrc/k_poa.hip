@@ -13,6 +13,7 @@
 // two DPP max-scans per 64-column chunk; row maxima (adaptive band) are DPP reductions.
 #include "c3_dev.h"
 #include "c3_args.h"
+#include "c3_launch.h"
 #include <type_traits>
 
 #define WSYNC() __syncthreads()

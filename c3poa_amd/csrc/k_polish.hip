@@ -16,6 +16,7 @@
 //   k_stitch  one wave per read: window consensi concatenated into the final sequence.
 #include "c3_dev.h"
 #include "c3_args.h"
+#include "c3_launch.h"
 #include <algorithm>
 #include <type_traits>
 

@@ -19,6 +19,7 @@
 #include "c3_dev.h"
 #include "c3_args.h"
 #include "c3_post.h"
+#include "c3_launch.h"
 
 #define PO_WAVES 4
 #define PO_LONG 32768                 // read bytes above which the workgroup shares the body segments

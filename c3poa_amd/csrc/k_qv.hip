@@ -30,6 +30,7 @@
 // flat loads for one wave, and the traceback is a scalar loop; the row chain is what a next version would shorten.
 #include "c3_dev.h"
 #include "c3_args.h"
+#include "c3_launch.h"
 
 #define QV_LDS_N 8192
 #define QV_NEG (-(1 << 28))

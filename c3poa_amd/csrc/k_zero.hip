@@ -8,6 +8,7 @@
 // H/E row in LDS, direction bytes in global memory, scalar traceback.
 #include "c3_dev.h"
 #include "c3_args.h"
+#include "c3_launch.h"
 
 #define ZW 4096           // columns kept in the LDS row buffers
 #define WSYNC() __syncthreads()

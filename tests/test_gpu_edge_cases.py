@@ -364,6 +364,45 @@ def test_handle_reuse_across_different_batches():
     assert want[0][-2][0] in (0, 3) and any(c for c in want[1])
 
 
+def test_one_read_calls_leave_the_configuration_alone():
+    """call_peaks, zero_repeats and poa_msa override mdistcutoff / zero / the MSA switch for one call only: a handle with
+    non-default values gives the same batch results before and after them, the refused poa_msa shape included"""
+    from c3poa_amd import _lib
+    rng = np.random.default_rng(21)
+    s = _rand(rng, 2600)
+    d0, d1 = s[:1300], s[700:]                                             # overlapping ends around one splint
+    q0, q1 = _qual(rng, len(d0)), _qual(rng, len(d1))
+    small = list(synth.generate("cfg1", n_reads=9, start=500))
+    zr = d0 + synth.SPLINT1 + d1
+    reads = [(r[1], r[2], r[3]) for r in small] + [(zr, _qual(rng, len(zr)), "+"), (_rand(rng, 900), _qual(rng, 900), "+")]
+
+    def run(h):
+        h.upload([r[0] for r in reads], [r[1] for r in reads], [r[2] for r in reads])
+        h.run()
+        res, cons = h.results()
+        rec = [(int(r["status"]), int(r["n_sub"]), int(r["n_peaks"]), int(r["has_front"]), int(r["has_tail"]), int(r["front_end"]),
+                int(r["tail_beg"]), int(r["cons_len"]), int(r["draft_len"]), int(r["n_win"]),
+                tuple(r["peaks"][:r["n_peaks"]]), tuple(r["sub_beg"][:r["n_sub"]]), tuple(r["sub_end"][:r["n_sub"]])) for r in res]
+        return rec, cons
+
+    h = _lib.Handle(mdistcutoff=700, zero=0); h.set_splints([synth.SPLINT1])
+    want = run(h)
+    assert any(want[1]) and not want[1][-2]                                # zero=0: the one-splint read is not rescued
+    track = h.track(0)
+    assert len(h.call_peaks(track, 50)) >= 1                               # mdistcutoff 50 for this call
+    assert h.zero_repeats(d0, q0, d1, q1, 100) == s[700:1300]              # zero 1, mdistcutoff 100 for this call: the overlap
+    base = _rand(rng, 500)
+    subs = [base, base[:250] + "A" + base[250:], base[:100] + base[101:]]
+    cons, msa = h.poa_msa(subs, out_cons=True, out_msa=True)
+    assert len(msa) == 3 and len(cons) == 1
+    with pytest.raises(_lib.C3Error, match="exactly 2 sequences"):
+        h.poa_msa(subs[:2], out_cons=True, out_msa=True)
+    got = run(h)
+    h.close()
+    assert got[1] == want[1]
+    assert got[0] == want[0]
+
+
 def test_abi_error_paths_return_codes_not_crashes():
     """misuse of the C ABI returns a negative c3_err (and c3_last_error text) -- nothing crosses the boundary as a crash"""
     import ctypes as C

@@ -13,7 +13,7 @@
 #include "../include/c3poa.h"
 
 static std::string g_err;
-void c3_set_host_error(const char* msg) { g_err = msg; }      // the library's c3_api.hip holds this in the real build
+void c3_set_host_error(const char* msg) { g_err = msg; }      // the library's c3_handle.hip holds this in the real build
 
 template <class T> static T* exact(const std::vector<T>& v) {  // a heap block of exactly v.size() elements (never null)
   T* p = (T*)malloc(v.size() * sizeof(T) + (v.empty() ? 1 : 0));
