@@ -31,7 +31,8 @@ EXPORTS = ["c3_default_config", "c3_version", "c3_device_count", "c3_warm_device
            "c3_write_group_bgzf", "c3_write_consensus_fastq_bgzf",
            "c3_bgzf_scan", "c3_bgzf_decompress", "c3_bgzf_decompress_host", "c3_reader_open_inflate", "c3_reader_inflate_wait",
            "c3_fastq_parse", "c3_fastq_parse_host", "c3_reader_parse_on_device", "c3_reader_parse_stats",
-           "c3_post_emit", "c3_post_emit_host", "c3_post_emit_timing"]
+           "c3_post_emit", "c3_post_emit_host", "c3_post_emit_timing",
+           "c3_fasta_parse", "c3_fasta_parse_host", "c3_demux_emit", "c3_demux_emit_host", "c3_demux_emit_timing"]
 
 
 ZERO_MAX_CELLS = 16777216       # c3_default_config's zero_max_cells: largest front * tail the zero-repeat rescue takes
@@ -71,6 +72,25 @@ class Timing(C.Structure):
 
 class QvTiming(C.Structure):
     _fields_ = [("ms_qv", C.c_float)] + [(n, C.c_int64) for n in ("n_reads", "n_pieces", "n_skipped", "band_cells", "edge_hits")]
+
+
+class FastaInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_records", "consumed", "name_bytes", "base_bytes")] + [("departed", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _t in self._fields_}
+
+
+class DemuxInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_records", "n_kept", "consumed", "out_bytes")] + [("departed", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _t in self._fields_}
+
+
+class DemuxTiming(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("ms_parse", "ms_demux", "ms_emit", "ms_call")] + \
+               [(n, C.c_int64) for n in ("n_records", "n_kept", "in_bytes", "out_bytes")]
 
 
 class FastqInfo(C.Structure):
@@ -200,6 +220,13 @@ def load():
     lib.c3_post_emit.argtypes = [vp, C.POINTER(PostArgs), vp, C.c_int64, vp, vp]
     lib.c3_post_emit_host.argtypes = [C.POINTER(PostArgs), vp, C.c_int64, vp, vp]
     lib.c3_post_emit_timing.argtypes = [vp, C.POINTER(PostTiming)]
+    fa = [vp, C.c_int64, C.c_int, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int64, C.POINTER(FastaInfo)]
+    lib.c3_fasta_parse.argtypes = [vp] + fa
+    lib.c3_fasta_parse_host.argtypes = fa
+    de = [vp, C.c_int64, C.c_int] + [C.c_int, vp, vp, vp, vp] * 2 + [vp, C.c_int64, vp, C.c_int64, C.POINTER(DemuxInfo)]
+    lib.c3_demux_emit.argtypes = [vp] + de
+    lib.c3_demux_emit_host.argtypes = de
+    lib.c3_demux_emit_timing.argtypes = [vp, C.POINTER(DemuxTiming)]
     _lib = lib
     return lib
 
@@ -511,6 +538,28 @@ class Handle:
         args, keep, res = _demux_args(heads, set_a, set_b, return_dist)
         self._chk(self.lib.c3_demux_indexes(self.h, *args))
         return res
+
+    def fasta_parse(self, text, at_eof=True, caps=None):
+        """c3_fasta_parse (k_fasta): the FASTA records of `text` as read_fasta reads them (a FastaParse)"""
+        return _fasta_call(lambda *a: self.lib.c3_fasta_parse(self.h, *a), lambda: self.lib.c3_last_error(self.h), text, at_eof, caps)
+
+    def demux_emit(self, text, sets, at_eof=True, cap=None, max_records=None):
+        """c3_demux_emit (k_fasta, k_demux): FASTA text in, the bytes of Indexed_reads.fasta out (a DemuxEmit).  sets: a DemuxSets"""
+        return _demux_emit_call(lambda *a: self.lib.c3_demux_emit(self.h, *a), lambda: self.lib.c3_last_error(self.h), text, sets, at_eof, cap, max_records)
+
+    def demux_emit_raw(self, ptr, n, at_eof, sets, out, hashes):
+        """c3_demux_emit on caller-owned buffers: text at address `ptr` (n bytes), out (uint8 array) and hashes (uint64 array)
+        as capacities.  Returns (rc, info dict); nothing is raised, so that the caller can grow a buffer on E_LIMIT."""
+        info = DemuxInfo()
+        rc = self.lib.c3_demux_emit(self.h, ptr if n else None, n, int(bool(at_eof)), *(sets.args + (out.ctypes.data, out.size, hashes.ctypes.data, hashes.size, C.byref(info))))
+        return rc, info.as_dict()
+
+    def demux_emit_timing(self):
+        """c3_demux_emit_timing: event times of the parse kernels, k_demux and the emit kernels of the last demux_emit, and
+        the call with its copies"""
+        t = DemuxTiming()
+        self._chk(self.lib.c3_demux_emit_timing(self.h, C.byref(t)))
+        return {f[0]: getattr(t, f[0]) for f in DemuxTiming._fields_}
 
     def consensus_qv(self, cons, pieces):
         """c3_consensus_qv (k_qv): Phred+33 QV string of `cons` from pieces = [(seq, qual, mode)], mode QV_GLOBAL /
@@ -1154,6 +1203,150 @@ def fastq_parse_host(text, at_eof=False, min_len=0, text_offset=0, caps=None):
     """c3_fastq_parse_host: the longest prefix of whole strict records of `text`; the host statement of Bgzf.fastq_parse.
     caps = (names_cap, bases_cap, max_records) instead of sizes that always fit; C3Error (code E_LIMIT, .info) when too small"""
     return _fastq_call(load().c3_fastq_parse_host, (), text, at_eof, min_len, text_offset, caps)
+
+
+# ---- Sample demultiplexer, text in / file bytes out (C3POa_demux.py --emit gpu; DESIGN.md 5.7) ----
+FASTA_GUARD = 64                # bytes of 0xA5 either side of every output array of a fasta_parse / demux_emit call
+FASTA_MAX_TEXT = 0x7FF00000
+
+
+def fasta_max_records(n):
+    """records a text of n bytes can hold at most (a record is at least '>' and a terminator; the last may lack it)"""
+    return n // 2 + 1
+
+
+class FastaParse:
+    """result of c3_fasta_parse / c3_fasta_parse_host: info (dict), names / seqs (bytes), name_off / off (int64 arrays of
+    n_records + 1), hashes (uint64 array), guards_intact, untouched_beyond_results"""
+
+    def records(self):
+        no, o = self.name_off, self.off
+        return [(self.names[no[i]:no[i + 1]], self.seqs[o[i]:o[i + 1]]) for i in range(len(o) - 1)]
+
+
+def _guarded(bufs, used):
+    g = FASTA_GUARD
+    intact = all(bool((v[:g] == 0xA5).all()) and bool((v[len(v) - g:] == 0xA5).all()) for v in bufs.values())
+    untouched = all(bool((v[g + used[k]:] == 0xA5).all()) for k, v in bufs.items())
+    return intact, untouched
+
+
+def _fasta_call(fn, err, text, at_eof, caps=None):
+    src = _bytes(text)
+    n = len(src)
+    names_cap, bases_cap, max_records = caps if caps is not None else (n, n, fasta_max_records(n))
+    g = FASTA_GUARD
+    sizes = {"names": names_cap, "seqs": bases_cap, "name_off": 8 * (max_records + 1), "off": 8 * (max_records + 1), "hashes": 8 * max_records}
+    bufs = {k: np.full(v + 2 * g, 0xA5, dtype=np.uint8) for k, v in sizes.items()}
+    ptr = {k: v.ctypes.data + g for k, v in bufs.items()}
+    info = FastaInfo()
+    rc = fn(src if n else None, n, int(bool(at_eof)), ptr["names"], names_cap, ptr["name_off"], ptr["seqs"], bases_cap, ptr["off"],
+            ptr["hashes"], max_records, C.byref(info))
+    out = FastaParse()
+    out.info = info.as_dict()
+    used = dict.fromkeys(sizes, 0)
+    if rc == 0:
+        nr = out.info["n_records"]
+        used = {"names": out.info["name_bytes"], "seqs": out.info["base_bytes"], "name_off": 8 * (nr + 1), "off": 8 * (nr + 1), "hashes": 8 * nr}
+    out.guards_intact, out.untouched_beyond_results = _guarded(bufs, used)
+    if rc != 0:
+        e = C3Error("c3 error %d: %s" % (rc, err().decode()))
+        e.code, e.info, e.guards_intact, e.untouched = rc, out.info, out.guards_intact, out.untouched_beyond_results
+        raise e
+    for k in ("names", "seqs"):
+        setattr(out, k, bufs[k][g:g + used[k]].tobytes())
+    for k in ("name_off", "off"):
+        setattr(out, k, bufs[k][g:g + used[k]].view(np.int64).copy())
+    out.hashes = bufs["hashes"][g:g + used["hashes"]].view(np.uint64).copy()
+    return out
+
+
+def fasta_parse_host(text, at_eof=True, caps=None):
+    """c3_fasta_parse_host: the host statement of Handle.fasta_parse.  caps = (names_cap, bases_cap, max_records) instead of
+    sizes that always fit; C3Error (code E_LIMIT, .info) when too small"""
+    lib = load()
+    return _fasta_call(lib.c3_fasta_parse_host, lambda: lib.c3_last_error(None), text, at_eof, caps)
+
+
+class DemuxSets:
+    """the two index sets of c3_demux_emit: (names, sequences) of the Nextera and the TSO indexes in file order (str or bytes)"""
+
+    def __init__(self, a_names, a_seqs, b_names, b_seqs):
+        self._keep, args = [], []
+        self.max_name = [0, 0]
+        for s, (names, seqs) in enumerate(((a_names, a_seqs), (b_names, b_seqs))):
+            nb, sb = [_b(x) for x in names], [_b(x) for x in seqs]
+            if len(nb) != len(sb):
+                raise ValueError("an index set needs one name per sequence")
+            self.max_name[s] = max([len(x) for x in nb] or [0])
+            so, no = np.zeros(len(sb) + 1, dtype=np.int64), np.zeros(len(nb) + 1, dtype=np.int64)
+            np.cumsum([len(x) for x in sb], out=so[1:])
+            np.cumsum([len(x) for x in nb], out=no[1:])
+            sc, nc = b"".join(sb) + b"\0", b"".join(nb) + b"\0"
+            self._keep += [sc, nc, so, no]
+            args += [len(sb), C.cast(C.c_char_p(sc), C.c_void_p).value, so.ctypes.data, C.cast(C.c_char_p(nc), C.c_void_p).value, no.ctypes.data]
+        self.args = tuple(args)
+
+    def out_bound(self, n):
+        """bytes c3_demux_emit can return at most for a text of n bytes"""
+        return n + (n // 302 + 1) * (5 + self.max_name[0] + self.max_name[1]) + 16
+
+
+class DemuxEmit:
+    """result of c3_demux_emit / c3_demux_emit_host: info (dict), out (bytes), hashes (uint64 array of n_records),
+    guards_intact, untouched_beyond_results"""
+
+
+def _demux_emit_call(fn, err, text, sets, at_eof, cap=None, max_records=None):
+    src = _bytes(text)
+    n = len(src)
+    cap = sets.out_bound(n) if cap is None else int(cap)
+    max_records = fasta_max_records(n) if max_records is None else int(max_records)
+    g = FASTA_GUARD
+    bufs = {"out": np.full(cap + 2 * g, 0xA5, dtype=np.uint8), "hashes": np.full(8 * max_records + 2 * g, 0xA5, dtype=np.uint8)}
+    info = DemuxInfo()
+    rc = fn(src if n else None, n, int(bool(at_eof)), *(sets.args + (bufs["out"].ctypes.data + g, cap, bufs["hashes"].ctypes.data + g, max_records, C.byref(info))))
+    res = DemuxEmit()
+    res.info = info.as_dict()
+    used = {"out": res.info["out_bytes"], "hashes": 8 * res.info["n_records"]} if rc == 0 else {"out": 0, "hashes": 0}
+    res.guards_intact, res.untouched_beyond_results = _guarded(bufs, used)
+    if rc != 0:
+        e = C3Error("c3 error %d: %s" % (rc, err().decode()))
+        e.code, e.info, e.guards_intact, e.untouched = rc, res.info, res.guards_intact, res.untouched_beyond_results
+        raise e
+    res.out = bufs["out"][g:g + used["out"]].tobytes()
+    res.hashes = bufs["hashes"][g:g + used["hashes"]].view(np.uint64).copy()
+    return res
+
+
+def demux_emit_host(text, sets, at_eof=True, cap=None, max_records=None):
+    """c3_demux_emit_host: the host statement of Handle.demux_emit (same arguments and results)"""
+    lib = load()
+    return _demux_emit_call(lib.c3_demux_emit_host, lambda: lib.c3_last_error(None), text, sets, at_eof, cap, max_records)
+
+
+class PinnedBytes:
+    """a page-locked byte buffer from c3_host_alloc (plain memory without a GPU): .arr is a uint8 view, .ptr its address"""
+
+    def __init__(self, nbytes):
+        self.lib = load()
+        self._p = C.c_void_p()
+        if self.lib.c3_host_alloc(int(nbytes) + 64, C.byref(self._p)) != 0:
+            raise MemoryError("c3_host_alloc(%d)" % nbytes)
+        self.ptr, self.size = self._p.value, int(nbytes)
+        self.arr = np.frombuffer((C.c_uint8 * self.size).from_address(self.ptr), dtype=np.uint8)
+
+    def close(self):
+        if self._p:
+            self.arr = None
+            self.lib.c3_host_free(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Bgzf:

@@ -14,6 +14,12 @@ int c3_qv_check(const char* cons, int n, int n_pieces, const char* seq_cat, cons
 int c3_fastq_check_args(const char* who, const char* text, int64_t n, const char* names, int64_t names_cap, const int64_t* name_off,
                         const char* seqs, const char* quals, int64_t bases_cap, const int64_t* off, int64_t max_records,
                         c3_fastq_info* info);                                                                         // c3_fastq.cpp
+int c3_fasta_check_args(const char* who, const char* text, int64_t n, const char* names, int64_t names_cap, const int64_t* name_off,
+                        const char* seqs, int64_t bases_cap, const int64_t* off, const uint64_t* name_hash, int64_t max_records,
+                        c3_fasta_info* info);                                                                         // c3_fasta.cpp
+int c3_demux_emit_check_args(const char* who, const char* text, int64_t n, int n_a, const char* a_names, const int64_t* a_name_off,
+                             int n_b, const char* b_names, const int64_t* b_name_off, const char* out, int64_t cap,
+                             const uint64_t* name_hash, int64_t max_records, c3_demux_info* info);                    // c3_fasta.cpp
 int c3_bgzf_data_error(const char* who, int64_t member, int st);                                                      // c3_inflate.cpp
 
 // the reader's device stretches (c3_stream.hip, called by c3_io.cpp; not part of the public interface)

@@ -159,6 +159,8 @@ extern "C" void c3_destroy(c3_handle* h) {
   for (hipEvent_t ev : {h->ev_dn, h->ev_up[0], h->ev_up[1], h->ev_qv[0], h->ev_qv[1]}) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : h->ev) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : h->ev_post) if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : h->ev_fa) if (ev) (void)hipEventDestroy(ev);
+  if (h->h_fa_hdr) (void)hipHostFree(h->h_fa_hdr);
   if (h->h_tot) (void)hipHostFree(h->h_tot);
   delete h;
 }

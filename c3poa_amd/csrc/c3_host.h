@@ -86,6 +86,8 @@ struct c3_handle {
   DBuf d_qv, s_qv_dirs, s_qv_g, d_qv_cnt, d_gather_qv;                // QV stage: QV arena (like d_cons), direction slots, long-consensus slots, counters, snapshot
   hipEvent_t ev_qv[2] = {nullptr, nullptr}; c3_qv_timing qtm = {}; bool snap_qv = false;
   DBuf d_post[16]; hipEvent_t ev_post[5] = {}; c3_post_timing ptm = {};       // k_post: inputs, descriptors, pass buffers, arena; event times of the last call
+  // k_fasta: text, tables, arenas, output; event times of the last c3_demux_emit; page-locked copy of the device header
+  DBuf d_fa[20]; hipEvent_t ev_fa[10] = {}; c3_demux_timing dtm = {}; struct C3FaHdr* h_fa_hdr = nullptr;
   std::vector<Summary> sum; std::vector<int> work;
   int res_prefix = 0;            // entries of peaks[] / sub_beg[] / sub_end[] that any read of the resident batch uses (0: unknown)
   int peaks_grid = 0; bool debug_msa = false; bool injected = false;

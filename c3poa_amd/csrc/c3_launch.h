@@ -1,13 +1,13 @@
 // c3_launch.h -- the one declaration of every kernel launcher and kernel query.  The host units call through it, and every k_*.hip
 // that defines a launcher includes it too, so a prototype that drifts from its definition fails to compile in the kernel's own
-// translation unit.  Declarations only: the argument blocks are named, not defined (c3_args.h, c3_post.h, c3_inflate.h, c3_fastq.h).
+// translation unit.  Declarations only: the argument blocks are named, not defined (c3_args.h, c3_post.h, c3_inflate.h, c3_fastq.h, c3_fasta.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 struct ConkArgs; struct AdapterArgs; struct PostArgs; struct PeaksArgs; struct PoaArgs; struct PrepArgs; struct WinArgs; struct StitchArgs;
-struct ZeroArgs; struct QvArgs; struct C3BgzfMember; struct C3FqHdr;
+struct ZeroArgs; struct QvArgs; struct C3BgzfMember; struct C3FqHdr; struct FaArgs;
 
 extern "C" {
 void c3k_launch_conk(const ConkArgs*, int, int, int, hipStream_t);                                                          // k_conk.hip
@@ -37,4 +37,10 @@ void c3k_launch_fastq_lines(const uint8_t*, uint32_t, uint32_t, const int32_t*, 
 void c3k_launch_fastq_records(const uint8_t*, uint32_t, uint32_t, const int32_t*, int, int, int, int, int32_t*, int32_t*, long long*,
                               C3FqHdr*, int64_t*, int64_t*, int4*, hipStream_t);
 void c3k_launch_fastq_gather(const uint8_t*, const int4*, const int64_t*, const int64_t*, long long, uint8_t*, uint8_t*, uint8_t*, hipStream_t);
+void c3k_launch_fasta_count(const FaArgs*, hipStream_t);                                                                   // k_fasta.hip
+void c3k_launch_fasta_records(const FaArgs*, int, hipStream_t);
+void c3k_launch_fasta_gather(const FaArgs*, hipStream_t);
+void c3k_launch_demux_heads(const FaArgs*, hipStream_t);
+void c3k_launch_demux_len(const FaArgs*, hipStream_t);
+void c3k_launch_demux_emit(const FaArgs*, hipStream_t);
 }

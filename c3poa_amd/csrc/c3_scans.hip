@@ -1,7 +1,9 @@
 // c3_scans.hip -- side stages that borrow the batch handle's stream: splint / adapter finders over the resident batch,
-// match_index, the post-processing records (k_post) and the sample demultiplexer (k_demux).
+// match_index, the post-processing records (k_post), the sample demultiplexer (k_demux) and its text-in / file-bytes-out path
+// (k_fasta).
 #include "c3_host.h"
 #include "c3_post.h"
+#include "c3_fasta.h"
 
 // splint / strand finder (replaces the blat step of bin/preprocess.py:12-45,61-77): every read of the resident
 // batch is scored against every splint on both strands with the conk kernel; out[i*n_spl*2 + s*2 + rc] =
@@ -162,6 +164,22 @@ extern "C" int c3_post_emit_timing(c3_handle* h, c3_post_timing* t) {
   return C3_E_OK;
 }
 
+// meta of k_demux = Peq [I][K+1] words (bit j of Peq[k][c]: byte j of index k has code c), lengths [I] words, byte codes [256]
+static std::vector<uint32_t> dmx_meta(int n_a, const char* a_cat, const int64_t* a_off, int n_b, const char* b_cat, const int64_t* b_off,
+                                      const uint8_t* tab, int K1) {
+  const int I = n_a + n_b;
+  std::vector<uint32_t> meta((size_t)I * K1 + I + 64, 0u);
+  for (int k = 0; k < I; ++k) {
+    const char* cat = k < n_a ? a_cat : b_cat;
+    const int64_t* off = k < n_a ? a_off + k : b_off + (k - n_a);
+    const int m = (int)(off[1] - off[0]);
+    for (int j = 0; j < m; ++j) meta[(size_t)k * K1 + tab[(uint8_t)cat[off[0] + j]]] |= 1u << j;
+    meta[(size_t)I * K1 + k] = (uint32_t)m;
+  }
+  memcpy(&meta[(size_t)I * K1 + I], tab, 256);
+  return meta;
+}
+
 // sample demultiplexer (paper/Demultiplex_R2C2_reads.py, demultiplex): k_demux over n heads of 300 bytes; the host
 // statement is c3_demux_host (c3_io.cpp), which also holds the checks both share (c3_demux_prepare).
 extern "C" int c3_demux_indexes(c3_handle* h, int n, const char* heads, int n_a, const char* a_cat, const int64_t* a_off,
@@ -172,17 +190,8 @@ extern "C" int c3_demux_indexes(c3_handle* h, int n, const char* heads, int n_a,
   const int rc = c3_demux_prepare(n_a, a_cat, a_off, n_b, b_cat, b_off, tab, &K, &msg);
   if (rc != C3_E_OK) return c3_fail(h, rc, msg);
   if (n == 0) return C3_E_OK;
-  // meta = Peq [I][K+1] words (bit j of Peq[k][c]: byte j of index k has code c), lengths [I] words, byte codes [256]
   const int I = n_a + n_b, K1 = K + 1;
-  std::vector<uint32_t> meta((size_t)I * K1 + I + 64, 0u);
-  for (int k = 0; k < I; ++k) {
-    const char* cat = k < n_a ? a_cat : b_cat;
-    const int64_t* off = k < n_a ? a_off + k : b_off + (k - n_a);
-    const int m = (int)(off[1] - off[0]);
-    for (int j = 0; j < m; ++j) meta[(size_t)k * K1 + tab[(uint8_t)cat[off[0] + j]]] |= 1u << j;
-    meta[(size_t)I * K1 + k] = (uint32_t)m;
-  }
-  memcpy(&meta[(size_t)I * K1 + I], tab, 256);
+  const std::vector<uint32_t> meta = dmx_meta(n_a, a_cat, a_off, n_b, b_cat, b_off, tab, K1);
   const size_t hb = (size_t)n * C3_DEMUX_HEAD, wb = sizeof(int32_t) * 2 * (size_t)n, db = dist ? (size_t)n * I : 0;
   HIPCHK(hipSetDevice(h->cfg.device));
   HIPCHK(h->d_dmx_out.ensure(wb + db));
@@ -194,5 +203,173 @@ extern "C" int c3_demux_indexes(c3_handle* h, int n, const char* heads, int n_a,
   HIPCHK(hipMemcpyAsync(win, d_out, wb, hipMemcpyDeviceToHost, h->stream));
   if (dist) HIPCHK(hipMemcpyAsync(dist, d_out + wb, db, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));      // meta is a host vector of this frame
+  return C3_E_OK;
+}
+
+// ---- FASTA text parsed, demultiplexed and formatted on the device (k_fasta.hip; host statements c3_fasta.cpp) ----
+// One parse = two waits: the terminator count (sizes nl[] and the line and record tables), the header (sizes the arenas and
+// answers the capacity question before any byte is gathered).  c3_demux_emit waits once more for the output size.
+enum { FA_TEXT, FA_CNT, FA_NL, FA_LSE, FA_LDST, FA_BSUM, FA_HDR, FA_OFF, FA_NOFF, FA_RECL, FA_HASH, FA_NAMES, FA_SEQS, FA_KREC, FA_ROFF,
+       FA_OUT, FA_ANAMES, FA_ANO, FA_BNAMES, FA_BNO, FA_N };
+static_assert(FA_N <= sizeof(c3_handle::d_fa) / sizeof(DBuf), "c3_handle::d_fa is too short");
+
+static int fa_read_hdr(c3_handle* h) {
+  HIPCHK(hipMemcpyAsync(h->h_fa_hdr, h->d_fa[FA_HDR].p, sizeof(C3FaHdr), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return C3_E_OK;
+}
+
+// the text (n > 0) uploaded and parsed: line and record tables and the header on the device and in h->h_fa_hdr; no byte gathered
+// yet.  kept: krec[] and n_kept as well.
+static int fa_parse_device(c3_handle* h, const char* text, int64_t n, int at_eof, int kept, FaArgs* a) {
+  memset(a, 0, sizeof *a);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (!h->h_fa_hdr) HIPCHK(hipHostMalloc((void**)&h->h_fa_hdr, sizeof(C3FaHdr), hipHostMallocDefault));
+  for (hipEvent_t& ev : h->ev_fa) if (!ev) HIPCHK(hipEventCreate(&ev));
+  DBuf* d = h->d_fa;
+  const size_t tiles = ((size_t)n + 65535) / 65536;
+  HIPCHK(d[FA_TEXT].ensure((size_t)n + 256)); HIPCHK(d[FA_HDR].ensure(sizeof(C3FaHdr))); HIPCHK(d[FA_CNT].ensure(tiles * 4 * sizeof(int32_t)));
+  HIPCHK(hipMemcpyAsync(d[FA_TEXT].p, text, (size_t)n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(d[FA_HDR].p, 0xFF, 12, h->stream));           // first_high, first_headless: none; rec_of_high: -1
+  a->buf = d[FA_TEXT].as<uint8_t>(); a->hi = (uint32_t)n; a->at_eof = at_eof ? 1 : 0;
+  a->cnt = d[FA_CNT].as<int32_t>(); a->hdr = d[FA_HDR].as<C3FaHdr>();
+  HIPCHK(hipEventRecord(h->ev_fa[0], h->stream));
+  c3k_launch_fasta_count(a, h->stream);
+  HIPCHK(hipEventRecord(h->ev_fa[1], h->stream));
+  HIPCHK(hipGetLastError());
+  int rc = fa_read_hdr(h);
+  if (rc) return rc;
+  const int64_t T = h->h_fa_hdr->n_term;
+  if (T < 0 || T > n) return c3_fail(h, C3_E_HIP, "k_fasta: terminator count out of range");
+  const size_t nl = (size_t)T + 1, nb = (nl + 255) / 256;
+  HIPCHK(d[FA_NL].ensure((nl + 4) * sizeof(int32_t))); HIPCHK(d[FA_LSE].ensure((nl + 1) * sizeof(int32_t))); HIPCHK(d[FA_LDST].ensure((nl + 1) * sizeof(uint32_t)));
+  HIPCHK(d[FA_BSUM].ensure((nb + 1) * 3 * sizeof(long long)));
+  HIPCHK(d[FA_OFF].ensure((nl + 2) * sizeof(int64_t))); HIPCHK(d[FA_NOFF].ensure((nl + 2) * sizeof(int64_t)));
+  HIPCHK(d[FA_RECL].ensure((nl + 2) * sizeof(int32_t))); HIPCHK(d[FA_HASH].ensure((nl + 2) * sizeof(uint64_t)));
+  if (kept) HIPCHK(d[FA_KREC].ensure((nl + 2) * sizeof(int32_t)));
+  a->nl = d[FA_NL].as<int32_t>(); a->T = (int32_t)T; a->lse = d[FA_LSE].as<int32_t>(); a->ldst = d[FA_LDST].as<uint32_t>();
+  a->bsum = d[FA_BSUM].as<long long>(); a->off = d[FA_OFF].as<int64_t>(); a->name_off = d[FA_NOFF].as<int64_t>();
+  a->rec_line = d[FA_RECL].as<int32_t>(); a->hash = d[FA_HASH].as<uint64_t>(); a->krec = d[FA_KREC].as<int32_t>();
+  HIPCHK(hipEventRecord(h->ev_fa[2], h->stream));
+  c3k_launch_fasta_records(a, kept, h->stream);
+  HIPCHK(hipEventRecord(h->ev_fa[3], h->stream));
+  HIPCHK(hipGetLastError());
+  if ((rc = fa_read_hdr(h)) != C3_E_OK) return rc;
+  const C3FaHdr& f = *h->h_fa_hdr;
+  if (f.n_headers < 0 || f.n_headers > (int64_t)nl || f.n_records < 0 || f.n_records > f.n_headers || f.consumed < 0 || f.consumed > n ||
+      f.name_bytes < 0 || f.name_bytes > n || f.base_bytes < 0 || f.base_bytes > n || f.departed < 0 || f.departed > 2 ||
+      f.n_kept < 0 || f.n_kept > f.n_records)
+    return c3_fail(h, C3_E_HIP, "k_fasta: header out of range");
+  a->n_records = f.n_records; a->n_kept = f.n_kept;
+  return C3_E_OK;
+}
+
+// names and sequences of the delivered records gathered into the arenas (queued, not waited for)
+static int fa_gather_device(c3_handle* h, FaArgs* a) {
+  const C3FaHdr& f = *h->h_fa_hdr;
+  HIPCHK(h->d_fa[FA_NAMES].ensure((size_t)f.name_bytes + 256)); HIPCHK(h->d_fa[FA_SEQS].ensure((size_t)f.base_bytes + 256));
+  a->names = h->d_fa[FA_NAMES].as<uint8_t>(); a->seqs = h->d_fa[FA_SEQS].as<uint8_t>();
+  c3k_launch_fasta_gather(a, h->stream);
+  HIPCHK(hipGetLastError());
+  return C3_E_OK;
+}
+
+extern "C" int c3_fasta_parse(c3_handle* h, const char* text, int64_t n, int at_eof, char* names, int64_t names_cap, int64_t* name_off,
+                              char* seqs, int64_t bases_cap, int64_t* off, uint64_t* name_hash, int64_t max_records, c3_fasta_info* info) {
+  int rc = c3_fasta_check_args("c3_fasta_parse", text, n, names, names_cap, name_off, seqs, bases_cap, off, name_hash, max_records, info);
+  if (!h) return rc ? rc : host_fail(C3_E_ARG, "c3_fasta_parse: null handle");
+  if (rc) return c3_fail(h, rc, c3_last_error(nullptr));
+  if (n == 0) { name_off[0] = 0; off[0] = 0; return C3_E_OK; }
+  FaArgs a;
+  if ((rc = fa_parse_device(h, text, n, at_eof, 0, &a)) != C3_E_OK) return rc;
+  const C3FaHdr& f = *h->h_fa_hdr;
+  info->n_records = f.n_records; info->consumed = f.consumed; info->name_bytes = f.name_bytes; info->base_bytes = f.base_bytes; info->departed = f.departed;
+  if (f.n_records > max_records || f.name_bytes > names_cap || f.base_bytes > bases_cap)
+    return c3_fail(h, C3_E_LIMIT, "c3_fasta_parse: capacity too small (needed sizes in info)");
+  if (f.n_records == 0) { name_off[0] = 0; off[0] = 0; return C3_E_OK; }
+  if ((rc = fa_gather_device(h, &a)) != C3_E_OK) return rc;
+  const size_t R = (size_t)f.n_records;
+  HIPCHK(hipMemcpyAsync(off, a.off, (R + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(name_off, a.name_off, (R + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(name_hash, a.hash, R * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+  if (f.name_bytes) HIPCHK(hipMemcpyAsync(names, a.names, (size_t)f.name_bytes, hipMemcpyDeviceToHost, h->stream));
+  if (f.base_bytes) HIPCHK(hipMemcpyAsync(seqs, a.seqs, (size_t)f.base_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return C3_E_OK;
+}
+
+extern "C" int c3_demux_emit(c3_handle* h, const char* text, int64_t n, int at_eof,
+                             int n_a, const char* a_cat, const int64_t* a_off, const char* a_names, const int64_t* a_name_off,
+                             int n_b, const char* b_cat, const int64_t* b_off, const char* b_names, const int64_t* b_name_off,
+                             char* out, int64_t cap, uint64_t* name_hash, int64_t max_records, c3_demux_info* info) {
+  const double t_call = dbg_now_ms();
+  int rc = c3_demux_emit_check_args("c3_demux_emit", text, n, n_a, a_names, a_name_off, n_b, b_names, b_name_off, out, cap, name_hash, max_records, info);
+  if (!h) return rc ? rc : host_fail(C3_E_ARG, "c3_demux_emit: null handle");
+  if (rc) return c3_fail(h, rc, c3_last_error(nullptr));
+  uint8_t tab[256]; int K = 0; const char* msg = "";
+  if ((rc = c3_demux_prepare(n_a, a_cat, a_off, n_b, b_cat, b_off, tab, &K, &msg)) != C3_E_OK) return c3_fail(h, rc, msg);
+  h->dtm = c3_demux_timing{};
+  if (n == 0) return C3_E_OK;
+  FaArgs a;
+  if ((rc = fa_parse_device(h, text, n, at_eof, 1, &a)) != C3_E_OK) return rc;
+  const C3FaHdr& f = *h->h_fa_hdr;
+  const int64_t R = f.n_records, nk = f.n_kept;
+  info->n_records = R; info->n_kept = nk; info->consumed = f.consumed; info->departed = f.departed;
+  if (R > max_records) return c3_fail(h, C3_E_LIMIT, "c3_demux_emit: more records than max_records (needed sizes in info)");
+  if (nk > INT32_MAX) return c3_fail(h, C3_E_LIMIT, "c3_demux_emit: too many records in one text");
+  float ms[5] = {0, 0, 0, 0, 0};
+  if (nk > 0) {
+    DBuf* d = h->d_fa;
+    const int I = n_a + n_b, K1 = K + 1;
+    const std::vector<uint32_t> meta = dmx_meta(n_a, a_cat, a_off, n_b, b_cat, b_off, tab, K1);
+    const size_t anb = (size_t)a_name_off[n_a], bnb = (size_t)b_name_off[n_b];
+    HIPCHK(h->d_dmx_heads.ensure((size_t)nk * C3_DEMUX_HEAD + 16)); HIPCHK(h->d_dmx_out.ensure(sizeof(int32_t) * 2 * (size_t)nk));
+    HIPCHK(h->d_dmx_meta.put(meta.data(), sizeof(uint32_t) * meta.size(), h->stream));
+    HIPCHK(d[FA_ANAMES].ensure(anb + 16)); HIPCHK(d[FA_BNAMES].ensure(bnb + 16));
+    if (anb) HIPCHK(hipMemcpyAsync(d[FA_ANAMES].p, a_names, anb, hipMemcpyHostToDevice, h->stream));
+    if (bnb) HIPCHK(hipMemcpyAsync(d[FA_BNAMES].p, b_names, bnb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(d[FA_ANO].put(a_name_off, sizeof(int64_t) * (size_t)(n_a + 1), h->stream)); HIPCHK(d[FA_BNO].put(b_name_off, sizeof(int64_t) * (size_t)(n_b + 1), h->stream));
+    HIPCHK(d[FA_ROFF].ensure(sizeof(int64_t) * ((size_t)nk + 1)));
+    a.heads = h->d_dmx_heads.as<uint8_t>(); a.win = h->d_dmx_out.as<int32_t>(); a.roff = d[FA_ROFF].as<int64_t>();
+    a.a_names = d[FA_ANAMES].as<uint8_t>(); a.a_no = d[FA_ANO].as<int64_t>(); a.b_names = d[FA_BNAMES].as<uint8_t>(); a.b_no = d[FA_BNO].as<int64_t>();
+    HIPCHK(hipEventRecord(h->ev_fa[4], h->stream));
+    if ((rc = fa_gather_device(h, &a)) != C3_E_OK) return rc;
+    c3k_launch_demux_heads(&a, h->stream);
+    HIPCHK(hipEventRecord(h->ev_fa[5], h->stream));
+    c3k_launch_demux(a.heads, (int)nk, h->d_dmx_meta.as<uint8_t>(), n_a, n_b, K1, h->d_dmx_out.as<int32_t>(), nullptr, h->stream);
+    HIPCHK(hipEventRecord(h->ev_fa[6], h->stream));
+    c3k_launch_demux_len(&a, h->stream);
+    HIPCHK(hipEventRecord(h->ev_fa[7], h->stream));
+    HIPCHK(hipGetLastError());
+    if ((rc = fa_read_hdr(h)) != C3_E_OK) return rc;           // (meta is a host vector of this frame: the wait covers its upload)
+    const int64_t need = f.out_bytes;
+    // a record is at least its five literals and 301 sequence bytes, at most everything the text holds plus two index names
+    if (need < nk * (C3_DEMUX_HEAD + 6) || need > n + nk * (int64_t)(5 + anb + bnb)) return c3_fail(h, C3_E_HIP, "k_fasta: output size out of range");
+    info->out_bytes = need;
+    if (need > cap) return c3_fail(h, C3_E_LIMIT, "c3_demux_emit: out too small (bytes needed in info)");
+    HIPCHK(d[FA_OUT].ensure((size_t)need + 16));
+    a.out = d[FA_OUT].as<uint8_t>();
+    HIPCHK(hipEventRecord(h->ev_fa[8], h->stream));
+    c3k_launch_demux_emit(&a, h->stream);
+    HIPCHK(hipEventRecord(h->ev_fa[9], h->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, a.out, (size_t)need, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (R > 0) HIPCHK(hipMemcpyAsync(name_hash, a.hash, (size_t)R * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  float t01, t23;
+  HIPCHK(hipEventElapsedTime(&t01, h->ev_fa[0], h->ev_fa[1])); HIPCHK(hipEventElapsedTime(&t23, h->ev_fa[2], h->ev_fa[3]));
+  if (nk > 0) {
+    HIPCHK(hipEventElapsedTime(&ms[0], h->ev_fa[4], h->ev_fa[5])); HIPCHK(hipEventElapsedTime(&ms[1], h->ev_fa[5], h->ev_fa[6]));
+    HIPCHK(hipEventElapsedTime(&ms[2], h->ev_fa[6], h->ev_fa[7])); HIPCHK(hipEventElapsedTime(&ms[3], h->ev_fa[8], h->ev_fa[9]));
+  }
+  h->dtm.ms_parse = t01 + t23 + ms[0]; h->dtm.ms_demux = ms[1]; h->dtm.ms_emit = ms[2] + ms[3];
+  h->dtm.n_records = R; h->dtm.n_kept = nk; h->dtm.in_bytes = n; h->dtm.out_bytes = info->out_bytes;
+  h->dtm.ms_call = (float)(dbg_now_ms() - t_call);
+  return C3_E_OK;
+}
+extern "C" int c3_demux_emit_timing(c3_handle* h, c3_demux_timing* t) {
+  if (!h || !t) return C3_E_ARG;
+  *t = h->dtm;
   return C3_E_OK;
 }

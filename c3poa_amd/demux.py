@@ -8,6 +8,7 @@ is k_demux (c3_demux_indexes) in batches of bounded size; c3_demux_host is its h
 demultiplex and write_fasta_file keep the reference's function shapes.
 """
 import os
+import sys
 
 import numpy as np
 
@@ -113,3 +114,114 @@ def write_fasta_file(path, reads):
         items = list(reads.items())
         for i in range(0, len(items), 4096):
             out.write("".join(">%s\n%s\n" % kv for kv in items[i:i + 4096]))
+
+
+# ---- --emit gpu: FASTA text up, Indexed_reads.fasta bytes down (c3_demux_emit) --------------------------
+EMIT_CHUNK = 64 << 20   # bytes of input per device call (--demux-chunk); far below C3_FASTA_MAX_TEXT, large enough that the
+                        # three waits of a call do not show
+
+
+def _plain(strings):
+    """no byte >= 0x80 and no '|': what the device path needs of index names and sequences"""
+    return all(ord(c) < 0x80 and c != "|" for s in strings for c in s)
+
+
+def run_emit_gpu(input_fasta, output_path, nextera_file, tso_file, chunk=EMIT_CHUNK, handle=None, stats=None):
+    """C3POa_demux.py --emit gpu: the input file goes to the device in chunks of raw bytes, each chunk is parsed, searched
+    and formatted there (c3_demux_emit) and the returned bytes are appended to <output_path>/Indexed_reads.fasta.part, renamed
+    at the end.  No Python loop over reads.  Returns (reads written, reads in the file), or None after a one-line note on
+    stderr where only the host path gives the reference's result (nothing is left behind then); stats (a dict) receives
+    chunks, records_device and fallback.  Index files are loaded by load_indexes: the same DemuxErrors, before any GPU work."""
+    stats = {} if stats is None else stats
+    stats.update(chunks=0, records_device=0, fallback=None)
+    a_names, a_seqs = load_indexes(nextera_file)
+    b_names, b_seqs = load_indexes(tso_file)
+    final = os.path.join(output_path, "Indexed_reads.fasta")
+    part = final + ".part"
+    made_dir = [False]
+    state = {"out": None, "buf": None, "own": None}
+
+    def fallback(reason):
+        if state["out"] is not None:
+            state["out"].close()
+            state["out"] = None
+        if os.path.exists(part):
+            os.remove(part)
+        if made_dir[0]:
+            try:
+                os.rmdir(output_path)
+            except OSError:
+                pass
+        stats["fallback"] = reason
+        print("C3POa_demux: --emit gpu falls back to the host path: %s" % reason, file=sys.stderr)
+        return None
+
+    if not _plain(a_names + a_seqs + b_names + b_seqs):
+        return fallback("an index name or sequence holds '|' or a byte >= 0x80")
+    sets = _lib.DemuxSets(a_names, a_seqs, b_names, b_seqs)
+    size = max(1, min(int(chunk), _lib.FASTA_MAX_TEXT))
+    if handle is None:
+        handle = state["own"] = _lib.Handle(device=0)
+    try:
+        buf = state["buf"] = _lib.PinnedBytes(size)
+        out = np.empty(sets.out_bound(size), dtype=np.uint8)
+        hashes = np.empty(size // 64 + 1024, dtype=np.uint64)
+        collected, written, have, at_eof = [], 0, 0, False
+        with open(input_fasta, "rb") as f:
+            while not at_eof:
+                got = f.readinto(memoryview(buf.arr)[have:size]) if have < size else 0
+                at_eof = have < size and got < size - have
+                n = have + got
+                while True:
+                    rc, info = handle.demux_emit_raw(buf.ptr, n, at_eof, sets, out, hashes)
+                    if rc == _lib.E_LIMIT and info["n_records"] > hashes.size:
+                        hashes = np.empty(info["n_records"] + info["n_records"] // 8, dtype=np.uint64)
+                    elif rc == _lib.E_LIMIT and info["out_bytes"] > out.size:
+                        out = np.empty(info["out_bytes"] + info["out_bytes"] // 8, dtype=np.uint8)
+                    else:
+                        break
+                if rc != 0:
+                    return fallback("c3_demux_emit: %s" % handle.lib.c3_last_error(handle.h).decode())
+                if info["departed"]:
+                    return fallback("a byte >= 0x80 in the input" if info["departed"] == 1 else "a sequence line in front of the first header")
+                stats["chunks"] += 1
+                stats["records_device"] += info["n_records"]
+                written += info["n_kept"]
+                if info["n_records"]:
+                    collected.append(hashes[:info["n_records"]].copy())
+                if info["out_bytes"]:
+                    if state["out"] is None:
+                        made_dir[0] = not os.path.isdir(output_path)
+                        os.makedirs(output_path, exist_ok=True)
+                        state["out"] = open(part, "wb")
+                    state["out"].write(memoryview(out)[:info["out_bytes"]])
+                used = info["consumed"]
+                if used == 0 and not at_eof and n == size:           # one record longer than the chunk: grow it
+                    if size >= _lib.FASTA_MAX_TEXT:
+                        return fallback("a record longer than C3_FASTA_MAX_TEXT")
+                    size = min(2 * size, _lib.FASTA_MAX_TEXT)
+                    grown = _lib.PinnedBytes(size)
+                    grown.arr[:n] = buf.arr[:n]
+                    buf.close()
+                    buf = state["buf"] = grown
+                    out = np.empty(sets.out_bound(size), dtype=np.uint8)
+                elif used:
+                    buf.arr[:n - used] = buf.arr[used:n]
+                have = n - used
+        allh = np.concatenate(collected) if collected else np.empty(0, dtype=np.uint64)
+        if np.unique(allh).size != allh.size:
+            return fallback("repeated headers in the input (the host path keeps one record per header)")
+        if state["out"] is None:
+            os.makedirs(output_path, exist_ok=True)
+            state["out"] = open(part, "wb")
+        state["out"].close()
+        state["out"] = None
+        os.replace(part, final)
+        return written, int(allh.size)
+    finally:
+        if state["out"] is not None:
+            state["out"].close()
+        if state["buf"] is not None:
+            state["buf"].close()
+        if state["own"] is not None:
+            state["own"].close()

@@ -504,6 +504,49 @@ int c3_post_emit(c3_handle* h, const c3_post_args* a, char* arena, int64_t cap, 
 int c3_post_emit_host(const c3_post_args* a, char* arena, int64_t cap, int64_t* stream_off, int64_t* n_kept);
 int c3_post_emit_timing(c3_handle* h, c3_post_timing* t);
 
+/* ---- Sample demultiplexer, text in / file bytes out (C3POa_demux.py --emit gpu) ----
+ * FASTA text as read_fasta of paper/Demultiplex_R2C2_reads.py reads it, for ASCII bytes (the rule is c3poa_amd/csrc/c3_fasta.h):
+ * a line ends at every '\n' and every '\r' (the last line may lack one); the bytes 9..13 and 28..32 are stripped at its end,
+ * nothing at its front; a stripped-empty line is ignored; a line whose first byte is '>' opens a record, its name being
+ * everything behind the '>' (may be empty); every other line is appended, stripped, to the sequence of the open record (which
+ * may stay empty).
+ * With at_eof == 0 the last record of the text is left unconsumed (its sequence may continue): info->consumed is the offset of
+ * the last header line's first byte, 0 when the text holds no header; with at_eof != 0 everything is consumed.  A text starts
+ * at the start of the file or at a header line.  DEPARTURES deliver only the records that lie wholly in front of the first
+ * offending byte, with consumed at the header line of the first record not delivered: departed = 1, a byte >= 0x80;
+ * departed = 2, a non-blank sequence line in front of the first header (nothing delivered, consumed = 0).
+ * c3_fasta_parse delivers every record: names / name_off[n_records + 1], seqs / off[n_records + 1] as in c3_host_batch, and
+ * name_hash[n_records], the 64-bit FNV-1a hash of each name.  It runs k_fasta on the handle's device; c3_fasta_parse_host is
+ * its host statement.  n_records > max_records, name_bytes > names_cap or base_bytes > bases_cap return C3_E_LIMIT with the
+ * needed sizes in info and nothing written; n > C3_FASTA_MAX_TEXT returns C3_E_LIMIT; null arguments and a null handle return
+ * C3_E_ARG (text may be null when n == 0); n == 0 is success with all counts zero.
+ * c3_demux_emit runs parse -> heads -> k_demux -> format on the device and returns the bytes of Indexed_reads.fasta for the
+ * delivered records in out: per record with more than C3_DEMUX_HEAD sequence bytes, in input order,
+ * '>' name '|' A '_' B '\n' sequence '\n', A / B being the name of the winning index of each set (c3_demux_indexes) or empty;
+ * shorter records are dropped.  Index sets as in c3_demux_indexes (same limits, same error texts), their names as
+ * a_names / a_name_off[n_a + 1] and b_names / b_name_off[n_b + 1].  name_hash[n_records] as above, for every delivered record,
+ * kept or not.  out_bytes > cap returns C3_E_LIMIT with info->out_bytes = the need and out left alone; n_records > max_records
+ * likewise.  c3_demux_emit_host is the host statement, byte for byte.  Errors of the host statements through
+ * c3_last_error(NULL). */
+#define C3_FASTA_MAX_TEXT 0x7FF00000
+typedef struct { int64_t n_records, consumed, name_bytes, base_bytes; int32_t departed; } c3_fasta_info;
+typedef struct { int64_t n_records, n_kept, consumed, out_bytes; int32_t departed; } c3_demux_info;
+int c3_fasta_parse(c3_handle* h, const char* text, int64_t n, int at_eof, char* names, int64_t names_cap, int64_t* name_off,
+                   char* seqs, int64_t bases_cap, int64_t* off, uint64_t* name_hash, int64_t max_records, c3_fasta_info* info);
+int c3_fasta_parse_host(const char* text, int64_t n, int at_eof, char* names, int64_t names_cap, int64_t* name_off,
+                        char* seqs, int64_t bases_cap, int64_t* off, uint64_t* name_hash, int64_t max_records, c3_fasta_info* info);
+int c3_demux_emit(c3_handle* h, const char* text, int64_t n, int at_eof,
+                  int n_a, const char* a_cat, const int64_t* a_off, const char* a_names, const int64_t* a_name_off,
+                  int n_b, const char* b_cat, const int64_t* b_off, const char* b_names, const int64_t* b_name_off,
+                  char* out, int64_t cap, uint64_t* name_hash, int64_t max_records, c3_demux_info* info);
+int c3_demux_emit_host(const char* text, int64_t n, int at_eof,
+                       int n_a, const char* a_cat, const int64_t* a_off, const char* a_names, const int64_t* a_name_off,
+                       int n_b, const char* b_cat, const int64_t* b_off, const char* b_names, const int64_t* b_name_off,
+                       char* out, int64_t cap, uint64_t* name_hash, int64_t max_records, c3_demux_info* info);
+/* kernel times of the last c3_demux_emit on the handle (hipEvents on its stream) and of the call with its copies */
+typedef struct { float ms_parse, ms_demux, ms_emit, ms_call; int64_t n_records, n_kept, in_bytes, out_bytes; } c3_demux_timing;
+int c3_demux_emit_timing(c3_handle* h, c3_demux_timing* t);
+
 #ifdef __cplusplus
 }
 #endif
