@@ -63,6 +63,11 @@ def parse_args(argv=None):
     parser.add_argument("--consensus-fastq", dest="consensus_fastq", action="store_true", default=False,
                         help="Also write <splint>/R2C2_Consensus.fastq: every consensus with per-base support QVs computed on "
                              "the GPU (not calibrated error probabilities; see DESIGN.md). Off by default.")
+    parser.add_argument("--emit", choices=["host", "gpu"], default="host",
+                        help="Where the consensus and subread records are formatted: the writer threads on the host "
+                             "(default), or the GPU, while the batch is still resident (with --bgzf they are compressed there "
+                             "as well). The files are the same byte for byte; measured at 1 M reads the run is slower "
+                             "without --bgzf and faster with it (DESIGN.md 5.8).")
     parser.add_argument("--version", "-v", action="version", version=VERSION, help="Prints the C3POa version.")
     if argv is None and len(sys.argv) == 1:
         parser.print_help()

@@ -32,7 +32,8 @@ EXPORTS = ["c3_default_config", "c3_version", "c3_device_count", "c3_warm_device
            "c3_bgzf_scan", "c3_bgzf_decompress", "c3_bgzf_decompress_host", "c3_reader_open_inflate", "c3_reader_inflate_wait",
            "c3_fastq_parse", "c3_fastq_parse_host", "c3_reader_parse_on_device", "c3_reader_parse_stats",
            "c3_post_emit", "c3_post_emit_host", "c3_post_emit_timing",
-           "c3_fasta_parse", "c3_fasta_parse_host", "c3_demux_emit", "c3_demux_emit_host", "c3_demux_emit_timing"]
+           "c3_fasta_parse", "c3_fasta_parse_host", "c3_demux_emit", "c3_demux_emit_host", "c3_demux_emit_timing",
+           "c3_emit_group", "c3_emit_group_host", "c3_batch_emit_snapshot", "c3_batch_emit_fetch", "c3_emit_timing_get", "c3_append_streams"]
 
 
 ZERO_MAX_CELLS = 16777216       # c3_default_config's zero_max_cells: largest front * tail the zero-repeat rescue takes
@@ -112,6 +113,11 @@ class PostArgs(C.Structure):
 class PostTiming(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("ms_classify", "ms_scan", "ms_emit", "ms_call")] + \
                [(k, C.c_int64) for k in ("n_reads", "n_kept", "in_bytes", "out_bytes")]
+
+
+class EmitTiming(C.Structure):
+    _fields_ = [(k, C.c_float) for k in ("ms_len", "ms_scan", "ms_write", "ms_bgzf", "ms_call")] + \
+               [(k, C.c_int64) for k in ("n_reads", "n_records", "in_bytes", "out_bytes")]
 
 
 class HostBatchStruct(C.Structure):
@@ -227,6 +233,13 @@ def load():
     lib.c3_demux_emit.argtypes = [vp] + de
     lib.c3_demux_emit_host.argtypes = de
     lib.c3_demux_emit_timing.argtypes = [vp, C.POINTER(DemuxTiming)]
+    em = [C.POINTER(HostBatchStruct), vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.POINTER(C.c_int64)]
+    lib.c3_emit_group.argtypes = [vp] + em
+    lib.c3_emit_group_host.argtypes = em
+    lib.c3_batch_emit_snapshot.argtypes = [vp, vp, vp, C.c_int, C.c_int]
+    lib.c3_batch_emit_fetch.argtypes = [vp, vp, C.c_int64, vp]
+    lib.c3_emit_timing_get.argtypes = [vp, C.POINTER(EmitTiming)]
+    lib.c3_append_streams.argtypes = [C.POINTER(C.c_char_p), vp, vp, C.c_int]
     _lib = lib
     return lib
 
@@ -391,11 +404,12 @@ class Handle:
         self._chk(self.lib.c3_batch_results_snapshot(self.h))
         return self.n, int(self.off[-1]) + 16
 
-    def results_fetch(self, into, shape):
+    def results_fetch(self, into, shape, with_cons=True):
         """second half (c3_batch_results_fetch): copies the snapshot into `into` (a ResultBuffers); may run on ANOTHER thread
-        while this handle's owner works on the next batch.  `shape` = the value results_snapshot returned."""
-        res, buf, coff = into.fit(*shape)
-        rc = self.lib.c3_batch_results_fetch(self.h, res.ctypes.data, buf.ctypes.data, len(buf), coff.ctypes.data)
+        while this handle's owner works on the next batch.  `shape` = the value results_snapshot returned.  with_cons=False:
+        the records and offsets alone (cons = NULL), for callers that take the bytes from emit_fetch."""
+        res, buf, coff = into.fit(*shape) if with_cons else into.fit(shape[0], 16)
+        rc = self.lib.c3_batch_results_fetch(self.h, res.ctypes.data, buf.ctypes.data if with_cons else None, len(buf) if with_cons else 0, coff.ctypes.data)
         if rc != 0:
             raise C3Error("c3_batch_results_fetch failed (%d)" % rc)
         return res, buf, coff
@@ -531,6 +545,39 @@ class Handle:
         t = PostTiming()
         self._chk(self.lib.c3_post_emit_timing(self.h, C.byref(t)))
         return {f[0]: getattr(t, f[0]) for f in PostTiming._fields_}
+
+    def emit_group(self, hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, zero=True, cap=None, arena=None):
+        """c3_emit_group (k_emit): the file bytes of write_group (+ write_consensus_fastq with qv_buf) for one group, as an
+        EmitStreams.  Same arguments as emit_group_host."""
+        return _emit_call(lambda *a: self.lib.c3_emit_group(self.h, *a), lambda: self.lib.c3_last_error(self.h),
+                          hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, zero, cap, arena)
+
+    def emit_snapshot(self, hb, zero=True, bgzf=False, qv=False):
+        """c3_batch_emit_snapshot: formats the records of the resident batch (whose names are hb's) on the device and freezes
+        the streams; the handle may then commit and run the next batch.  Returns the number of streams emit_fetch delivers."""
+        no = np.ascontiguousarray(hb.name_off, dtype=np.int64)
+        self._chk(self.lib.c3_batch_emit_snapshot(self.h, hb.c.names, no.ctypes.data, 1 if zero else 0, EMIT_BGZF if bgzf else 0))
+        return self.n_splints * (3 if qv else 2)
+
+    def emit_fetch(self, into, n_streams):
+        """c3_batch_emit_fetch: (arena bytes, stream_off[n_streams + 1]) of the emit snapshot in `into` (an EmitBuffers); may run
+        on ANOTHER thread while this handle's owner works on the next batch.  An arena that is too small is grown once."""
+        so = np.zeros(n_streams + 1, dtype=np.int64)
+        rc = self.lib.c3_batch_emit_fetch(self.h, into.ptr, into.size, so.ctypes.data)
+        if rc == E_LIMIT:
+            into.fit(int(so[n_streams]))
+            rc = self.lib.c3_batch_emit_fetch(self.h, into.ptr, into.size, so.ctypes.data)
+        if rc != 0:
+            e = C3Error("c3_batch_emit_fetch failed (%d)" % rc)
+            e.code = rc
+            raise e
+        return into, so
+
+    def emit_timing(self):
+        """c3_emit_timing_get: event times of the last emit_group, or of the snapshot the last emit_fetch delivered"""
+        t = EmitTiming()
+        self._chk(self.lib.c3_emit_timing_get(self.h, C.byref(t)))
+        return {f[0]: getattr(t, f[0]) for f in EmitTiming._fields_}
 
     def demux_indexes(self, heads, set_a, set_b, return_dist=False):
         """c3_demux_indexes (k_demux): winners (n, 2) int32 of index sets A and B (index number or -1) for every head
@@ -911,6 +958,18 @@ class HostBatch:
         self.off = np.ctypeslib.as_array(C.cast(c.off, C.POINTER(C.c_int64)), shape=(self.n + 1,)).copy()
         self.name_off = np.ctypeslib.as_array(C.cast(c.name_off, C.POINTER(C.c_int64)), shape=(self.n + 1,)).copy()
 
+    @classmethod
+    def from_lists(cls, names, seqs, quals):
+        """a group assembled from Python bytes (tests, tools): the arrays live as long as the object"""
+        nm, sq, ql = [_b(x) for x in names], [_b(x) for x in seqs], [_b(x) for x in quals]
+        assert len(nm) == len(sq) == len(ql) and all(len(a) == len(b) for a, b in zip(sq, ql))
+        n = len(nm)
+        no, off = np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in nm], out=no[1:]); np.cumsum([len(x) for x in sq], out=off[1:])
+        keep = [np.frombuffer(b"".join(x) + b"\0" * 16, dtype=np.uint8) for x in (nm, sq, ql)] + [no, off]
+        c = HostBatchStruct(n, 0, keep[0].ctypes.data, no.ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, off.ctypes.data)
+        return cls(c, owner=keep)
+
     def names(self):
         raw = C.string_at(self.c.names, int(self.name_off[-1])) if self.n else b""
         no = self.name_off
@@ -1084,6 +1143,95 @@ def write_consensus_fastq(hb, res, cons_buf, cons_off, qv_buf, splint_ids, fq_pa
                                       sid.ctypes.data, n_spl, fp, 1 if zero else 0)
     if rc != 0:
         raise OSError("c3_write_consensus_fastq failed (%d)" % rc)
+
+
+# ---- records formatted on the GPU (--emit gpu; include/c3poa.h "Records formatted on the GPU") ----
+EMIT_BGZF = 1
+EMIT_KINDS = ("consensus_fasta", "subread_fastq", "consensus_fastq")
+
+
+class EmitStreams:
+    """result of emit_group / emit_group_host: stream x = splint * K + kind lies at arena[stream_off[x]:stream_off[x + 1]]"""
+
+    def __init__(self, arena, stream_off, n_records, K):
+        self.arena, self.stream_off, self.n_records, self.K = arena, stream_off, n_records, K
+
+    def stream(self, x):
+        return self.arena[int(self.stream_off[x]):int(self.stream_off[x + 1])].tobytes()
+
+    def streams(self):
+        return [self.stream(x) for x in range(len(self.stream_off) - 1)]
+
+
+def _emit_call(fn, err, hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, zero, cap=None, arena=None):
+    """cap None: the arena is sized by a first call with no arena (C3_E_LIMIT reports the need).  An explicit cap / arena is
+    handed through as it is; a C3Error then carries .code and .stream_off."""
+    K = 3 if qv_buf is not None else 2
+    S = n_splints * K
+    sid = np.ascontiguousarray(splint_ids, dtype=np.int16)
+    res = np.ascontiguousarray(res)
+    coff = np.ascontiguousarray(cons_off, dtype=np.int64) if cons_off is not None else None
+    so = np.zeros(max(S, 0) + 2, dtype=np.int64)
+    nrec = C.c_int64(0)
+
+    def call(ar, c):
+        return fn(C.byref(hb.c), res.ctypes.data if len(res) else None, cons_buf.ctypes.data if cons_buf is not None else None,
+                  coff.ctypes.data if coff is not None else None, qv_buf.ctypes.data if qv_buf is not None else None,
+                  sid.ctypes.data if len(sid) else None, n_splints, 1 if zero else 0, ar.ctypes.data if ar is not None else None, c,
+                  so.ctypes.data, C.byref(nrec))
+
+    if cap is None:
+        rc = call(None, 0)
+        if rc == E_LIMIT:
+            cap = int(so[S])
+            arena = np.zeros(cap + 64, dtype=np.uint8)
+            rc = call(arena, cap)
+        elif rc == 0:
+            arena = np.zeros(0, dtype=np.uint8)
+    else:
+        rc = call(arena, cap)
+    if rc != 0:
+        e = C3Error("c3_emit_group failed (%d): %s" % (rc, err().decode()))
+        e.code, e.stream_off = rc, so[:max(S, 0) + 1].copy()
+        raise e
+    return EmitStreams(arena, so[:S + 1].copy(), int(nrec.value), K)
+
+
+def emit_group_host(hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, zero=True, cap=None, arena=None):
+    """c3_emit_group_host: the host statement of Handle.emit_group (same arguments and results).  hb: a HostBatch; res: RESULT_DTYPE
+    records; cons_buf / cons_off / qv_buf as results_raw / results_fetch_qv return them (cons_buf and qv_buf may be None)"""
+    lib = load()
+    return _emit_call(lib.c3_emit_group_host, lambda: lib.c3_last_error(None), hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, zero, cap, arena)
+
+
+class EmitBuffers:
+    """a grow-only page-locked arena for Handle.emit_fetch (one per batch in flight, pooled by the pipeline)"""
+
+    def __init__(self, nbytes=1 << 16):
+        self._pb = PinnedBytes(nbytes)
+        self.ptr, self.size, self.arr = self._pb.ptr, self._pb.size, self._pb.arr
+
+    def fit(self, nbytes):
+        if nbytes > self.size:
+            self._pb.close()
+            self._pb = PinnedBytes(nbytes + nbytes // 8)
+            self.ptr, self.size, self.arr = self._pb.ptr, self._pb.size, self._pb.arr
+
+    def close(self):
+        self.arr = None
+        self._pb.close()
+
+
+def append_streams(paths, arena_ptr, stream_off):
+    """c3_append_streams: every non-empty stream appended to paths[x] (None: skipped) with write_group's reservation"""
+    lib = load()
+    n = len(paths)
+    pp = (C.c_char_p * max(n, 1))(*[_b(p) if p is not None else None for p in paths])
+    so = np.ascontiguousarray(stream_off, dtype=np.int64)
+    assert len(so) == n + 1
+    rc = lib.c3_append_streams(pp, arena_ptr, so.ctypes.data, n)
+    if rc != 0:
+        raise OSError("c3_append_streams failed (%d): %s" % (rc, lib.c3_last_error(None).decode(errors="replace")))
 
 
 # ---- BGZF output (--bgzf; include/c3poa.h "BGZF output", DESIGN.md 5.3) ----

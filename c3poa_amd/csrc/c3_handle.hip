@@ -1,7 +1,8 @@
 // c3_handle.hip -- the batch handle of the C ABI (include/c3poa.h): create / destroy, splints, staging and commit of a batch,
-// results (snapshot + fetch), probes.  The stages themselves are c3_stages.hip.
+// results and formatted records (snapshot + fetch), probes.  The stages themselves are c3_stages.hip.
 // No CPU fallback exists in this library: without a gfx950 device c3_create fails.
 #include "c3_host.h"
+#include "c3_bgzf.h"
 
 thread_local double c3h::g_alloc_ms = 0.0;      // (DBuf::ensure adds to it, c3_batch_run reads it)
 
@@ -160,6 +161,9 @@ extern "C" void c3_destroy(c3_handle* h) {
   for (hipEvent_t ev : h->ev) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : h->ev_post) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : h->ev_fa) if (ev) (void)hipEventDestroy(ev);
+  for (c3h::EmitBufs* eb : {&h->emit_sa, &h->emit_snap}) for (hipEvent_t ev : eb->ev) if (ev) (void)hipEventDestroy(ev);
+  if (h->ev_emit_dn) (void)hipEventDestroy(h->ev_emit_dn);
+  if (h->h_emit_sizes) (void)hipHostFree(h->h_emit_sizes);
   if (h->h_fa_hdr) (void)hipHostFree(h->h_fa_hdr);
   if (h->h_tot) (void)hipHostFree(h->h_tot);
   delete h;
@@ -415,6 +419,119 @@ extern "C" int c3_batch_results_qv(c3_handle* h, c3_read_result* res, char* cons
 extern "C" int c3_batch_results(c3_handle* h, c3_read_result* res, char* cons, int64_t cons_cap, int64_t* cons_off) {
   if (!h || h->n <= 0 || !res) return C3_E_ARG;
   return results_now(h, res, cons, cons_cap, cons_off, nullptr);
+}
+
+// The records of the resident batch as file bytes, in two halves like the results above (include/c3poa.h "Records formatted on
+// the GPU"; the three steps are c3h::emit_run, c3_scans.hip):
+//   c3_batch_emit_snapshot  (owner thread, after c3_batch_run) uploads the names -- the only input that is not on the device --
+//                           and formats from the resident buffers into the snapshot's own arena: the consensus and QV bytes of
+//                           read i lie at d_cons / d_qv + off[i], their length is the record's.  One 8 * (S + 2)-byte read back.
+//   c3_batch_emit_fetch     copies the streams out on the download stream; with C3_EMIT_BGZF each stream goes through k_bgzf
+//                           first (chunks of BGZF_CHUNK_BLOCKS blocks, staged 4-byte aligned with 256 bytes of slack behind them).
+extern "C" int c3_batch_emit_snapshot(c3_handle* h, const char* names, const int64_t* name_off, int zero, int flags) {
+  if (!h || h->n <= 0 || !names || !name_off || (flags & ~C3_EMIT_BGZF)) return C3_E_ARG;
+  if (h->emit_pending.load(std::memory_order_acquire)) return c3_fail(h, C3_E_STATE, "c3_batch_emit_snapshot: the previous emit snapshot has not been fetched");
+  if (h->n_spl > C3_EMIT_MAX_SPLINTS) return c3_fail(h, C3_E_LIMIT, "c3_batch_emit_snapshot: more than 64 splints");
+  const double t_call = dbg_now_ms();
+  const int n = h->n;
+  if (name_off[0] != 0) return c3_fail(h, C3_E_ARG, "c3_batch_emit_snapshot: name_off must start at 0");
+  for (int i = 0; i < n; ++i) if (name_off[i + 1] < name_off[i]) return c3_fail(h, C3_E_ARG, "c3_batch_emit_snapshot: name_off not ascending");
+  for (int i = 0; i < n; ++i) if (name_off[i + 1] - name_off[i] >= (1ll << 31)) return c3_fail(h, C3_E_LIMIT, "c3_batch_emit_snapshot: a name of 2^31 bytes or more");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (!h->ev_emit_dn) HIPCHK(hipEventCreateWithFlags(&h->ev_emit_dn, hipEventDisableTiming));
+  const size_t nmb = (size_t)name_off[n];
+  HIPCHK(h->d_emit_names.put(names, nmb, h->stream, 16));
+  HIPCHK(h->d_emit_noff.put(name_off, sizeof(int64_t) * (size_t)(n + 1), h->stream));
+  const bool have_cons = (h->stages_done & C3_STAGE_POLISH) != 0, have_qv = have_cons && (h->stages_done & C3_STAGE_QV) != 0;
+  EmitArgs p; memset(&p, 0, sizeof(p));
+  p.n = n; p.n_splints = h->n_spl; p.K = have_qv ? 3 : 2; p.zero = zero;
+  p.names = h->d_emit_names.as<uint8_t>(); p.name_off = h->d_emit_noff.as<int64_t>();
+  p.seqs = h->d_ascii.as<uint8_t>(); p.quals = h->d_qual.as<uint8_t>(); p.off = h->d_off.as<int64_t>();
+  p.info = h->d_info.as<C3Info>(); p.sid = h->d_sid.as<int16_t>();
+  p.cons = have_cons ? h->d_cons.as<uint8_t>() : nullptr; p.qv = have_qv ? h->d_qv.as<uint8_t>() : nullptr;
+  p.cons_at = h->d_off.as<int64_t>(); p.cons_off = nullptr;
+  const int rc = c3h::emit_run(h, p, h->emit_snap, h->stream, h->emit_so, -1);
+  if (rc != C3_E_OK) return rc;
+  HIPCHK(hipEventRecord(h->ev_emit_dn, h->stream));
+  const int SK = p.n_splints * p.K;
+  c3_emit_timing& t = h->emit_tm;
+  t = c3_emit_timing{};
+  HIPCHK(hipEventElapsedTime(&t.ms_len, h->emit_snap.ev[0], h->emit_snap.ev[1]));
+  HIPCHK(hipEventElapsedTime(&t.ms_scan, h->emit_snap.ev[1], h->emit_snap.ev[2]));
+  t.n_reads = n; t.n_records = h->emit_so[(size_t)SK + 1]; t.in_bytes = (int64_t)nmb + 2 * h->total;
+  t.ms_call = (float)(dbg_now_ms() - t_call);
+  h->emit_S = SK; h->emit_flags = flags;
+  h->emit_pending.store(true, std::memory_order_release);
+  return C3_E_OK;
+}
+
+extern "C" int c3_batch_emit_fetch(c3_handle* h, char* arena, int64_t cap, int64_t* stream_off) {
+  if (!h || !stream_off || cap < 0 || (cap > 0 && !arena)) return C3_E_ARG;
+  if (!h->emit_pending.load(std::memory_order_acquire)) return C3_E_STATE;          // (h->err belongs to the owner thread: not touched here)
+  const double t_call = dbg_now_ms();
+  const int S = h->emit_S;
+  const std::vector<int64_t>& so = h->emit_so;
+  const bool z = (h->emit_flags & C3_EMIT_BGZF) != 0;
+  // capacity first: the plain total, or the sum of the compressed bounds
+  int64_t need = 0;
+  for (int x = 0; x < S; ++x) { stream_off[x] = need; const int64_t len = so[(size_t)x + 1] - so[(size_t)x]; need += z ? (len ? c3_bgzf_bound(len) : 0) : len; }
+  stream_off[S] = need;
+  if (need > cap) return C3_E_LIMIT;                                                 // (the snapshot stays: fetch again with a larger arena)
+  hipError_t e;
+#define DNCHK(x) do { if ((e = (x)) != hipSuccess) { h->emit_pending.store(false, std::memory_order_release); return C3_E_HIP; } } while (0)
+  DNCHK(hipSetDevice(h->cfg.device));
+  hipStream_t dn = h->stream_dn;
+  DNCHK(hipStreamWaitEvent(dn, h->ev_emit_dn, 0));
+  const char* src = h->emit_snap.arena.as<char>();
+  int64_t out = 0;
+  float ms_bgzf = 0.f;
+  if (!z) {
+    if (need) DNCHK(hipMemcpyAsync(arena, src, (size_t)need, hipMemcpyDeviceToHost, dn));
+    out = need;
+  } else {
+    const double t_z = dbg_now_ms();
+    const int64_t CH = (int64_t)BGZF_CHUNK_BLOCKS * BGZF_BLOCK;
+    int64_t longest = 0;
+    for (int x = 0; x < S; ++x) longest = std::max(longest, so[(size_t)x + 1] - so[(size_t)x]);
+    const int64_t first = std::min(CH, longest);
+    const int nb_max = (int)((first + BGZF_BLOCK - 1) / BGZF_BLOCK);
+    if (!h->h_emit_sizes) DNCHK(hipHostMalloc((void**)&h->h_emit_sizes, BGZF_CHUNK_BLOCKS * sizeof(int), hipHostMallocDefault));
+    DNCHK(h->d_emit_zin.ensure((size_t)first + 256)); DNCHK(h->d_emit_zslots.ensure((size_t)nb_max * BGZF_SLOT));
+    DNCHK(h->d_emit_zsizes.ensure((size_t)nb_max * sizeof(int))); DNCHK(h->d_emit_zpacked.ensure((size_t)nb_max * BGZF_MAX_MEMBER));
+    for (int x = 0; x < S; ++x) {
+      stream_off[x] = out;
+      const int64_t len = so[(size_t)x + 1] - so[(size_t)x];
+      for (int64_t c0 = 0; c0 < len; c0 += CH) {
+        const int64_t cn = std::min(CH, len - c0);
+        const int nb = (int)((cn + BGZF_BLOCK - 1) / BGZF_BLOCK);
+        DNCHK(hipMemcpyAsync(h->d_emit_zin.p, src + so[(size_t)x] + c0, (size_t)cn, hipMemcpyDeviceToDevice, dn));
+        c3k_launch_bgzf(h->d_emit_zin.as<uint8_t>(), (long long)cn, nb, h->d_emit_zslots.as<uint8_t>(), h->d_emit_zsizes.as<int>(), h->d_emit_zpacked.as<uint8_t>(), dn);
+        DNCHK(hipGetLastError());
+        DNCHK(hipMemcpyAsync(h->h_emit_sizes, h->d_emit_zsizes.p, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, dn));
+        DNCHK(hipStreamSynchronize(dn));
+        int64_t tot = 0;
+        for (int b = 0; b < nb; ++b) {
+          const int sz = h->h_emit_sizes[b];
+          if (sz < BGZF_HDR + 13 || sz > BGZF_MAX_MEMBER) { h->emit_pending.store(false, std::memory_order_release); return C3_E_HIP; }
+          tot += sz;
+        }
+        if (out + tot > cap) { h->emit_pending.store(false, std::memory_order_release); return C3_E_HIP; }      // (cannot be: cap >= the sum of the bounds)
+        DNCHK(hipMemcpyAsync(arena + out, h->d_emit_zpacked.p, (size_t)tot, hipMemcpyDeviceToHost, dn));
+        out += tot;
+      }
+    }
+    stream_off[S] = out;
+    DNCHK(hipStreamSynchronize(dn));
+    ms_bgzf = (float)(dbg_now_ms() - t_z);
+  }
+  DNCHK(hipStreamSynchronize(dn));
+  c3_emit_timing t = h->emit_tm;
+  DNCHK(hipEventElapsedTime(&t.ms_write, h->emit_snap.ev[3], h->emit_snap.ev[4]));
+#undef DNCHK
+  t.ms_bgzf = ms_bgzf; t.out_bytes = out; t.ms_call += (float)(dbg_now_ms() - t_call);
+  h->etm = t;
+  h->emit_pending.store(false, std::memory_order_release);
+  return C3_E_OK;
 }
 
 // PMC calibration: read `bytes` with one dword per lane, write `bytes` with one dword per

@@ -5,6 +5,7 @@
 #include "c3_args.h"
 #include "c3_launch.h"
 #include "c3_checks.h"
+#include "c3_emit.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -20,7 +21,11 @@ namespace c3h {                                  // defined once, used by severa
 extern thread_local double g_alloc_ms;           // host time spent growing device buffers (hipFree synchronises the device); c3_handle.hip
 int qv_scratch(c3_handle* h, long long max_m, long long max_n, int n_items, QvArgs& a, int* grid);      // c3_stages.hip
 int fetch_msa_rows(c3_handle* h, int read, int nrows, char* out, int64_t cap, int* msa_len);           // c3_handle.hip
+struct EmitBufs;
+int emit_run(c3_handle* h, EmitArgs& p, EmitBufs& eb, hipStream_t s, std::vector<int64_t>& so, int64_t cap);          // c3_scans.hip
 }
+
+#define BGZF_CHUNK_BLOCKS 2048                   // BGZF blocks per device chunk of a compression (c3_stream.hip, c3_batch_emit_fetch)
 
 static inline double dbg_now_ms() { using namespace std::chrono; return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count(); }
 // C3_DEBUG=1: progress lines on stderr, each stamped with the host clock (ms) -- shows the host gaps between the stages
@@ -56,6 +61,10 @@ struct DBuf {                                   // owns one device allocation (m
   template <class T> T* as() const { return (T*)p; }
 };
 
+// k_emit: pass buffers and arena of one formatting (c3_emit_group has one set, the emit snapshot another), event pairs around
+// k_emit_len / the scans / k_emit_write
+struct c3h::EmitBufs { DBuf work, offs, arena; hipEvent_t ev[5] = {}; };
+
 struct Summary { int status, n_sub, max_sub, sum_sub, max_dang, front, tail, n_peaks; };
 enum { EV_N = 10 };
 struct c3_handle {
@@ -88,6 +97,12 @@ struct c3_handle {
   DBuf d_post[16]; hipEvent_t ev_post[5] = {}; c3_post_timing ptm = {};       // k_post: inputs, descriptors, pass buffers, arena; event times of the last call
   // k_fasta: text, tables, arenas, output; event times of the last c3_demux_emit; page-locked copy of the device header
   DBuf d_fa[20]; hipEvent_t ev_fa[10] = {}; c3_demux_timing dtm = {}; struct C3FaHdr* h_fa_hdr = nullptr;
+  // k_emit: inputs of c3_emit_group and its pass buffers; times of the last c3_emit_group / delivered emit snapshot
+  DBuf d_emit[10]; c3h::EmitBufs emit_sa; c3_emit_timing etm = {};
+  // emit snapshot in flight (c3_batch_emit_snapshot .. _fetch): names, pass buffers + arena, BGZF staging of the fetch
+  c3h::EmitBufs emit_snap; DBuf d_emit_names, d_emit_noff, d_emit_zin, d_emit_zslots, d_emit_zsizes, d_emit_zpacked;
+  hipEvent_t ev_emit_dn = nullptr; int* h_emit_sizes = nullptr;
+  std::atomic<bool> emit_pending{false}; int emit_S = 0, emit_flags = 0; std::vector<int64_t> emit_so; c3_emit_timing emit_tm = {};
   std::vector<Summary> sum; std::vector<int> work;
   int res_prefix = 0;            // entries of peaks[] / sub_beg[] / sub_end[] that any read of the resident batch uses (0: unknown)
   int peaks_grid = 0; bool debug_msa = false; bool injected = false;

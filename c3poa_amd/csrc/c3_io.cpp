@@ -29,6 +29,7 @@
 
 #include "../../include/c3poa.h"
 #include "c3_checks.h"
+#include "c3_emit.h"
 
 namespace {
 
@@ -707,16 +708,11 @@ inline void fastq(Out& o, const char* name, size_t nl, long idx, const char* s, 
 inline size_t fastq_bound(size_t nl, int64_t len) { return nl + 2 * (size_t)std::max<int64_t>(len, 0) + 32; }
 
 // which records does read i produce?  (one place for the rules of C3POa.py:115-132 / determine_consensus.py:57-77,108-114)
+// (the rule itself is c3_emit_of of c3_emit.h, which k_emit applies as well)
 struct Emit { bool any, cons; int ns; };
 inline Emit emit_of(const c3_read_result& r, int s, int n_splints, int zero, int64_t clen) {
-  Emit e = {false, false, r.n_sub};
-  if (s < 0 || s >= n_splints) return e;
-  if (r.status == C3_ST_NOT_ASSIGNED || r.status == C3_ST_NO_PEAKS || r.status == C3_ST_TOO_SHORT) return e;   // C3POa.py:115,125,131
-  const int nd = (r.has_front ? 1 : 0) + (r.has_tail ? 1 : 0);
-  if (r.n_sub == 0) { if (!(zero && nd == 2)) return e; }
-  else if (r.status == C3_ST_LIMIT) return e;
-  e.any = true; e.cons = r.status == C3_ST_OK && clen > 0;
-  return e;
+  const C3EmitDec d = c3_emit_of(r, s, n_splints, zero, clen);
+  return Emit{d.any != 0, d.cons != 0, d.ns};
 }
 
 }  // namespace
@@ -1058,6 +1054,25 @@ extern "C" int c3_write_consensus_fastq_bgzf(c3_bgzf* z, const c3_host_batch* b,
     if (rc == C3_E_OK && !append_file(fq_paths[s], zbuf.data(), (size_t)clen)) rc = C3_E_ARG;
   }
   return rc;
+}
+
+// --emit gpu: finished streams (c3_emit_group, c3_batch_emit_fetch) appended to their files with the writers' reservation
+extern "C" int c3_append_streams(const char* const* paths, const char* arena, const int64_t* stream_off, int n_streams) {
+  if (!paths || !stream_off || n_streams < 0) return C3_E_ARG;
+  for (int x = 0; x < n_streams; ++x) if (stream_off[x + 1] < stream_off[x] || stream_off[0] < 0) return C3_E_ARG;
+  if (n_streams > 0 && stream_off[n_streams] > stream_off[0] && !arena) return C3_E_ARG;
+  for (int x = 0; x < n_streams; ++x) {
+    const int64_t len = stream_off[x + 1] - stream_off[x];
+    if (!len || !paths[x]) continue;
+    if (!append_file(paths[x], arena + stream_off[x], (size_t)len)) {      // (the code c3_write_group and its kin return for I/O errors, with the reason)
+      const int err = errno;
+      char msg[512];
+      snprintf(msg, sizeof msg, "c3_append_streams: stream %d: cannot append %lld bytes to %s: %s", x, (long long)len, paths[x], strerror(err));
+      c3_set_host_error(msg);
+      return C3_E_ARG;
+    }
+  }
+  return C3_E_OK;
 }
 
 // ---- oligo-dT index matcher of the post-processing step (C3POa_postprocessing.py:266-285, match_index) ----------

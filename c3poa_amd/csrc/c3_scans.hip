@@ -1,6 +1,6 @@
 // c3_scans.hip -- side stages that borrow the batch handle's stream: splint / adapter finders over the resident batch,
 // match_index, the post-processing records (k_post), the sample demultiplexer (k_demux) and its text-in / file-bytes-out path
-// (k_fasta).
+// (k_fasta), the main CLI's records (k_emit).
 #include "c3_host.h"
 #include "c3_post.h"
 #include "c3_fasta.h"
@@ -371,5 +371,94 @@ extern "C" int c3_demux_emit(c3_handle* h, const char* text, int64_t n, int at_e
 extern "C" int c3_demux_emit_timing(c3_handle* h, c3_demux_timing* t) {
   if (!h || !t) return C3_E_ARG;
   *t = h->dtm;
+  return C3_E_OK;
+}
+
+// ---- the main CLI's records (k_emit.hip; host statement and shared checks: c3_emit.cpp; the rule: c3_emit.h) ------------------
+// The three steps of one formatting on stream s, all pointers of p on the device: lengths + scans, the stream sizes read back
+// (so[S * K + 2]: starts, total, records; the arena is sized from them), the write pass.  cap >= 0: C3_E_LIMIT without the
+// write pass when the streams need more.  Serves c3_emit_group (below) and c3_batch_emit_snapshot (c3_handle.hip).
+int c3h::emit_run(c3_handle* h, EmitArgs& p, EmitBufs& eb, hipStream_t s, std::vector<int64_t>& so, int64_t cap) {
+  for (hipEvent_t& ev : eb.ev) if (!ev) HIPCHK(hipEventCreate(&ev));
+  const int n = p.n, SK = p.n_splints * p.K, nb = (n + 255) / 256;
+  // work = head [n] | len [n][3] | roff [n][3] | bsum [nb][SK + 1]
+  const size_t w_len = sizeof(EmitHead) * (size_t)n, w_roff = w_len + sizeof(int64_t) * C3_EMIT_KINDS * (size_t)n;
+  const size_t w_bsum = w_roff + sizeof(int64_t) * C3_EMIT_KINDS * (size_t)n;
+  static_assert(sizeof(EmitHead) % 8 == 0, "the arrays behind head[] hold 64-bit entries");
+  HIPCHK(eb.work.ensure(w_bsum + sizeof(long long) * (size_t)(nb + 1) * (SK + 1)));
+  HIPCHK(eb.offs.ensure(sizeof(int64_t) * (SK + 2)));
+  uint8_t* w = eb.work.as<uint8_t>();
+  p.head = (EmitHead*)w; p.len = (int64_t*)(w + w_len); p.roff = (int64_t*)(w + w_roff); p.bsum = (long long*)(w + w_bsum);
+  p.stream_off = eb.offs.as<int64_t>(); p.arena = nullptr;
+  HIPCHK(hipEventRecord(eb.ev[0], s));
+  c3k_launch_emit_len(&p, s);
+  HIPCHK(hipEventRecord(eb.ev[1], s));
+  c3k_launch_emit_scan(&p, s);
+  HIPCHK(hipEventRecord(eb.ev[2], s));
+  HIPCHK(hipGetLastError());
+  so.assign((size_t)SK + 2, 0);
+  HIPCHK(hipMemcpyAsync(so.data(), eb.offs.p, sizeof(int64_t) * (SK + 2), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  int64_t need = 0;                                              // the sums come from lengths the rule bounds: anything else is a kernel fault
+  for (int x = 0; x <= SK; ++x) { if (so[x] < need) return c3_fail(h, C3_E_HIP, "k_emit: stream offsets out of order"); need = so[x]; }
+  if (so[0] != 0 || so[SK + 1] < 0 || so[SK + 1] > (int64_t)n * (C3_EMIT_MAX_SUB + 4)) return c3_fail(h, C3_E_HIP, "k_emit: header out of range");
+  if (cap >= 0 && need > cap) return C3_E_LIMIT;
+  HIPCHK(eb.arena.ensure((size_t)need + 256));                  // (256: what k_bgzf may read behind a chunk, c3_batch_emit_fetch)
+  p.arena = eb.arena.as<uint8_t>();
+  HIPCHK(hipEventRecord(eb.ev[3], s));
+  c3k_launch_emit_write(&p, s);
+  HIPCHK(hipEventRecord(eb.ev[4], s));
+  HIPCHK(hipGetLastError());
+  return C3_E_OK;
+}
+
+// the stand-alone call: three steps on the handle's stream: upload + lengths + scans, the stream sizes read back, write + download
+extern "C" int c3_emit_group(c3_handle* h, const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
+                             const char* qv, const int16_t* splint_id, int n_splints, int zero, char* arena, int64_t cap,
+                             int64_t* stream_off, int64_t* n_records) {
+  if (!h) return C3_E_ARG;
+  const double t_call = dbg_now_ms();
+  const int rc = c3_emit_check_args("c3_emit_group", b, res, cons, cons_off, qv, splint_id, n_splints, zero, arena, cap, stream_off, n_records);
+  if (rc != C3_E_OK) return c3_fail(h, rc, c3_last_error(nullptr));
+  HIPCHK(hipSetDevice(h->cfg.device));
+  const int n = b->n, K = qv ? 3 : 2, SK = n_splints * K;
+  h->etm = c3_emit_timing{};
+  if (n == 0) { for (int x = 0; x <= SK; ++x) stream_off[x] = 0; *n_records = 0; return C3_E_OK; }
+  const size_t sb = (size_t)b->off[n], nmb = (size_t)b->name_off[n], cb = cons ? (size_t)cons_off[n] : 0, ob = sizeof(int64_t) * (size_t)(n + 1);
+  // every input buffer keeps 16 bytes of slack, as k_post's
+  struct Up { const void* src; size_t bytes; } up[10] = {
+    {b->names, nmb}, {b->name_off, ob}, {b->seqs, sb}, {b->quals, sb}, {b->off, ob}, {res, sizeof(c3_read_result) * (size_t)n},
+    {splint_id, sizeof(int16_t) * (size_t)n}, {cons, cb}, {qv, qv ? cb : 0}, {cons_off, cons ? ob : 0}};
+  DBuf* d = h->d_emit;
+  for (int k = 0; k < 10; ++k) {
+    HIPCHK(d[k].ensure(up[k].bytes + 16));
+    if (up[k].bytes) HIPCHK(hipMemcpyAsync(d[k].p, up[k].src, up[k].bytes, hipMemcpyHostToDevice, h->stream));
+  }
+  EmitArgs p; memset(&p, 0, sizeof(p));
+  p.n = n; p.n_splints = n_splints; p.K = K; p.zero = zero;
+  p.names = d[0].as<uint8_t>(); p.name_off = d[1].as<int64_t>(); p.seqs = d[2].as<uint8_t>(); p.quals = d[3].as<uint8_t>(); p.off = d[4].as<int64_t>();
+  p.info = d[5].as<c3_read_result>(); p.sid = d[6].as<int16_t>();
+  p.cons = cons ? d[7].as<uint8_t>() : nullptr; p.qv = qv ? d[8].as<uint8_t>() : nullptr;
+  p.cons_at = d[9].as<int64_t>(); p.cons_off = cons ? d[9].as<int64_t>() : nullptr;
+  std::vector<int64_t> so;
+  c3h::EmitBufs& eb = h->emit_sa;
+  const int rr = c3h::emit_run(h, p, eb, h->stream, so, cap);
+  if (rr != C3_E_OK && rr != C3_E_LIMIT) return rr;
+  memcpy(stream_off, so.data(), sizeof(int64_t) * (SK + 1));
+  *n_records = so[SK + 1];
+  if (rr == C3_E_LIMIT) return c3_fail(h, C3_E_LIMIT, "c3_emit_group: arena too small (bytes needed in stream_off[S])");
+  const int64_t need = so[SK];
+  if (need) HIPCHK(hipMemcpyAsync(arena, eb.arena.p, (size_t)need, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipEventElapsedTime(&h->etm.ms_len, eb.ev[0], eb.ev[1]));
+  HIPCHK(hipEventElapsedTime(&h->etm.ms_scan, eb.ev[1], eb.ev[2]));
+  HIPCHK(hipEventElapsedTime(&h->etm.ms_write, eb.ev[3], eb.ev[4]));
+  h->etm.n_reads = n; h->etm.n_records = so[SK + 1]; h->etm.in_bytes = (int64_t)(nmb + 2 * sb + cb * (qv ? 2 : 1)); h->etm.out_bytes = need;
+  h->etm.ms_call = (float)(dbg_now_ms() - t_call);
+  return C3_E_OK;
+}
+extern "C" int c3_emit_timing_get(c3_handle* h, c3_emit_timing* t) {
+  if (!h || !t) return C3_E_ARG;
+  *t = h->etm;
   return C3_E_OK;
 }

@@ -7,8 +7,7 @@
 
 // ---- BGZF output (k_bgzf.hip; host statement c3_bgzf.cpp) ---------------------------------
 // Input goes to the device in chunks of BGZF_CHUNK_BLOCKS blocks: copy in (the pieces land back to back), k_bgzf + k_bgzf_pack,
-// the member sizes back, then one copy of the packed members straight into the caller's buffer.
-#define BGZF_CHUNK_BLOCKS 2048
+// the member sizes back, then one copy of the packed members straight into the caller's buffer (BGZF_CHUNK_BLOCKS: c3_host.h).
 
 extern "C" int c3_bgzf_create(int device, c3_bgzf** out) {
   if (!out) return C3_E_ARG;

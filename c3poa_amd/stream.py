@@ -88,6 +88,10 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
     # --consensus-fastq: per-base QVs on the GPU (STAGE_QV) and R2C2_Consensus.fastq beside the FASTA
     qv_on = bool(getattr(args, "consensus_fastq", False))
     fq_paths = [args.out_path + n + "/R2C2_Consensus.fastq" for n in splint_names] if qv_on else []
+    # --emit gpu: the records of every batch are formatted on the GPU while it is resident (k_emit; with --bgzf compressed there
+    # as well) and the writer only appends the finished streams
+    emit_gpu = getattr(args, "emit", "host") == "gpu"
+    zero_on = bool(getattr(args, "zero", True))
     fused = assigner is None
     used = set(adapter_set or ())                                             # cat_files runs per adapter_set entry (C3POa.py:259)
     if fused:
@@ -114,6 +118,8 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
         cons_w, sub_w, fq_w = [p + ".gz" for p in cons_paths], [p + ".gz" for p in sub_paths], [p + ".gz" for p in fq_paths]
     else:
         cons_w, sub_w, fq_w = cons_paths, sub_paths, fq_paths
+    # stream s * K + kind of c3_batch_emit_fetch -> its file
+    emit_paths = [p for k in range(len(splint_names)) for p in ((cons_w[k], sub_w[k]) + ((fq_w[k],) if qv_on else ()))]
     # C3_GPU_BATCH_READS overrides the GPU batch size (tests drive the multi-batch pipeline with small inputs)
     gpu_batch = int(os.environ.get("C3_GPU_BATCH_READS", "0"))
     batch_reads = gpu_batch if gpu_batch > 0 else max(int(args.groupSize), GPU_BATCH_READS)
@@ -171,6 +177,10 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
     free_results = queue.Queue()
     for _k in range(4 * n_work + 2):                # run -> fetch -> (queue of 2) -> write: four batches per worker can hold one
         free_results.put(_lib.ResultBuffers())
+    free_emit = queue.Queue()                       # --emit gpu: page-locked arenas of the streams, grow-only, owned like the result buffers
+    emit_bufs = [_lib.EmitBuffers() for _k in range(4 * n_work)] if emit_gpu else []
+    for eb_ in emit_bufs:
+        free_emit.put(eb_)
     parsed = [queue.Queue(maxsize=1) for _ in range(n_ranges)]
     to_write = [queue.Queue(maxsize=2) for _ in range(n_work)]
     to_fetch = [queue.Queue(maxsize=1) for _ in range(n_work)]
@@ -179,6 +189,8 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
         ev_.set()
     t = dict(parse=0.0, assign=0.0, upload=0.0, upload_dev=0.0, run=0.0, run_c=0.0, run_dev=0.0, alloc=0.0, fetch=0.0, snapshot=0.0, write=0.0, wait_in=0.0, wait_out=0.0,
              setup=0.0, close=0.0, scan=0.0, reads=0, batches=0, short=0, assigned=0, ranges=n_ranges)
+    if emit_gpu:                                    # kernel times of k_emit (and k_bgzf inside the fetch), summed over the batches
+        t.update(emit_len=0.0, emit_scan=0.0, emit_write=0.0, emit_bgzf=0.0, emit_call=0.0, emit_bytes=0, emit_records=0)
     seen = set()
     errors, lock = [], threading.Lock()
 
@@ -303,12 +315,13 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
                     break
                 fetched[w].clear()
                 shape = h.results_snapshot()
+                n_streams = h.emit_snapshot(hb, zero_on, bgzf, qv_on) if emit_gpu else 0
                 t3 = time.perf_counter()
                 with lock:
                     t["upload_dev"] += up_dev; t["run_dev"] += run_dev; t["run_c"] += run_c; t["alloc"] += wl_c
                     t["run"] += t2 - t1; t["snapshot"] += t3 - t2
                 tw = time.perf_counter()
-                to_fetch[w].put((h, hb, sid, shape))
+                to_fetch[w].put((h, hb, sid, shape, n_streams))
                 with lock:
                     t["wait_out"] += time.perf_counter() - tw
                 if done:
@@ -345,11 +358,21 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
             item = to_fetch[w].get()
             if item is None:
                 break
-            h, hb, sid, shape = item
+            h, hb, sid, shape, n_streams = item
             rb = free_results.get()
+            eb = free_emit.get() if emit_gpu else None
+            so = None
             t0 = time.perf_counter()
             try:
-                if qv_on:
+                if emit_gpu:                        # the records alone (the prefix copy is small), then the finished streams
+                    (res, buf, coff), qv = h.results_fetch(rb, shape, with_cons=False), None
+                    eb, so = h.emit_fetch(eb, n_streams)
+                    et = h.emit_timing()
+                    with lock:
+                        for k_ in ("len", "scan", "write", "bgzf", "call"):
+                            t["emit_" + k_] += et["ms_" + k_] * 1e-3
+                        t["emit_bytes"] += et["out_bytes"]; t["emit_records"] += et["n_records"]
+                elif qv_on:
                     res, buf, coff, qv = h.results_fetch_qv(rb, shape)
                 else:
                     (res, buf, coff), qv = h.results_fetch(rb, shape), None
@@ -357,13 +380,15 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
                 errors.append(e)
                 fetched[w].set()
                 free_results.put(rb)                # the buffers of a batch that is lost go back to their owners
+                if eb is not None:
+                    free_emit.put(eb)
                 free_sets[hb.range_index].put(hb.set_index)
                 continue
             fetched[w].set()
             with lock:
                 t["fetch"] += time.perf_counter() - t0
             del h, item
-            to_write[w].put((hb, sid, res, buf, coff, qv, rb))
+            to_write[w].put((hb, sid, res, buf, coff, qv, rb, eb, so))
         to_write[w].put(None)
 
     def writer_thread(w):                           # c3_write_group releases the GIL: overlaps parsing and the GPUs
@@ -372,11 +397,13 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
             item = to_write[w].get()
             if item is None:
                 break
-            hb, sid, res, buf, coff, qv, rb = item
+            hb, sid, res, buf, coff, qv, rb, eb, so = item
             t0 = time.perf_counter()
             try:
                 if not errors:
-                    if bgzf:
+                    if emit_gpu:                    # finished bytes (text, or BGZF members with --bgzf): appended, nothing formatted here
+                        _lib.append_streams(emit_paths, eb.ptr, so)
+                    elif bgzf:
                         if z is None:
                             z = _lib.Bgzf(worker_device(w))
                         _lib.write_group_bgzf(z, hb, res, buf, coff, sid, cons_w, sub_w, getattr(args, "zero", True))
@@ -393,6 +420,8 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
             k, j = hb.range_index, hb.set_index
             del hb, item, res, buf, coff, qv
             free_results.put(rb)
+            if eb is not None:
+                free_emit.put(eb)
             free_sets[k].put(j)
         if z is not None:
             z.close()
@@ -419,6 +448,11 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
     else:
         for rd in readers:
             rd.close()
+    if keep_pinned:                                 # ... and the page-locked arenas of --emit gpu likewise
+        _KEPT.extend(emit_bufs)
+    else:
+        for eb_ in emit_bufs:
+            eb_.close()
     t["at_readers_closed"] = time.perf_counter() - t_start
     if fused:
         os.replace(finder_psl + ".part", finder_psl)              # a rerun finds the PSL and takes the two-pass route

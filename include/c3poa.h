@@ -547,6 +547,55 @@ int c3_demux_emit_host(const char* text, int64_t n, int at_eof,
 typedef struct { float ms_parse, ms_demux, ms_emit, ms_call; int64_t n_records, n_kept, in_bytes, out_bytes; } c3_demux_timing;
 int c3_demux_emit_timing(c3_handle* h, c3_demux_timing* t);
 
+/* ---- Records formatted on the GPU (C3POa.py --emit gpu) ----
+ * The file bytes of c3_write_group (and of c3_write_consensus_fastq when qv is given) for one group, as streams in one arena
+ * instead of appended to files.  The per-read rule is c3poa_amd/csrc/c3_emit.h (emit_of and the record order of the writer, the
+ * average-quality text by integer arithmetic).  b / res / cons / cons_off / qv / splint_id / n_splints / zero mean what they
+ * mean in c3_write_group and c3_write_consensus_fastq; cons may be NULL (no consensus records), qv needs cons.
+ * Output: K kinds per splint, K = 2 without qv (consensus FASTA, subread FASTQ), K = 3 with it (+ consensus FASTQ); stream
+ * s * K + kind at [stream_off[x], stream_off[x + 1]), x = 0 .. n_splints * K - 1; records within a stream are in read order.
+ * *n_records = records written over all streams.  When the streams need more than cap bytes: C3_E_LIMIT, stream_off is filled
+ * all the same (stream_off[n_splints * K] = bytes needed) and the arena is left alone.
+ * Every record is validated before anything is formatted (on the host, before any launch): offsets ascending from 0 (a
+ * group may hold any number of bytes; one read, name or consensus must stay below 2^31: C3_E_LIMIT), and for each read that writes something n_sub in 0 .. 250, 0 <= sub_beg <= sub_end <= L for its kept
+ * subreads, front_end / tail_beg of the pieces it writes inside the read, L > 0 where a consensus record is due; otherwise
+ * C3_E_ARG with a text naming the read.  More than 64 splints: C3_E_LIMIT.
+ * c3_emit_group uploads its arguments, runs k_emit on the handle's device and copies the arena down; c3_emit_group_host is
+ * its host statement, byte for byte (errors through c3_last_error(NULL)). */
+#define C3_EMIT_BGZF 1            /* flags of c3_batch_emit_snapshot: the fetch delivers BGZF members instead of text */
+int c3_emit_group(c3_handle* h, const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
+                  const char* qv, const int16_t* splint_id, int n_splints, int zero, char* arena, int64_t cap,
+                  int64_t* stream_off, int64_t* n_records);
+int c3_emit_group_host(const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
+                       const char* qv, const int16_t* splint_id, int n_splints, int zero, char* arena, int64_t cap,
+                       int64_t* stream_off, int64_t* n_records);
+/* The same for the RESIDENT batch, in two halves like c3_batch_results_snapshot / _fetch, so that the finished bytes leave the
+ * device beside the next batch's kernels and the host formats nothing.
+ * c3_batch_emit_snapshot (owner thread, after c3_batch_run with C3_STAGE_POLISH, before the next c3_batch_commit) uploads the
+ * names of the resident batch (name_off[n + 1] from 0), formats its records from the resident buffers (splint ids as uploaded,
+ * n_splints = rows of c3_set_splints; K = 3 when the batch ran C3_STAGE_QV) into a grow-only device arena of its own and
+ * records an event.  It does not replace the results snapshot.  One emit snapshot per handle: a second one before the fetch
+ * returns C3_E_STATE, as does a fetch without a snapshot.
+ * c3_batch_emit_fetch copies the streams into arena / stream_off[n_splints * K + 1] on the handle's download stream and returns
+ * when they have landed; it touches nothing but the emit snapshot and may run on another thread beside the owner's next
+ * c3_batch_commit / c3_batch_run (it does not set c3_last_error).  cap too small: C3_E_LIMIT with stream_off filled
+ * (stream_off[n_splints * K] = bytes needed) and THE SNAPSHOT KEPT, so the caller can fetch again with a larger arena.
+ * With C3_EMIT_BGZF set at snapshot time every non-empty stream is compressed by k_bgzf before it leaves the device (as one
+ * text, exactly the members c3_write_group_bgzf / c3_write_consensus_fastq_bgzf append for the same group); stream_off then
+ * describes the compressed streams, and the bytes needed are the sum of c3_bgzf_bound over the streams. */
+int c3_batch_emit_snapshot(c3_handle* h, const char* names, const int64_t* name_off, int zero, int flags);
+int c3_batch_emit_fetch(c3_handle* h, char* arena, int64_t cap, int64_t* stream_off);
+/* kernel times (hipEvents) of the last c3_emit_group, or of the snapshot that the last c3_batch_emit_fetch delivered: k_emit_len,
+ * the scans, k_emit_write, k_bgzf inside the fetch (host time of the compression loop), host time of the call(s) with their
+ * copies; bytes read (names, bases, qualities, consensus) and bytes delivered.  Ask on the thread that made that call. */
+typedef struct { float ms_len, ms_scan, ms_write, ms_bgzf, ms_call; int64_t n_reads, n_records, in_bytes, out_bytes; } c3_emit_timing;
+int c3_emit_timing_get(c3_handle* h, c3_emit_timing* t);
+/* Appends stream x (arena + stream_off[x], stream_off[x + 1] - stream_off[x] bytes) to paths[x] for every non-empty stream
+ * whose path is not NULL, with c3_write_group's per-file reservation and locking (several workers may share the files).
+ * A file that cannot be opened or written fails the call with the writers' code for that, C3_E_ARG, and a c3_last_error(NULL)
+ * text naming the path and the system's reason.  Host code. */
+int c3_append_streams(const char* const* paths, const char* arena, const int64_t* stream_off, int n_streams);
+
 #ifdef __cplusplus
 }
 #endif
