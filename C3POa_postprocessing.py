@@ -3,7 +3,7 @@
 
 Same flags, inputs and output files as rvolden/C3POa v2.2.3 (/root/reference/C3POa_postprocessing.py:17-62, 400-434):
     python3 C3POa_postprocessing.py -i R2C2_Consensus.fasta -a adapters.fasta -o out [-x indexes.fasta] [-u] [-t] [-b]
-                                    [-n N] [-g 1000] [-bt] [-co] [-c config] [--emit gpu [--keep-quals]]
+                                    [-n N] [-g 1000] [-bt] [-co] [-c config] [--emit gpu [--keep-quals] [--bgzf] [--parse gpu [--inflate gpu]]]
 The adapter-to-read alignment that upstream delegates to blat runs on the GPU (c3_scan_adapters); the PSL file
 <out>/adapter_to_consensus_alignment.psl is written and reused exactly as upstream reuses it.
 """
@@ -40,6 +40,16 @@ def parse_args(argv=None):
                    help="gpu: classify, trim, orient, demultiplex and format the records on the GPU (k_post); host (default): as before.")
     p.add_argument("--keep-quals", dest="keep_quals", action="store_true", default=False,
                    help="Carry the qualities of a FASTQ input through: the three read files become .fastq (needs --emit gpu).")
+    p.add_argument("--bgzf", action="store_true", default=False,
+                   help="Write the read files (three per destination, and the 10x file) as BGZF <name>.gz, compressed on the GPU "
+                        "(k_bgzf) as they are written; the TSV and the PSL stay plain (needs --emit gpu; not with -co).")
+    p.add_argument("--parse", choices=["host", "gpu"], default="host",
+                   help="gpu: the input goes to the GPU as text, piece by piece, and is parsed there (k_fastx); only finished file "
+                        "bytes come back (needs --emit gpu).  host (default): the reader parses, as before.")
+    p.add_argument("--inflate", choices=["host", "gpu"], default="host",
+                   help="gpu: a BGZF input is inflated on the GPU as well (k_inflate; needs --parse gpu).")
+    p.add_argument("--post-chunk", dest="post_chunk", type=int, default=64 << 20, help=argparse.SUPPRESS)
+    p.add_argument("--emit-stats", dest="emit_stats", action="store_true", default=False, help=argparse.SUPPRESS)
     p.add_argument("--post-batch", dest="post_batch", type=int, default=200000, help=argparse.SUPPRESS)
     p.add_argument("--version", "-v", action="version", version=VERSION, help="Prints the C3POa version.")
     if argv is None and len(sys.argv) == 1:
@@ -48,6 +58,16 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.keep_quals and args.emit != "gpu":
         p.error("--keep-quals needs --emit gpu")
+    if args.bgzf and args.emit != "gpu":
+        p.error("--bgzf needs --emit gpu")
+    if args.parse == "gpu" and args.emit != "gpu":
+        p.error("--parse gpu needs --emit gpu")
+    if args.inflate == "gpu" and args.parse != "gpu":
+        p.error("--inflate gpu needs --parse gpu")
+    if args.post_chunk < 1:
+        p.error("--post-chunk must be at least 1")
+    if args.bgzf and args.compress_output:
+        p.error("-co and --bgzf both compress the output: give one of them")
     return args
 
 

@@ -33,7 +33,8 @@ EXPORTS = ["c3_default_config", "c3_version", "c3_device_count", "c3_warm_device
            "c3_fastq_parse", "c3_fastq_parse_host", "c3_reader_parse_on_device", "c3_reader_parse_stats",
            "c3_post_emit", "c3_post_emit_host", "c3_post_emit_timing",
            "c3_fasta_parse", "c3_fasta_parse_host", "c3_demux_emit", "c3_demux_emit_host", "c3_demux_emit_timing",
-           "c3_emit_group", "c3_emit_group_host", "c3_batch_emit_snapshot", "c3_batch_emit_fetch", "c3_emit_timing_get", "c3_append_streams"]
+           "c3_emit_group", "c3_emit_group_host", "c3_batch_emit_snapshot", "c3_batch_emit_fetch", "c3_emit_timing_get", "c3_append_streams",
+           "c3_fastx_strict_parse_host", "c3_post_emit_text", "c3_post_text_reset", "c3_post_text_timing_get"]
 
 
 ZERO_MAX_CELLS = 16777216       # c3_default_config's zero_max_cells: largest front * tail the zero-repeat rescue takes
@@ -99,6 +100,25 @@ class FastqInfo(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _t in self._fields_}
+
+
+class FastxInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_records", "consumed", "name_bytes", "base_bytes")] + [("departed", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _t in self._fields_}
+
+
+class PostTextInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_records", "n_kept", "consumed", "text_bytes", "out_bytes")] + [("departed", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _t in self._fields_}
+
+
+class PostTextTiming(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("ms_inflate", "ms_parse", "ms_gather", "ms_adapter", "ms_post", "ms_bgzf", "ms_call")] + \
+               [(n, C.c_int64) for n in ("n_records", "n_kept", "in_bytes", "text_bytes", "out_bytes")]
 
 
 class PostArgs(C.Structure):
@@ -240,6 +260,12 @@ def load():
     lib.c3_batch_emit_fetch.argtypes = [vp, vp, C.c_int64, vp]
     lib.c3_emit_timing_get.argtypes = [vp, C.POINTER(EmitTiming)]
     lib.c3_append_streams.argtypes = [C.POINTER(C.c_char_p), vp, vp, C.c_int]
+    lib.c3_fastx_strict_parse_host.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, C.c_int64,
+                                               C.POINTER(FastxInfo)]
+    lib.c3_post_emit_text.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, C.POINTER(PostArgs), vp, C.c_int64, vp, vp, C.c_int64,
+                                      C.POINTER(PostTextInfo)]
+    lib.c3_post_text_reset.argtypes = [vp]
+    lib.c3_post_text_timing_get.argtypes = [vp, C.POINTER(PostTextTiming)]
     _lib = lib
     return lib
 
@@ -540,6 +566,60 @@ class Handle:
         scan_adapters returned for the batch.  Returns (arena uint8 array, stream_off[S + 1], kept reads)."""
         return _post_call(lambda *a: self.lib.c3_post_emit(self.h, *a), lambda: self.lib.c3_last_error(self.h), plan, batch, table)
 
+    def post_emit_text(self, plan, piece, at_eof=False, in_bgzf=False, out_bgzf=False, keep_quals=False, cap=None, max_records=None, bufs=None):
+        """c3_post_emit_text: the next piece of a consensus file (bytes; whole BGZF members with in_bgzf) through parse,
+        k_adapter and k_post on the device.  Returns a PostText: info (dict), arena (uint8 array), stream_off[S + 1], hashes
+        (uint64 array of n_records), guards_intact.  cap / max_records: instead of sizes found by asking again; C3Error (code,
+        .info, .stream_off, .guards_intact, .untouched) on a refusal.  bufs: a dict the call keeps its output arrays in from one
+        piece to the next (no guard bytes then; the results are views that the next call overwrites)."""
+        src = piece if isinstance(piece, np.ndarray) else np.frombuffer(_bytes(piece), dtype=np.uint8)
+        n = len(src)
+        flags = (POST_IN_BGZF if in_bgzf else 0) | (POST_OUT_BGZF if out_bgzf else 0) | (POST_KEEP_QUALS if keep_quals else 0)
+        a = _post_args(plan, 0, None, None, None, None, None, None)
+        S = plan.n_streams
+        so = np.zeros(S + 1, dtype=np.int64)
+        info = PostTextInfo()
+        ask = cap is None and max_records is None
+        cap = (24 if in_bgzf else 3) * n + 65536 if cap is None else int(cap)
+        max_records = (8 if in_bgzf else 1) * (n // 8) + 16 if max_records is None else int(max_records)
+        g = FASTA_GUARD if bufs is None else 0
+        for _try in range(3):
+            if bufs is None:
+                arena, hashes = np.full(cap + 2 * g, 0xA5, dtype=np.uint8), np.full(8 * max_records + 2 * g, 0xA5, dtype=np.uint8)
+            else:
+                if len(bufs.get("arena", ())) < cap:
+                    bufs["arena"] = np.empty(cap, dtype=np.uint8)
+                if len(bufs.get("hashes", ())) < 8 * max_records:
+                    bufs["hashes"] = np.empty(8 * max_records, dtype=np.uint8)
+                arena, hashes, cap, max_records = bufs["arena"], bufs["hashes"], len(bufs["arena"]), len(bufs["hashes"]) // 8
+            rc = self.lib.c3_post_emit_text(self.h, src.ctypes.data if n else None, n, int(bool(at_eof)), flags, C.byref(a), arena.ctypes.data + g, cap,
+                                            so.ctypes.data, hashes.ctypes.data + g, max_records, C.byref(info))
+            if ask and rc == E_LIMIT and (so[S] > cap or info.n_records > max_records):
+                cap, max_records = max(cap, int(so[S])), max(max_records, int(info.n_records))
+                continue
+            break
+        out = PostText()
+        out.info, out.stream_off = info.as_dict(), so
+        used = {"arena": int(so[S]), "hashes": 8 * int(info.n_records)} if rc == 0 else {"arena": 0, "hashes": 0}
+        out.guards_intact, out.untouched_beyond_results = _guarded({"arena": arena, "hashes": hashes}, used) if bufs is None else (True, True)
+        if rc != 0:
+            e = C3Error("c3 error %d: %s" % (rc, self.lib.c3_last_error(self.h).decode()))
+            e.code, e.info, e.stream_off, e.guards_intact, e.untouched = rc, out.info, so, out.guards_intact, out.untouched_beyond_results
+            raise e
+        out.arena = arena[g:g + used["arena"]]
+        out.hashes = hashes[g:g + used["hashes"]].view(np.uint64).copy()
+        return out
+
+    def post_text_reset(self):
+        """c3_post_text_reset: drops the tail the text path keeps between two pieces and forgets the file's kind"""
+        self._chk(self.lib.c3_post_text_reset(self.h))
+
+    def post_text_timing(self):
+        """c3_post_text_timing_get: times of the last post_emit_text"""
+        t = PostTextTiming()
+        self._chk(self.lib.c3_post_text_timing_get(self.h, C.byref(t)))
+        return {f[0]: getattr(t, f[0]) for f in PostTextTiming._fields_}
+
     def post_emit_timing(self):
         """c3_post_emit_timing: event times of the three passes of the last post_emit and the call with its copies"""
         t = PostTiming()
@@ -718,16 +798,30 @@ def _ptr(x):
     return None if x is None else (x.ctypes.data if isinstance(x, np.ndarray) else x)
 
 
+POST_IN_BGZF, POST_OUT_BGZF, POST_KEEP_QUALS = 1, 2, 4       # flags of c3_post_emit_text
+
+
+class PostText:
+    """result of c3_post_emit_text: info (dict), arena (uint8 array), stream_off (int64 array of S + 1), hashes (uint64 array)"""
+
+    def streams(self):
+        so = self.stream_off
+        return [self.arena[int(so[s]):int(so[s + 1])].tobytes() for s in range(len(so) - 1)]
+
+
+def _post_args(plan, n, names, name_off, seqs, quals, off, table):
+    return PostArgs(n, names, name_off, seqs, quals, off, table, len(plan.ad_len), plan.ad_len.ctypes.data, plan.ad_class.ctypes.data,
+                    plan.class5, C.cast(C.c_char_p(plan.ad_name_cat), C.c_void_p).value, plan.ad_name_off.ctypes.data,
+                    int(plan.has_index), len(plan.idx_seqs), C.cast(C.c_char_p(plan.idx_cat), C.c_void_p).value,
+                    plan.idx_off.ctypes.data, plan.idx_dest.ctypes.data, len(plan.dests),
+                    int(plan.undirectional), int(plan.trim), int(plan.barcoded))
+
+
 def _post_call(fn, err, plan, batch, table):
     tab = np.ascontiguousarray(table, dtype=np.int32)
     n_ad = len(plan.ad_len)
     assert tab.size == batch.n * n_ad * 24
-    a = PostArgs(batch.n, _ptr(batch.names), _ptr(batch.name_off), _ptr(batch.seqs), _ptr(batch.quals), _ptr(batch.off),
-                 tab.ctypes.data, n_ad, plan.ad_len.ctypes.data, plan.ad_class.ctypes.data, plan.class5,
-                 C.cast(C.c_char_p(plan.ad_name_cat), C.c_void_p).value, plan.ad_name_off.ctypes.data,
-                 int(plan.has_index), len(plan.idx_seqs), C.cast(C.c_char_p(plan.idx_cat), C.c_void_p).value,
-                 plan.idx_off.ctypes.data, plan.idx_dest.ctypes.data, len(plan.dests),
-                 int(plan.undirectional), int(plan.trim), int(plan.barcoded))
+    a = _post_args(plan, batch.n, _ptr(batch.names), _ptr(batch.name_off), _ptr(batch.seqs), _ptr(batch.quals), _ptr(batch.off), tab.ctypes.data)
     S = plan.n_streams
     so = np.zeros(S + 1, dtype=np.int64)
     kept = C.c_int64(0)
@@ -1414,6 +1508,65 @@ def fasta_parse_host(text, at_eof=True, caps=None):
     sizes that always fit; C3Error (code E_LIMIT, .info) when too small"""
     lib = load()
     return _fasta_call(lib.c3_fasta_parse_host, lambda: lib.c3_last_error(None), text, at_eof, caps)
+
+
+# ---- Strict FASTA / FASTQ records (the input of C3POa_postprocessing.py; DESIGN.md 5.9) ----
+class FastxParse:
+    """result of c3_fastx_strict_parse_host: info (dict), names / seqs / quals (bytes; quals None for kind 2), name_off / off
+    (int64 arrays of n_records + 1), hashes (uint64 array), guards_intact, untouched_beyond_results"""
+
+    def records(self):
+        no, o = self.name_off, self.off
+        q = self.quals
+        return [(self.names[no[i]:no[i + 1]], self.seqs[o[i]:o[i + 1]], q[o[i]:o[i + 1]] if q is not None else None)
+                for i in range(len(o) - 1)]
+
+
+def fastx_kind(first_byte):
+    """the kind a file's first byte announces: 4 ('@'), 2 ('>') or 0 (neither: a departure)"""
+    return {b"@": 4, b">": 2}.get(bytes(first_byte[:1]), 0)
+
+
+def fastx_max_records(n, kind):
+    """records a text of n bytes can hold at most (a record is at least one byte and a '\n' per line; the last may lack it)"""
+    return (n + 1) // (2 * kind) + 1
+
+
+def fastx_strict_parse_host(text, at_eof=False, kind=2, caps=None):
+    """c3_fastx_strict_parse_host: the longest prefix of whole strict records of `text` (kind 2: two-line FASTA, kind 4: FASTQ).
+    caps = (names_cap, bases_cap, max_records) instead of sizes that always fit; C3Error (code E_LIMIT, .info) when too small"""
+    lib = load()
+    src = _bytes(text)
+    n = len(src)
+    names_cap, bases_cap, max_records = caps if caps is not None else (n, n, fastx_max_records(n, kind if kind in (2, 4) else 2))
+    g = FASTA_GUARD
+    sizes = {"names": names_cap, "seqs": bases_cap, "quals": bases_cap if kind == 4 else 0, "name_off": 8 * (max_records + 1),
+             "off": 8 * (max_records + 1), "hashes": 8 * max_records}
+    bufs = {k: np.full(v + 2 * g, 0xA5, dtype=np.uint8) for k, v in sizes.items()}
+    ptr = {k: v.ctypes.data + g for k, v in bufs.items()}
+    info = FastxInfo()
+    rc = lib.c3_fastx_strict_parse_host(src if n else None, n, int(bool(at_eof)), int(kind), ptr["names"], names_cap, ptr["name_off"],
+                                        ptr["seqs"], ptr["quals"] if kind == 4 else None, bases_cap, ptr["off"], ptr["hashes"],
+                                        max_records, C.byref(info))
+    out = FastxParse()
+    out.info = info.as_dict()
+    used = dict.fromkeys(sizes, 0)
+    if rc == 0:
+        nr = out.info["n_records"]
+        used = {"names": out.info["name_bytes"], "seqs": out.info["base_bytes"], "quals": out.info["base_bytes"] if kind == 4 else 0,
+                "name_off": 8 * (nr + 1), "off": 8 * (nr + 1), "hashes": 8 * nr}
+    out.guards_intact, out.untouched_beyond_results = _guarded(bufs, used)
+    if rc != 0:
+        e = _c3_fail(rc)
+        e.info, e.guards_intact, e.untouched = out.info, out.guards_intact, out.untouched_beyond_results
+        raise e
+    for k in ("names", "seqs"):
+        setattr(out, k, bufs[k][g:g + used[k]].tobytes())
+    out.quals = bufs["quals"][g:g + used["quals"]].tobytes() if kind == 4 else None
+    for k in ("name_off", "off"):
+        setattr(out, k, bufs[k][g:g + used[k]].view(np.int64).copy())
+    out.hashes = bufs["hashes"][g:g + used["hashes"]].view(np.uint64).copy()
+    return out
 
 
 class DemuxSets:

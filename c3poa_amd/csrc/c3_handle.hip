@@ -38,6 +38,10 @@ __global__ __launch_bounds__(256) void k_pack(const uint8_t* ascii, const int64_
     }
   }
 }
+// the 2-bit pack of n reads that lie on the device (c3_batch_stage; the text path of the post-processing step, c3_text.hip)
+extern "C" void c3k_launch_pack(const uint8_t* ascii, const int64_t* off, const int64_t* woff, int n, uint32_t* pk, int grid, hipStream_t s) {
+  hipLaunchKernelGGL(k_pack, dim3((unsigned)grid), dim3(256), 0, s, ascii, off, woff, n, pk);
+}
 // consensus of read r lives at arena[off[r] ..]; compact copies go to out[coff[r] .. coff[r+1]) (one wave per read)
 __global__ __launch_bounds__(256) void k_gather_cons(const char* arena, const int64_t* off, const int64_t* coff, int n, char* out) {
   const int lane = threadIdx.x & 63;
@@ -165,6 +169,7 @@ extern "C" void c3_destroy(c3_handle* h) {
   if (h->ev_emit_dn) (void)hipEventDestroy(h->ev_emit_dn);
   if (h->h_emit_sizes) (void)hipHostFree(h->h_emit_sizes);
   if (h->h_fa_hdr) (void)hipHostFree(h->h_fa_hdr);
+  c3h::post_text_free(h);
   if (h->h_tot) (void)hipHostFree(h->h_tot);
   delete h;
 }
@@ -227,8 +232,7 @@ extern "C" int c3_batch_stage(c3_handle* h, int n, const char* seqs, const char*
   HIPCHK(hipMemcpyAsync(t.d_woff.p, t.woff.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, su));
   HIPCHK(hipMemcpyAsync(t.d_strand.p, t.strand.data(), n, hipMemcpyHostToDevice, su));
   HIPCHK(hipMemcpyAsync(t.d_sid.p, t.sid.data(), sizeof(int16_t) * n, hipMemcpyHostToDevice, su));
-  dim3 g((unsigned)std::min((n + 3) / 4, h->n_cus * 32));
-  hipLaunchKernelGGL(k_pack, g, dim3(256), 0, su, t.d_ascii.as<uint8_t>(), t.d_off.as<int64_t>(), t.d_woff.as<int64_t>(), n, t.d_pk.as<uint32_t>());
+  c3k_launch_pack(t.d_ascii.as<uint8_t>(), t.d_off.as<int64_t>(), t.d_woff.as<int64_t>(), n, t.d_pk.as<uint32_t>(), std::min((n + 3) / 4, h->n_cus * 32), su);
   HIPCHK(hipEventRecord(h->ev_up[1], su));
   HIPCHK(hipGetLastError());
   t.pending = true;

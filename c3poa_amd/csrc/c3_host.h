@@ -6,6 +6,8 @@
 #include "c3_launch.h"
 #include "c3_checks.h"
 #include "c3_emit.h"
+#include "c3_post.h"
+#include "c3_fastx.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -23,6 +25,12 @@ int qv_scratch(c3_handle* h, long long max_m, long long max_n, int n_items, QvAr
 int fetch_msa_rows(c3_handle* h, int read, int nrows, char* out, int64_t cap, int* msa_len);           // c3_handle.hip
 struct EmitBufs;
 int emit_run(c3_handle* h, EmitArgs& p, EmitBufs& eb, hipStream_t s, std::vector<int64_t>& so, int64_t cap);          // c3_scans.hip
+// k_post in two halves on a batch whose arrays (p.n, p.names .. p.table) lie on the device; k_adapter on such a batch (c3_scans.hip)
+int post_sizes(c3_handle* h, const c3_post_args* a, PostArgs& p, std::vector<int64_t>& so);
+int post_write(c3_handle* h, PostArgs& p, int64_t need);
+int adapters_device(c3_handle* h, const C3Batch& b, int64_t max_len, int32_t* d_out);
+int bgzf_inflate_to_device(c3_bgzf* z, const char* src, int64_t n, int64_t nm, uint8_t* d_dst, int64_t* out_len);    // c3_stream.hip
+void post_text_free(c3_handle* h);                                                                                     // c3_text.hip
 }
 
 #define BGZF_CHUNK_BLOCKS 2048                   // BGZF blocks per device chunk of a compression (c3_stream.hip, c3_batch_emit_fetch)
@@ -65,6 +73,17 @@ struct DBuf {                                   // owns one device allocation (m
 // k_emit_len / the scans / k_emit_write
 struct c3h::EmitBufs { DBuf work, offs, arena; hipEvent_t ev[5] = {}; };
 
+// the text path of the post-processing step (c3_text.hip): text[cur] holds the text of the last call, its bytes
+// [tail_from, text_n) being the unconsumed tail that goes in front of the next piece; the passes' tables and arenas; the inflater
+struct PostText {
+  DBuf text[2]; int cur = 0, kind = 0; int64_t text_n = 0, tail_from = 0;
+  DBuf cnt, nl, slen, nlen, bsum, hdr, lhdr, off, name_off, woff, src, hash, names, seqs, quals, pk, table;
+  DBuf zin, zslots, zsizes, zpacked;
+  C3FxHdr* h_hdr = nullptr; C3FqHdr* h_lhdr = nullptr; int* h_sizes = nullptr; c3_bgzf* z = nullptr;
+  hipEvent_t ev[8] = {};
+  c3_post_text_timing tm = {};
+};
+
 struct Summary { int status, n_sub, max_sub, sum_sub, max_dang, front, tail, n_peaks; };
 enum { EV_N = 10 };
 struct c3_handle {
@@ -95,6 +114,7 @@ struct c3_handle {
   DBuf d_qv, s_qv_dirs, s_qv_g, d_qv_cnt, d_gather_qv;                // QV stage: QV arena (like d_cons), direction slots, long-consensus slots, counters, snapshot
   hipEvent_t ev_qv[2] = {nullptr, nullptr}; c3_qv_timing qtm = {}; bool snap_qv = false;
   DBuf d_post[16]; hipEvent_t ev_post[5] = {}; c3_post_timing ptm = {};       // k_post: inputs, descriptors, pass buffers, arena; event times of the last call
+  PostText pt;
   // k_fasta: text, tables, arenas, output; event times of the last c3_demux_emit; page-locked copy of the device header
   DBuf d_fa[20]; hipEvent_t ev_fa[10] = {}; c3_demux_timing dtm = {}; struct C3FaHdr* h_fa_hdr = nullptr;
   // k_emit: inputs of c3_emit_group and its pass buffers; times of the last c3_emit_group / delivered emit snapshot

@@ -50,19 +50,31 @@ extern "C" int c3_scan_adapters(c3_handle* h, int32_t* out) {
   if (!h || h->n <= 0 || h->n_spl <= 0 || !out) return C3_E_STATE;
   HIPCHK(hipSetDevice(h->cfg.device));
   const size_t items = (size_t)h->n * h->n_spl * 2;
-  const long long dcap = (long long)(h->maxL + 1) * (h->max_spl + 1) + 64;
-  const int grid = (int)std::min<size_t>(items, (size_t)h->n_cus * 16);
-  DBuf res, dd;
-  HIPCHK(res.ensure(sizeof(int32_t) * 12 * items)); HIPCHK(dd.ensure((size_t)dcap * grid));
-  HIPCHK(zero_cnt(h, &dev_cnt(h)->queue));
-  AdapterArgs a; memset(&a, 0, sizeof(a));
-  a.b = dev_batch(h); a.p = dev_params(h->cfg); a.cnt = dev_cnt(h);
-  a.ad_codes = h->d_sp_codes.as<uint8_t>(); a.ad_len = h->d_sp_len.as<int>(); a.n_ad = h->n_spl;
-  a.D = dd.as<uint8_t>(); a.dcap = dcap; a.out = res.as<int32_t>();
-  c3k_launch_adapter(&a, grid, h->stream);
-  HIPCHK(hipGetLastError());
+  DBuf res;
+  HIPCHK(res.ensure(sizeof(int32_t) * 12 * items));
+  const int rc = c3h::adapters_device(h, dev_batch(h), h->maxL, res.as<int32_t>());
+  if (rc != C3_E_OK) return rc;
   HIPCHK(hipMemcpyAsync(out, res.p, sizeof(int32_t) * 12 * items, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  return C3_E_OK;
+}
+// k_adapter over the batch b (on the device, longest read max_len) against the splint table, queued on the handle's stream:
+// d_out[b.n * n_spl * 2][12] stays on the device.  The direction bytes live until the stream has run the kernel.
+int c3h::adapters_device(c3_handle* h, const C3Batch& b, int64_t max_len, int32_t* d_out) {
+  const size_t items = (size_t)b.n * h->n_spl * 2;
+  const long long dcap = (long long)(max_len + 1) * (h->max_spl + 1) + 64;
+  const int grid = (int)std::min<size_t>(items, (size_t)h->n_cus * 16);
+  DBuf dd;
+  HIPCHK(dd.ensure((size_t)dcap * grid));
+  HIPCHK(h->d_counter.ensure(sizeof(C3Counters)));
+  HIPCHK(zero_cnt(h, &dev_cnt(h)->queue));
+  AdapterArgs a; memset(&a, 0, sizeof(a));
+  a.b = b; a.p = dev_params(h->cfg); a.cnt = dev_cnt(h);
+  a.ad_codes = h->d_sp_codes.as<uint8_t>(); a.ad_len = h->d_sp_len.as<int>(); a.n_ad = h->n_spl;
+  a.D = dd.as<uint8_t>(); a.dcap = dcap; a.out = d_out;
+  c3k_launch_adapter(&a, grid, h->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));        // (dd is freed on return)
   return C3_E_OK;
 }
 
@@ -94,35 +106,66 @@ extern "C" int c3_match_index_batch(c3_handle* h, int n, const char* pieces, con
 extern "C" int c3_post_emit(c3_handle* h, const c3_post_args* a, char* arena, int64_t cap, int64_t* stream_off, int64_t* n_kept) {
   if (!h) return C3_E_ARG;
   const double t_call = dbg_now_ms();
-  const int rc = c3_post_check_args("c3_post_emit", a, arena, cap, stream_off, n_kept);
+  int rc = c3_post_check_args("c3_post_emit", a, arena, cap, stream_off, n_kept);
   if (rc != C3_E_OK) return c3_fail(h, rc, c3_last_error(nullptr));
   HIPCHK(hipSetDevice(h->cfg.device));
-  for (hipEvent_t& ev : h->ev_post) if (!ev) HIPCHK(hipEventCreate(&ev));
   PostArgs p; memset(&p, 0, sizeof(p));
-  p.n = a->n; p.S = 3 * a->n_dest + 3;
-  p.o.n_ad = a->n_ad; p.o.class5 = a->class5; p.o.undirectional = a->undirectional != 0; p.o.trim = a->trim != 0; p.o.barcoded = a->barcoded != 0;
-  p.o.quals = a->quals != nullptr; p.o.has_index = a->has_index != 0; p.o.n_idx = a->has_index ? a->n_idx : 0; p.o.n_dest = a->n_dest;
-  const int S = p.S, n = a->n, nb = (n + 255) / 256;
+  const int S = 3 * a->n_dest + 3, n = a->n;
   const size_t sb = n ? (size_t)a->off[n] : 0, nmb = n ? (size_t)a->name_off[n] : 0, tb = sizeof(int32_t) * 24 * (size_t)n * a->n_ad;
-  const size_t anb = a->n_ad ? (size_t)a->ad_name_off[a->n_ad] : 0, ib = p.o.n_idx ? (size_t)a->idx_off[p.o.n_idx] : 0;
   // every input buffer keeps 16 bytes of slack: the dword copies of k_post_emit read whole aligned dwords
-  struct Up { const void* src; size_t bytes; } up[13] = {
+  struct Up { const void* src; size_t bytes; } up[6] = {
     {a->names, nmb}, {a->name_off, sizeof(int64_t) * (n + 1)}, {a->seqs, sb}, {a->quals, a->quals ? sb : 0}, {a->off, sizeof(int64_t) * (n + 1)},
-    {a->table, tb}, {a->ad_len, sizeof(int32_t) * a->n_ad}, {a->ad_class, sizeof(int32_t) * a->n_ad}, {a->ad_names, anb},
-    {a->ad_name_off, a->n_ad ? sizeof(int64_t) * (a->n_ad + 1) : 0}, {a->idx_cat, ib}, {a->idx_off, p.o.n_idx ? sizeof(int64_t) * (p.o.n_idx + 1) : 0},
-    {a->idx_dest, sizeof(int32_t) * p.o.n_idx}};
+    {a->table, tb}};
   DBuf* d = h->d_post;
-  for (int k = 0; k < 13; ++k) {
+  for (int k = 0; k < 6; ++k) {
     HIPCHK(d[k].ensure(up[k].bytes + 16));
     if (n > 0 && up[k].bytes) HIPCHK(hipMemcpyAsync(d[k].p, up[k].src, up[k].bytes, hipMemcpyHostToDevice, h->stream));
   }
-  DBuf& work = d[13]; DBuf& offs = d[14]; DBuf& out = d[15];
+  p.n = n;
+  p.names = d[0].as<uint8_t>(); p.name_off = d[1].as<int64_t>(); p.seqs = d[2].as<uint8_t>(); p.quals = a->quals ? d[3].as<uint8_t>() : nullptr;
+  p.off = d[4].as<int64_t>(); p.table = d[5].as<int32_t>();
+  std::vector<int64_t> so;
+  if ((rc = c3h::post_sizes(h, a, p, so)) != C3_E_OK) return rc;
+  const int64_t need = so[S];
+  memcpy(stream_off, so.data(), sizeof(int64_t) * (S + 1));
+  *n_kept = so[S + 1];
+  h->ptm = c3_post_timing{};
+  if (need > cap) return c3_fail(h, C3_E_LIMIT, "c3_post_emit: arena too small (bytes needed in stream_off[S])");
+  if ((rc = c3h::post_write(h, p, need)) != C3_E_OK) return rc;
+  if (need) HIPCHK(hipMemcpyAsync(arena, h->d_post[15].p, (size_t)need, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipEventElapsedTime(&h->ptm.ms_classify, h->ev_post[0], h->ev_post[1]));
+  HIPCHK(hipEventElapsedTime(&h->ptm.ms_scan, h->ev_post[1], h->ev_post[2]));
+  HIPCHK(hipEventElapsedTime(&h->ptm.ms_emit, h->ev_post[3], h->ev_post[4]));
+  h->ptm.n_reads = n; h->ptm.n_kept = so[S + 1]; h->ptm.in_bytes = (int64_t)(nmb + sb * (a->quals ? 2 : 1) + tb); h->ptm.out_bytes = need;
+  h->ptm.ms_call = (float)(dbg_now_ms() - t_call);
+  return C3_E_OK;
+}
+// The first half of k_post on a batch whose arrays lie on the device (p.n, p.names, p.name_off, p.seqs, p.quals, p.off and
+// p.table set by the caller): the descriptors of `a` uploaded, classify + scans, and so[S + 2] (stream starts, total, kept
+// reads) read back and checked.  c3_post_emit and the text path (c3_text.hip) share it.
+int c3h::post_sizes(c3_handle* h, const c3_post_args* a, PostArgs& p, std::vector<int64_t>& so) {
+  for (hipEvent_t& ev : h->ev_post) if (!ev) HIPCHK(hipEventCreate(&ev));
+  p.S = 3 * a->n_dest + 3;
+  p.o.n_ad = a->n_ad; p.o.class5 = a->class5; p.o.undirectional = a->undirectional != 0; p.o.trim = a->trim != 0; p.o.barcoded = a->barcoded != 0;
+  p.o.quals = p.quals != nullptr; p.o.has_index = a->has_index != 0; p.o.n_idx = a->has_index ? a->n_idx : 0; p.o.n_dest = a->n_dest;
+  const int S = p.S, n = p.n, nb = (n + 255) / 256;
+  const size_t anb = a->n_ad ? (size_t)a->ad_name_off[a->n_ad] : 0, ib = p.o.n_idx ? (size_t)a->idx_off[p.o.n_idx] : 0;
+  struct Up { const void* src; size_t bytes; } up[7] = {
+    {a->ad_len, sizeof(int32_t) * a->n_ad}, {a->ad_class, sizeof(int32_t) * a->n_ad}, {a->ad_names, anb},
+    {a->ad_name_off, a->n_ad ? sizeof(int64_t) * (a->n_ad + 1) : 0}, {a->idx_cat, ib}, {a->idx_off, p.o.n_idx ? sizeof(int64_t) * (p.o.n_idx + 1) : 0},
+    {a->idx_dest, sizeof(int32_t) * p.o.n_idx}};
+  DBuf* d = h->d_post;
+  for (int k = 0; k < 7; ++k) {
+    HIPCHK(d[6 + k].ensure(up[k].bytes + 16));
+    if (n > 0 && up[k].bytes) HIPCHK(hipMemcpyAsync(d[6 + k].p, up[k].src, up[k].bytes, hipMemcpyHostToDevice, h->stream));
+  }
+  DBuf& work = d[13]; DBuf& offs = d[14];
   // work = dec [n] | len [n][6] | roff [n][6] | bsum [nb][S + 1]
   const size_t w_dec = 0, w_len = w_dec + sizeof(C3PostDec) * n, w_roff = w_len + sizeof(int64_t) * C3_POST_REC * n, w_bsum = w_roff + sizeof(int64_t) * C3_POST_REC * n;
   HIPCHK(work.ensure(w_bsum + sizeof(long long) * (size_t)(nb + 1) * (S + 1)));
   HIPCHK(offs.ensure(sizeof(int64_t) * (S + 2)));
-  p.names = d[0].as<uint8_t>(); p.name_off = d[1].as<int64_t>(); p.seqs = d[2].as<uint8_t>(); p.quals = a->quals ? d[3].as<uint8_t>() : nullptr;
-  p.off = d[4].as<int64_t>(); p.table = d[5].as<int32_t>(); p.ad_len = d[6].as<int32_t>(); p.ad_class = d[7].as<int32_t>();
+  p.ad_len = d[6].as<int32_t>(); p.ad_class = d[7].as<int32_t>();
   p.ad_names = d[8].as<uint8_t>(); p.ad_name_off = d[9].as<int64_t>(); p.idx_cat = d[10].as<uint8_t>(); p.idx_off = d[11].as<int64_t>();
   p.idx_dest = d[12].as<int32_t>();
   p.dec = (C3PostDec*)(work.as<uint8_t>() + w_dec); p.len = (int64_t*)(work.as<uint8_t>() + w_len); p.roff = (int64_t*)(work.as<uint8_t>() + w_roff);
@@ -133,29 +176,23 @@ extern "C" int c3_post_emit(c3_handle* h, const c3_post_args* a, char* arena, in
   c3k_launch_post_scan(&p, h->stream);
   HIPCHK(hipEventRecord(h->ev_post[2], h->stream));
   HIPCHK(hipGetLastError());
-  std::vector<int64_t> so((size_t)S + 2);
+  so.assign((size_t)S + 2, 0);
   HIPCHK(hipMemcpyAsync(so.data(), offs.p, sizeof(int64_t) * (S + 2), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   int64_t need = 0;                                              // the sums come from lengths the rule bounds: anything else is a kernel fault
   for (int s = 0; s <= S; ++s) { if (so[s] < need) return c3_fail(h, C3_E_HIP, "k_post: stream offsets out of order"); need = so[s]; }
   if (so[0] != 0 || so[S + 1] < 0 || so[S + 1] > n) return c3_fail(h, C3_E_HIP, "k_post: header out of range");
-  memcpy(stream_off, so.data(), sizeof(int64_t) * (S + 1));
-  *n_kept = so[S + 1];
-  h->ptm = c3_post_timing{};
-  if (need > cap) return c3_fail(h, C3_E_LIMIT, "c3_post_emit: arena too small (bytes needed in stream_off[S])");
-  HIPCHK(out.ensure((size_t)need + 16));
+  return C3_E_OK;
+}
+// The second half: the records of the batch written into d_post[15] (`need` = so[S] bytes), queued on the handle's stream.
+int c3h::post_write(c3_handle* h, PostArgs& p, int64_t need) {
+  DBuf& out = h->d_post[15];
+  HIPCHK(out.ensure((size_t)need + 256));                         // (256: what k_bgzf may read behind a stream, c3_text.hip)
   p.arena = out.as<uint8_t>();
   HIPCHK(hipEventRecord(h->ev_post[3], h->stream));
   c3k_launch_post_emit(&p, h->stream);
   HIPCHK(hipEventRecord(h->ev_post[4], h->stream));
   HIPCHK(hipGetLastError());
-  if (need) HIPCHK(hipMemcpyAsync(arena, out.p, (size_t)need, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipEventElapsedTime(&h->ptm.ms_classify, h->ev_post[0], h->ev_post[1]));
-  HIPCHK(hipEventElapsedTime(&h->ptm.ms_scan, h->ev_post[1], h->ev_post[2]));
-  HIPCHK(hipEventElapsedTime(&h->ptm.ms_emit, h->ev_post[3], h->ev_post[4]));
-  h->ptm.n_reads = n; h->ptm.n_kept = so[S + 1]; h->ptm.in_bytes = (int64_t)(nmb + sb * (a->quals ? 2 : 1) + tb); h->ptm.out_bytes = need;
-  h->ptm.ms_call = (float)(dbg_now_ms() - t_call);
   return C3_E_OK;
 }
 extern "C" int c3_post_emit_timing(c3_handle* h, c3_post_timing* t) {

@@ -144,6 +144,10 @@ static int bgzf_inflate_members(c3_bgzf* z, const char* src, int64_t n, int64_t 
   return C3_E_OK;
 }
 
+int c3h::bgzf_inflate_to_device(c3_bgzf* z, const char* src, int64_t n, int64_t nm, uint8_t* d_dst, int64_t* out_len) {
+  return bgzf_inflate_members(z, src, n, nm, d_dst, nullptr, out_len);
+}
+
 extern "C" int c3_bgzf_decompress(c3_bgzf* z, const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len) {
   if (!z || !out_len || n < 0 || (n > 0 && !src)) return host_fail(C3_E_ARG, "c3_bgzf_decompress: bad arguments");
   *out_len = 0;

@@ -25,12 +25,11 @@
 #include "c3_dev.h"
 #include "c3_fastq.h"
 #include "c3_launch.h"
+#include "k_text.h"
 
 #define FQ_TILE 65536u
-#define FQ_WAVES 4
 #define FQ_SUB (FQ_TILE / FQ_WAVES)
 #define FQ_STEP 1024u                 // 64 lanes x 16 bytes
-#define FQ_LONG 32768                 // sequence bytes above which the workgroup shares a record
 
 // 0x80 in every byte of w that is '\n' (exact: no borrow runs into the neighbouring byte)
 __device__ __forceinline__ uint32_t fq_nlmask(uint32_t w) {
@@ -66,20 +65,6 @@ __global__ __launch_bounds__(64 * FQ_WAVES) void k_fastq_count(const uint8_t* bu
     for (uint32_t s = 0; s < FQ_SUB; s += FQ_STEP) c += __popc(fq_lane_mask(buf, base + s + 16u * lane, lo, hi));
   c = wave_scan_add(c);
   if (lane == 63) cnt[blockIdx.x * FQ_WAVES + wv] = c;
-}
-
-// exclusive scan over the 256 lanes of a workgroup; every lane calls it
-template <class T> __device__ __forceinline__ T fq_block_excl(T v, T* lds, T* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  T inc = v;
-  for (int d = 1; d < 64; d <<= 1) { const T t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
-  __syncthreads();                                       // (lds is reused from one call to the next)
-  if (lane == 63) lds[wv] = inc;
-  __syncthreads();
-  T base = 0, tot = 0;
-  for (int k = 0; k < FQ_WAVES; ++k) { const T x = lds[k]; if (k < wv) base += x; tot += x; }
-  *total = tot;
-  return base + inc - v;
 }
 
 // cnt[0..m) -> exclusive prefix sums, in place; the header gets the line counts and is made ready for k_fastq_records
@@ -198,21 +183,6 @@ __global__ __launch_bounds__(256) void k_fastq_rfin(const int32_t* slen, const i
   name_off[i] = bsum[3 * blockIdx.x + 2] + en;
   const int32_t b0 = r == 0 ? (int32_t)lo : nl[4 * r - 1] + 1;
   src[i] = make_int4(nl[4 * r] + 1, nl[4 * r + 2] + 1, b0 + 1, 0);        // sequence, quality, name
-}
-
-// dst[0..len) = src[0..len) by the 64 lanes of a wave, any alignment on either side
-__device__ __forceinline__ void fq_wave_copy(uint8_t* dst, const uint8_t* src, uint32_t len, int lane) {
-  const uint32_t head = min(len, (uint32_t)((4u - ((uintptr_t)dst & 3u)) & 3u));
-  if ((uint32_t)lane < head) dst[lane] = src[lane];
-  const uint32_t nd = (len - head) >> 2;
-  uint32_t* d4 = (uint32_t*)(dst + head);
-  const uint8_t* s = src + head;
-  const uint32_t sh = (uint32_t)((uintptr_t)s & 3u);
-  const uint32_t* sa = (const uint32_t*)(s - sh);
-  if (sh == 0) { for (uint32_t k = (uint32_t)lane; k < nd; k += 64u) d4[k] = sa[k]; }
-  else         { for (uint32_t k = (uint32_t)lane; k < nd; k += 64u) d4[k] = __builtin_amdgcn_alignbyte(sa[k + 1], sa[k], sh); }   // sa[k + 1] holds byte s + 4k + 3 at least
-  const uint32_t done = head + 4u * nd, tail = len - done;
-  if ((uint32_t)lane < tail) dst[done + lane] = src[done + lane];
 }
 
 __global__ __launch_bounds__(64 * FQ_WAVES) void k_fastq_gather(const uint8_t* buf, const int4* src, const int64_t* off, const int64_t* name_off,

@@ -7,6 +7,7 @@ same information from k_adapter (c3_scan_adapters) and writes the same `adapter_
 native c3_match_index.  Output files and record formats follow write_fasta_file (:287-398).
 """
 import gzip
+import json
 import os
 import shutil
 import sys
@@ -229,10 +230,13 @@ def run(args):
         idx_to_seq, seq_to_idx = {}, {}
     psl = args.output_path + PSL_NAME
     keep_quals = bool(getattr(args, "keep_quals", False))
+    bgzf = bool(getattr(args, "bgzf", False))
     if getattr(args, "emit", "host") == "gpu":
-        n = run_emit_gpu(args, idx_to_seq, seq_to_idx, psl, keep_quals)
+        n = run_emit_text(args, idx_to_seq, seq_to_idx, psl, keep_quals) if getattr(args, "parse", "host") == "gpu" else None
+        if n is None:
+            n = run_emit_gpu(args, idx_to_seq, seq_to_idx, psl, keep_quals)
         if n is not None:
-            _multiprocess_conventions(args, idx_to_seq, ".fastq" if keep_quals else ".fasta")
+            _multiprocess_conventions(args, idx_to_seq, ".fastq" if keep_quals else ".fasta", ".gz" if bgzf else "")
             return n
         if keep_quals:
             sys.exit("--keep-quals needs the device path (--emit gpu), which this run cannot take (see the note above)")
@@ -246,13 +250,50 @@ def run(args):
         print("Reading existing psl file", file=sys.stderr)
     adapter_dict = parse_blat(psl, reads)
     n = write_fasta_file(args, args.output_path, adapter_dict, reads, seq_to_idx, idx_to_seq)
-    _multiprocess_conventions(args, idx_to_seq, ".fasta")
+    if bgzf:                                                    # the files of the fallback leave as BGZF all the same
+        _bgzf_tree(args.output_path, idx_to_seq)
+    _multiprocess_conventions(args, idx_to_seq, ".fasta", ".gz" if bgzf else "")
     return n
 
 
-def _multiprocess_conventions(args, idx_to_seq, suffix):
+BGZF_PIECE = 1024 * _lib.BGZF_BLOCK                            # text bytes per c3_bgzf_compress call of _bgzf_file: whole members
+
+
+def _bgzf_finish(paths):
+    """the EOF member behind every member chain of --bgzf (a file that got no record holds nothing else)"""
+    for p in paths:
+        with open(p, "ab") as fh:
+            fh.write(_lib.BGZF_EOF)
+
+
+def _bgzf_file(z, path):
+    """path -> path.gz: its text through c3_bgzf_compress piece by piece, then the EOF member; the plain file goes"""
+    with open(path, "rb") as src, open(path + ".gz", "wb") as dst:
+        while True:
+            piece = src.read(BGZF_PIECE)
+            if not piece:
+                break
+            dst.write(z.compress(piece))
+        dst.write(_lib.BGZF_EOF)
+    os.remove(path)
+
+
+def _bgzf_tree(path, idx_to_seq):
+    """--bgzf after a fallback to the host path: every read file it wrote (three per destination, the 10x file) compressed
+    by k_bgzf file by file; the TSV and the PSL stay plain"""
+    dirs = [path + idx + "/" for idx in list(idx_to_seq) + ["no_index_found"]] if idx_to_seq else [path]
+    found = [d + nm for d in dirs for nm in (FLC, FLC_LEFT, FLC_RIGHT)] + [path + FLC_10X]
+    found = [p for p in found if os.path.exists(p)]
+    if found:
+        z = _lib.Bgzf()
+        for p in found:
+            _bgzf_file(z, p)
+        z.close()
+
+
+def _multiprocess_conventions(args, idx_to_seq, suffix, gz=""):
     """the end of main() with -n > 1 (:165-214): every destination holds every file, -co compresses them.  suffix: .fasta, or
-    .fastq for the three read files under --keep-quals"""
+    .fastq for the three read files under --keep-quals; gz: ".gz" under --bgzf, where a missing file is the EOF member alone"""
     if args.threads > 1:
         names = [nm[:-len(".fasta")] + suffix for nm in (FLC, FLC_LEFT, FLC_RIGHT)]
         dirs = [args.output_path]
@@ -263,6 +304,10 @@ def _multiprocess_conventions(args, idx_to_seq, suffix):
         for d in dirs:                                          # chunk_process cats into every destination (:165-214)
             os.makedirs(d, exist_ok=True)
             for nm in names:
+                if gz:
+                    if not os.path.exists(d + nm + gz):
+                        _bgzf_finish([d + nm + gz])
+                    continue
                 if not os.path.exists(d + nm):
                     open(d + nm, "w").close()
                 if args.compress_output:
@@ -301,7 +346,8 @@ def run_emit_gpu(args, idx_to_seq, seq_to_idx, psl, keep_quals):
     (c3_post_emit); only finished file bytes come back.  Returns the number of reads written, or None after a one-line note on
     stderr when the run has to take the host path (which gives the same files): a PSL to reuse, two records with one name
     (the host's dict collapses them), a byte >= 0x80 (Python cuts characters, the device bytes), or index sets beyond the
-    device limits."""
+    device limits.  Under --bgzf the read streams (three per destination, the 10x file) are compressed by k_bgzf
+    (c3_bgzf_compress) before they are appended to <name>.gz, and every such file ends in one EOF member."""
     def fallback(why):
         print("--emit gpu: %s; using the host path" % why, file=sys.stderr)
 
@@ -342,7 +388,8 @@ def run_emit_gpu(args, idx_to_seq, seq_to_idx, psl, keep_quals):
         return fallback("two records share a name")
     # the files as write_fasta_file opens them
     suffix = ".fastq" if keep_quals else ".fasta"
-    files = [nm[:-len(".fasta")] + suffix for nm in (FLC, FLC_LEFT, FLC_RIGHT)]
+    gz = ".gz" if getattr(args, "bgzf", False) else ""
+    files = [nm[:-len(".fasta")] + suffix + gz for nm in (FLC, FLC_LEFT, FLC_RIGHT)]
     if plan.has_index:
         for idx in idx_to_seq:
             if os.path.exists(path + idx):
@@ -352,9 +399,11 @@ def run_emit_gpu(args, idx_to_seq, seq_to_idx, psl, keep_quals):
         for nm in files:
             open(path + nm, "w").close()
     if args.barcoded:
-        open(path + FLC_10X, "w").close()
-    targets = [path + (d + "/" if plan.has_index else "") + nm for d in plan.dests for nm in files] + [path + FLC_10X, path + MUX_TSV, psl + ".part"]
+        open(path + FLC_10X + gz, "w").close()
+    targets = [path + (d + "/" if plan.has_index else "") + nm for d in plan.dests for nm in files] + [path + FLC_10X + gz, path + MUX_TSV, psl + ".part"]
+    n_read_streams = len(targets) - 2                       # everything but the TSV and the PSL
     open(psl + ".part", "w").close()
+    z = _lib.Bgzf() if gz else None
     h = _lib.Handle()
     h.set_splints([a[1] for a in adapters])
     kept = 0
@@ -372,7 +421,168 @@ def run_emit_gpu(args, idx_to_seq, seq_to_idx, psl, keep_quals):
             if so[s + 1] > so[s]:
                 os.makedirs(os.path.dirname(target), exist_ok=True)
                 with open(target, "ab") as fh:
-                    fh.write(arena[int(so[s]):int(so[s + 1])].data)
+                    if z is not None and s < n_read_streams:
+                        fh.write(z.compress(arena[int(so[s]):int(so[s + 1])].tobytes()))
+                    else:
+                        fh.write(arena[int(so[s]):int(so[s + 1])].data)
     h.close()
+    if z is not None:
+        z.close()
+        _bgzf_finish([t for t in targets[:n_read_streams] if os.path.exists(t)])
     os.replace(psl + ".part", psl)
+    return kept
+
+
+def _is_bgzf(head):
+    """the first 18 bytes of a file are a BGZF member header (gzip with the 'BC' extra field first)"""
+    return len(head) >= 18 and head[:4] == b"\x1f\x8b\x08\x04" and head[10:12] == b"\x06\x00" and head[12:16] == b"BC\x02\x00"
+
+
+def _bgzf_whole_members(buf):
+    """bytes of buf that are whole BGZF members (walked by the BSIZE field; c3_bgzf_scan then vouches for them)"""
+    at = 0
+    while at + 18 <= len(buf):
+        size = int.from_bytes(buf[at + 16:at + 18], "little") + 1
+        if not _is_bgzf(buf[at:at + 18]) or at + size > len(buf):
+            break
+        at += size
+    return at
+
+
+def _text_pieces(path, chunk, inflate_gpu):
+    """(piece, at_eof, in_bgzf) of the input in pieces of about `chunk` bytes: plain text as it stands; a BGZF file cut at member
+    boundaries when the device inflates; any other .gz (and BGZF without --inflate gpu) through zlib on the host"""
+    with open(path, "rb") as fh:
+        head = fh.read(18)
+    gz = head[:2] == b"\x1f\x8b"
+    in_bgzf = gz and inflate_gpu and _is_bgzf(head)
+    fh = gzip.open(path, "rb") if gz and not in_bgzf else open(path, "rb")
+    with fh:
+        buf, done = b"", False
+        while not done:
+            more = fh.read(chunk)
+            done = not more
+            buf += more
+            if in_bgzf:
+                k = _bgzf_whole_members(buf)
+                if done and k != len(buf):
+                    raise _lib.C3Error("%s: the BGZF file ends inside a member" % path)
+                if k == 0 and not done:
+                    continue                                    # a member longer than the chunk: read on
+                if not done:
+                    nxt = fh.read(1)                            # is anything left?  (at_eof goes with the last members)
+                    if nxt:
+                        rest = buf[k:] + nxt
+                    else:
+                        done, rest = True, buf[k:]
+                        if rest:
+                            raise _lib.C3Error("%s: the BGZF file ends inside a member" % path)
+                    piece, buf = buf[:k], rest
+                else:
+                    piece, buf = buf, b""
+                yield piece, done, True
+            else:
+                if not done:
+                    nxt = fh.read(1)
+                    if not nxt:
+                        done = True
+                    piece, buf = buf, nxt
+                else:
+                    piece, buf = buf, b""
+                yield piece, done, False
+
+
+def run_emit_text(args, idx_to_seq, seq_to_idx, psl, keep_quals):
+    """--emit gpu --parse gpu: the input goes to the device as text (or, with --inflate gpu, as BGZF members) in pieces of
+    --post-chunk bytes; c3_post_emit_text parses, aligns, classifies and formats there and returns file bytes, which are
+    appended to .part files that take their names at the end.  Returns the number of reads written, or None after a one-line
+    note on stderr when the run has to take the batch path of --emit gpu instead (which gives the same files and keeps its own
+    fallbacks): a departure from the strict record rule, two records with one name hash, a refusal of the call, a PSL to
+    reuse, a plain-gzip input under --inflate gpu."""
+    stats = {"records_device": 0, "calls": 0, "inflated_bytes": 0, "fallback": True}
+
+    def fallback(why):
+        print("--parse gpu: %s; using the batch path of --emit gpu" % why, file=sys.stderr)
+        if getattr(args, "emit_stats", False):
+            print(json.dumps(stats), file=sys.stderr)
+
+    path = args.output_path
+    inflate_gpu = getattr(args, "inflate", "host") == "gpu"
+    if os.path.exists(psl) and os.stat(psl).st_size > 0:
+        return fallback("%s exists and is reused" % PSL_NAME)
+    adapters = [(r[0], r[1]) for r in fastx_read(args.adapter_file)]
+    if any(a[0] == "-" for a in adapters) or "-" in idx_to_seq:
+        return fallback("an adapter or index is named '-' (the host path's placeholder)")
+    with open(args.input_fasta_file, "rb") as fh:
+        head = fh.read(18)
+    if inflate_gpu and head[:2] == b"\x1f\x8b" and not _is_bgzf(head):
+        return fallback("%s is gzip but not BGZF, which the device does not inflate" % args.input_fasta_file)
+    plan = _lib.PostPlan(adapters, (idx_to_seq, seq_to_idx) if seq_to_idx else None, undirectional=args.undirectional,
+                         trim=args.trim, barcoded=args.barcoded)
+    suffix = ".fastq" if keep_quals else ".fasta"
+    gz = ".gz" if getattr(args, "bgzf", False) else ""
+    files = [nm[:-len(".fasta")] + suffix + gz for nm in (FLC, FLC_LEFT, FLC_RIGHT)]
+    targets = [path + (d + "/" if plan.has_index else "") + nm for d in plan.dests for nm in files] + [path + FLC_10X + gz, path + MUX_TSV, psl]
+    n_read_streams = len(targets) - 2
+    if plan.has_index:
+        for idx in idx_to_seq:
+            if os.path.exists(path + idx):
+                shutil.rmtree(path + idx)
+    always = [psl] + ([path + MUX_TSV] if plan.has_index else [path + nm for nm in files]) + ([path + FLC_10X + gz] if args.barcoded else [])
+    parts = set()
+
+    def discard():
+        for t in parts:
+            if os.path.exists(t + ".part"):
+                os.remove(t + ".part")
+
+    h = _lib.Handle()
+    kept, hashes, why, bufs = 0, [], None, {}
+    try:
+        h.set_splints([a[1] for a in adapters])
+        for piece, at_eof, in_bgzf in _text_pieces(args.input_fasta_file, max(1, int(getattr(args, "post_chunk", 64 << 20))), inflate_gpu):
+            try:
+                res = h.post_emit_text(plan, piece, at_eof=at_eof, in_bgzf=in_bgzf, out_bgzf=bool(gz), keep_quals=keep_quals, bufs=bufs)
+            except _lib.C3Error as e:
+                if keep_quals and "C3_POST_KEEP_QUALS on a FASTA text" in str(e):
+                    discard()
+                    sys.exit("--keep-quals: the records of %s have no quality line" % args.input_fasta_file)
+                why = "the device call was refused (%s)" % str(e).split(": ", 1)[-1]
+                break
+            stats["calls"] += 1
+            stats["records_device"] += res.info["n_records"]
+            stats["inflated_bytes"] += res.info["text_bytes"] - (0 if stats["calls"] == 1 else tail)
+            tail = res.info["text_bytes"] - res.info["consumed"]
+            if res.info["departed"]:
+                why = "the input departs from the strict record rule behind record %d" % stats["records_device"]
+                break
+            kept += res.info["n_kept"]
+            hashes.append(res.hashes)
+            so = res.stream_off
+            for s, target in enumerate(targets):
+                if so[s + 1] > so[s]:
+                    os.makedirs(os.path.dirname(target), exist_ok=True)
+                    parts.add(target)
+                    with open(target + ".part", "ab") as fh:
+                        fh.write(res.arena[int(so[s]):int(so[s + 1])].data)
+    except _lib.C3Error as e:                                   # (the piece cutter: a BGZF file that ends inside a member)
+        why = str(e)
+    finally:
+        h.close()
+    if why is None and hashes and len(np.unique(np.concatenate(hashes))) < stats["records_device"]:
+        why = "two records share a name hash"
+    if why is not None:
+        discard()
+        return fallback(why)
+    for t in always:
+        if t not in parts:
+            parts.add(t)
+            open(t + ".part", "wb").close()
+    if gz:
+        _bgzf_finish([t + ".part" for t in parts if t in targets[:n_read_streams]])
+    for t in parts:
+        os.replace(t + ".part", t)
+    stats["fallback"] = False
+    if getattr(args, "emit_stats", False):
+        print(json.dumps(stats), file=sys.stderr)
     return kept

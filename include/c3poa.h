@@ -596,6 +596,65 @@ int c3_emit_timing_get(c3_handle* h, c3_emit_timing* t);
  * text naming the path and the system's reason.  Host code. */
 int c3_append_streams(const char* const* paths, const char* arena, const int64_t* stream_off, int n_streams);
 
+/* ---- Strict FASTA / FASTQ records (the input of C3POa_postprocessing.py) ----
+ * A text is STRICT of kind 4 (the four-line FASTQ rule of "FASTQ records on the GPU") or of kind 2, the two-line FASTA that
+ * C3POa.py writes: line 0 begins with '>'; line 1 is not empty and does not begin with '>', '@' or '+'.  The kind of a file is
+ * announced by its first byte ('@' = 4, '>' = 2; any other byte is a departure) and is an argument here.  Lines, the '\r' rule
+ * and the name rule (line 0 after its first byte, up to the first blank or tab) are those of the FASTQ rule; with
+ * at_eof != 0 the last line may lack its '\n'.  The rule is c3poa_amd/csrc/c3_fastx.h.
+ * The call parses the longest prefix of whole strict records: info->consumed is its byte length, always a record boundary.
+ * A record that is merely incomplete at the end of the text (at_eof == 0) is left unconsumed.  The first record that is not
+ * strict is a DEPARTURE: a blank line, an empty sequence line, a record of the other kind, a byte >= 0x80 anywhere in the
+ * record, an incomplete record with at_eof set, and a sequence of several lines (kind 2: the line behind the first sequence
+ * line stands where a header is due, so the departure lies behind that record's first two lines).  Parsing stops in front of
+ * it, departed = 1, and the records before it are delivered.  Every record is delivered (no minimum length):
+ * names / name_off[n_records + 1], seqs / quals / off[n_records + 1] as in c3_host_batch (quals may be NULL for kind 2 and is
+ * then not written; kind 4 needs it), name_hash[n_records] = the 64-bit FNV-1a of each name, as c3_fasta_parse gives it.
+ * n_records > max_records, name_bytes > names_cap or base_bytes > bases_cap return C3_E_LIMIT with the needed sizes in info
+ * and nothing written to the arrays; n > C3_FASTX_MAX_TEXT returns C3_E_LIMIT; null arguments and a kind other than 2 or 4
+ * return C3_E_ARG (text may be null when n == 0); n == 0 is success with all counts zero.  Host code; errors through
+ * c3_last_error(NULL). */
+#define C3_FASTX_MAX_TEXT 0x7FF00000
+typedef struct { int64_t n_records, consumed, name_bytes, base_bytes; int32_t departed; } c3_fastx_info;
+int c3_fastx_strict_parse_host(const char* text, int64_t n, int at_eof, int kind, char* names, int64_t names_cap,
+                               int64_t* name_off, char* seqs, char* quals, int64_t bases_cap, int64_t* off,
+                               uint64_t* name_hash, int64_t max_records, c3_fastx_info* info);
+
+/* ---- Post-processing, text in / file bytes out (C3POa_postprocessing.py --emit gpu --parse gpu) ----
+ * c3_post_emit_text (C3POa_postprocessing.py:145,218-227,229-398): consecutive pieces of one consensus file in, the streams of
+ * c3_post_emit out, with no text, base, adapter table or record visiting the host in between.  src holds plain text, or with
+ * C3_POST_IN_BGZF whole BGZF members (inflated by k_inflate under the rules of "BGZF input": C3_E_DATA on a damaged member).
+ * The handle keeps the unconsumed tail of the (inflated) text on the device and puts it in front of the next piece;
+ * at_eof != 0 ends the file; c3_post_text_reset drops the tail and forgets the file's kind.  The kind (2 or 4) is the one the
+ * file's first byte announces ("Strict FASTA / FASTQ records"); any other first byte is a departure.
+ * The text is parsed by the strict rule (k_fastx), its bases packed for k_adapter where they lie, aligned against the rows of
+ * c3_set_splints (which must equal plan->n_ad in number), classified, cut and formatted by k_post.  plan carries the adapter,
+ * index and option fields of c3_post_args; its batch fields (n, names .. off) and table are ignored.  Qualities reach the
+ * records only with C3_POST_KEEP_QUALS (kind 4; with kind 2: C3_E_ARG).
+ * Output: the S = 3 * n_dest + 3 streams of c3_post_emit for the delivered records, stream_off[S + 1].  With C3_POST_OUT_BGZF
+ * every non-empty stream among the 3 * n_dest read streams and the 10x stream is compressed by k_bgzf as one text (byte for
+ * byte c3_bgzf_compress_host of that stream); the TSV and PSL streams stay plain; stream_off describes what is delivered.
+ * Too small a cap: C3_E_LIMIT with stream_off filled (stream_off[S] = bytes needed; with C3_POST_OUT_BGZF the sum of
+ * c3_bgzf_bound over the compressed streams plus the plain ones) and the arena left alone.  name_hash[n_records]: the 64-bit
+ * FNV-1a of every delivered record's name; n_records > max_records: C3_E_LIMIT with info->n_records = the need.
+ * info: n_records delivered, n_kept written, text_bytes = tail + (inflated) piece, consumed = how many of them the delivered
+ * records cover, out_bytes, departed.  A departure delivers the records in front of it.  Whatever c3_batch_upload or
+ * c3_post_emit would refuse for such a batch is refused here with the same code.  Every refusal happens before anything is
+ * written to arena and leaves the kept tail as it was, so the same piece can be passed again.
+ * c3_post_text_timing: times of the last call -- host time of the inflation and of the compression loop, hipEvent times of
+ * the parse (with its two read-backs), gather + pack, k_adapter and k_post, host time of the call with its copies. */
+#define C3_POST_IN_BGZF   1   /* src holds whole BGZF members; inflated on the device (k_inflate rules, C3_E_DATA on damage) */
+#define C3_POST_OUT_BGZF  2   /* the read-file streams leave as BGZF members */
+#define C3_POST_KEEP_QUALS 4  /* kind 4 only; kind 2 with it: C3_E_ARG */
+typedef struct { int64_t n_records, n_kept, consumed, text_bytes, out_bytes; int32_t departed; } c3_post_text_info;
+typedef struct { float ms_inflate, ms_parse, ms_gather, ms_adapter, ms_post, ms_bgzf, ms_call;
+                 int64_t n_records, n_kept, in_bytes, text_bytes, out_bytes; } c3_post_text_timing;
+int c3_post_emit_text(c3_handle* h, const char* src, int64_t n, int at_eof, int flags, const c3_post_args* plan,
+                      char* arena, int64_t cap, int64_t* stream_off, uint64_t* name_hash, int64_t max_records,
+                      c3_post_text_info* info);
+int c3_post_text_reset(c3_handle* h);
+int c3_post_text_timing_get(c3_handle* h, c3_post_text_timing* t);
+
 #ifdef __cplusplus
 }
 #endif
