@@ -88,6 +88,7 @@ struct WinArgs {
   // takes its windows from `wlist`, their number from device memory (cnt->win_ovf) and its queue from cnt->win_queue2
   // (k_window<true>: the first launch's code carries none of this)
   const int* wlist; int* ovf_list;
+  int no_chain;                           // test hook C3_DEBUG_WIN_CHAIN=0: the first layer of a window takes the general graph phases too
 };
 // k_window scratch of one slot, bytes per region (each region is one buffer strided by slot): ints W_INTS * Ncap ints (WCtx::I,
 // 18 * Ncap + 9 used), edges 4 * Ncap * K ints, bases 2 * Ncap bytes (base, mask), score Ncap long longs, DP cells hcap * (4 bytes

@@ -385,6 +385,7 @@ static int run_polish(c3_handle* h, float* ms_prep, float* ms_win, float* ms_st)
     a.wout = h->d_wout.as<uint8_t>(); a.wout_cap = wout_cap;
     HIPCHK(zero_counters(h));
     if (const char* e = getenv("C3_DEBUG_BAND")) a.band_mode = !strcmp(e, "off") ? 1 : !strcmp(e, "fail") ? 2 : !strcmp(e, "verify") ? 3 : 0;    // test hook (tests/test_gpu_band.py)
+    if (const char* e = getenv("C3_DEBUG_WIN_CHAIN")) a.no_chain = !strcmp(e, "0");      // test hook (tests/test_gpu_win_chain.py)
     a.ovf_list = slots2 ? h->d_wovf.as<int>() : nullptr;
     c3k_launch_window(&a, slots, h->stream);
     HIPCHK(hipGetLastError());

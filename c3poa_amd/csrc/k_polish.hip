@@ -502,7 +502,7 @@ __device__ void w_blocks(WCtx& c, int lane) {
   }
   WSYNC();
 }
-__device__ void w_reorder(WCtx& c, int n_old, int lane, int* lds, int lds_cap) {
+__device__ void w_reorder(WCtx& c, int n_old, int lane, int* lds, int lds_cap, bool ident) {
   const int n_new = c.n - n_old;
   // old node at old index i moves to i + #(anchor < i); new node k goes to anchor[k] + 1 + k.  The (sorted) anchors of the new
   // nodes are staged in LDS first: the binary search per old node is then 6-8 LDS reads instead of 6-8 dependent global loads
@@ -513,7 +513,7 @@ __device__ void w_reorder(WCtx& c, int n_old, int lane, int* lds, int lds_cap) {
   for (int i0 = 0; i0 < n_old; i0 += 64 * WU) {
     int v[WU];
 #pragma unroll
-    for (int u = 0; u < WU; ++u) { const int i = i0 + 64 * u + lane; v[u] = i < n_old ? c.order()[i] : -1; }
+    for (int u = 0; u < WU; ++u) { const int i = i0 + 64 * u + lane; v[u] = i < n_old ? (ident ? i : c.order()[i]) : -1; }      // (ident: the old order is the identity -- the backbone chain)
 #pragma unroll
     for (int u = 0; u < WU; ++u) {
       const int i = i0 + 64 * u + lane;
@@ -920,6 +920,125 @@ __device__ int win_rows_lin(WCtx& c, const C3Params& P, const uint32_t* pk, int 
 // (row kinds, band shifts) followed by either the H ring of the unbanded rows (the traceback windows reuse it) or the banded
 // rows' substitution table (up to 640 columns), ring and edge cells (sized for the widest band)
 #include "k_polish_band.h"
+
+// ---- the FIRST layer of a window meets the pristine backbone chain: node i at position i, every group a single node, one
+// in-edge and one out-edge of weight 0 in slot 0, coverage 1.  Whatever the graph phases would look up there is an arithmetic
+// function of the index, so the first layer skips the mask sweeps and the compaction (DP row r is node v0 + r - 1, R = the
+// length of the range) and takes the three functions below in place of the descriptor build, the fusion and the edge pass.
+// Every array a later layer, the consensus or the counters read comes out byte for byte as the general path leaves it; rows /
+// rowof / mask, which only the general path of the same layer reads, are not written.  Real calls with scalar arguments, as the
+// rows are: k_window's own register allocation does not pay for them.
+
+// win_build_desc for the chain: one predecessor = the row above (row 1: the virtual start row, p0 = 0 = r - 1 too), nothing kept
+// for a far successor, row R the only end row
+__device__ __attribute__((noinline)) void win_chain_desc(int* cI, uint4* crdesc, int cNcap, const uint8_t* bb_, int v0_, int R_, int allow2_, int mw_) {
+  WCtx c;
+  c.I = uni_ptr(cI); c.Ncap = uni32(cNcap);
+  uint4* const rdesc = uni_ptr(crdesc);
+  const uint8_t* const bb = uni_ptr(bb_);
+  const int v0 = uni32(v0_), R = uni32(R_), MW = uni32(mw_);
+  const unsigned two = uni32(allow2_) != 0;
+  const int lane = wave_lane();
+  extern __shared__ int lds_dyn[];
+  unsigned long long* m2 = (unsigned long long*)lds_dyn; unsigned long long* ma = m2 + MW;
+  for (int r0 = 1; r0 <= R; r0 += 64) {
+    const int r = r0 + lane;
+    if (r <= R) {
+      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+      u32x4 d;
+      d.x = (unsigned)GP(const uint8_t, bb)[v0 + r - 1] | (1u << 8) | ((unsigned)(r == R) << 18) | (two << 19) | ((two & (unsigned)(r < R)) << 20);
+      d.y = (unsigned)(r - 1); d.z = 0; d.w = 0;
+      GP(u32x4, rdesc)[r] = d;
+      GP(int, c.hend().ptr())[r] = INT32_MIN;
+      GP(int, c.opn().ptr())[r] = 0;                                        // kept[r]: no kept rows
+    }
+    const unsigned long long bl = two ? __ballot(r <= R) : 0ull;
+    if (lane == 0) { m2[r0 >> 6] = bl; ma[r0 >> 6] = bl; }
+  }
+  WSYNC();
+}
+
+// fusion + edge pass of the first layer (rq from the traceback -> tq, new nodes, edges, coverage); returns the new node count
+// (beyond Ncap: nothing but the node arrays below Ncap has been touched, the caller fails the window).  A group of one has no
+// sibling to look for: a mismatch is a new node in the group of its row's node.  The edge pass knows the old degrees, slots
+// and weights: backbone node i has its edges (i - 1 -> i) and (i -> i + 1) in slot 0 with weight 0, a new node none.
+__device__ __attribute__((noinline)) int win_chain_fuse(int* cI, int* cE, uint8_t* cB8, int cK, int cNcap, const uint8_t* bb_, const uint32_t* pk_, const uint8_t* qual_,
+                                                        int qbeg_, int Q_, int v0_, int blen_, int ring_off_) {
+  WCtx c;
+  c.I = uni_ptr(cI); c.E = uni_ptr(cE); c.B8 = uni_ptr(cB8); c.K = uni32(cK); c.Ncap = uni32(cNcap);
+  const uint8_t* const bb = uni_ptr(bb_);
+  const uint32_t* const pk = uni_ptr(pk_);
+  const uint8_t* const qual = uni_ptr(qual_);
+  const int qbeg = uni32(qbeg_), Q = uni32(Q_), v0 = uni32(v0_), blen = uni32(blen_), ring_off = uni32(ring_off_);
+  const int lane = wave_lane();
+  extern __shared__ int lds_dyn[];
+  const QArr rq = {(unsigned short*)((unsigned*)lds_dyn + ring_off + W_TBW), c.opq(), Q > W_QCAP};
+  const QArr tq = {(unsigned short*)((unsigned*)lds_dyn + ring_off + W_TBW) + W_QCAP, c.opn(), Q > W_QCAP};
+  int* const gI = c.I; int* const gE = c.E;
+  const unsigned N = (unsigned)c.Ncap, NK = N * (unsigned)c.K;
+#define CI_(k, i) GP(int, gI)[(unsigned)(k) * N + (unsigned)(i)]           /* WCtx::I array k (n_in 0, n_out 1, grp 2, ncov 8, anchor 10) */
+#define CE_(a, v, k) GP(int, gE)[(unsigned)(a) * NK + (unsigned)(k) * N + (unsigned)(v)]      /* in_from 0, in_w 1, out_to 2, out_w 3 */
+  int carry_anchor = -1, carry_new = 0;
+  for (int q0 = 0; q0 < Q; q0 += 128) {
+    int v_[2], cb_[2], bs_[2];
+    bool act_[2];
+#pragma unroll
+    for (int h2 = 0; h2 < 2; ++h2) {
+      const int q = q0 + 64 * h2 + lane;
+      act_[h2] = q < Q;
+      const int r = act_[h2] ? rq.get(q) : 0;
+      v_[h2] = r > 0 ? v0 + r - 1 : -1;
+      cb_[h2] = act_[h2] ? c3_code_at(pk, qbeg + q) : 0;
+      bs_[h2] = (int)GP(const uint8_t, bb)[max(v_[h2], 0)];
+    }
+#pragma unroll
+    for (int h2 = 0; h2 < 2; ++h2) {
+      const int q = q0 + 64 * h2 + lane;
+      if (q0 + 64 * h2 >= Q) break;
+      const bool act = act_[h2];
+      const int v = v_[h2], cb = cb_[h2];
+      int tgt = (v >= 0 && bs_[h2] == cb) ? v : -1;
+      const int isnew = act && tgt < 0;
+      const int as = max(wave_scan_max(v), carry_anchor);                   // anchor of row node v = its own position
+      carry_anchor = wave_bcast(as, 63);
+      const int ps = wave_scan_add(isnew);
+      const int k = carry_new + ps - isnew;
+      carry_new += wave_bcast(ps, 63);
+      if (isnew) {
+        const int id = blen + k;
+        if (id < c.Ncap) {
+          GP(uint8_t, c.B8)[id] = (uint8_t)cb; CI_(0, id) = 0; CI_(1, id) = 0; CI_(2, id) = v >= 0 ? v : id; CI_(8, id) = 0;
+          CI_(10, k) = as;
+        }
+        tgt = id;
+      }
+      if (act) tq.set(q, tgt);
+    }
+  }
+  const int nn = blen + carry_new;
+  if (nn > c.Ncap) return nn;
+  WSYNC();
+  for (int q0 = 0; q0 < Q; q0 += 64) {
+    const int q = q0 + lane;
+    const bool act = q < Q, ed = act && q > 0;
+    const int v = act ? tq.get(q) : 0, u = ed ? tq.get(q - 1) : 0;
+    const int qq = qbeg + (ed ? q : 1);
+    const int w = ((int)GP(const uint8_t, qual)[qq - 1] - 33) + ((int)GP(const uint8_t, qual)[qq] - 33);
+    if (act) CI_(8, v) = (v < blen) + 1;
+    if (!ed) continue;
+    if (v < blen && v == u + 1) { CE_(3, u, 0) = w; CE_(1, v, 0) = w; }     // the backbone edge: weight 0 + w in slot 0 of both lists
+    else {
+      const int no = u + 1 < blen, ni = v < blen && v > 0;                  // old degrees: a backbone node's chain edge, if it has one
+      CE_(2, u, no) = v; CE_(3, u, no) = w; CI_(1, u) = no + 1;
+      CE_(0, v, ni) = u; CE_(1, v, ni) = w; CI_(0, v) = ni + 1;
+    }
+  }
+#undef CI_
+#undef CE_
+  WSYNC();
+  return nn;
+}
+
 __host__ __device__ __forceinline__ int win_mask_words(int Ncap) { return ((Ncap + 64) >> 6) + 1; }
 __host__ __device__ __forceinline__ size_t win_lds_bytes(int Lcap, int Ncap) {
   const size_t masks = (size_t)32 * win_mask_words(Ncap);
@@ -934,7 +1053,8 @@ __device__ __forceinline__ int win_idx(int j, int cpl) { return cpl ? (j / cpl) 
 // cb_io: in = 0: not banded, k >= 1: banded with at least k cells per lane (a retry after a failed certificate asks for a wider
 // band); out = cells per lane of the band that ran (0 = the unbanded rows ran)
 __device__ int win_rows_dispatch(WCtx& c, const C3Params& P, const uint32_t* pk, int qbeg, int Q, int R, int lane, int* cpl_out, int* rs_out, unsigned long long* dbg,
-                                 unsigned long long* m2, unsigned long long* ma, unsigned long long* d0, unsigned long long* d1, int ring_off, int lds_ints, int begin, int end, int blen, int* cb_io, int* nblocks) {
+                                 unsigned long long* m2, unsigned long long* ma, unsigned long long* d0, unsigned long long* d1, int ring_off, int lds_ints, int begin, int end, int blen, int* cb_io, int* nblocks, const uint8_t* chain_bb, int chain_v0, int MW) {
+  // chain_bb != nullptr: the first layer of a window, the graph is the backbone chain and DP row r is node chain_v0 + r - 1
   const int need = (Q + 1 + 63) / 64;
   int cpl;
   // 16-bit keys (score * 4 + type) of the register-blocked rows: |score| <= pm * max(R, Q), |score - g * j| <= (match + |g|) * Q,
@@ -961,7 +1081,8 @@ __device__ int win_rows_dispatch(WCtx& c, const C3Params& P, const uint32_t* pk,
 #ifdef C3_PHASE_PROF
   const unsigned long long bd_t0 = __builtin_readcyclecounter();
 #endif
-  if (cb && !win_build_desc_band(c, R, Q, begin, end, blen, cb, lane, m2, ma, d0, d1, nblocks)) cb = 0;
+  if (cb && chain_bb) { *nblocks = R; if (!win_chain_desc_band(c.rdesc, chain_bb, chain_v0, R, Q, begin, end, cb, MW)) cb = 0; }
+  else if (cb && !win_build_desc_band(c, R, Q, begin, end, blen, cb, lane, m2, ma, d0, d1, nblocks)) cb = 0;
 #ifdef C3_EXP_X2_DESC
   if (cb && !win_build_desc_band(c, R, Q, begin, end, blen, cb, lane, m2, ma, d0, d1, nblocks)) cb = 0;
 #endif
@@ -988,7 +1109,16 @@ __device__ int win_rows_dispatch(WCtx& c, const C3Params& P, const uint32_t* pk,
 #ifdef C3_PHASE_PROF
   const unsigned long long bd_t1 = __builtin_readcyclecounter();
 #endif
-  win_build_desc(c, R, lane, m2, ma, cpl != 0);
+  if (chain_bb && cpl) win_chain_desc(c.I, c.rdesc, c.Ncap, chain_bb, chain_v0, R, 1, MW);
+  else {
+    if (chain_bb) {
+      // the linear fallback rows (layers beyond the register-blocked widths) walk the graph themselves: give them rows / rowof
+      for (int v = lane; v < c.n; v += 64) c.rowof()[v] = (v >= chain_v0 && v < chain_v0 + R) ? v - chain_v0 + 1 : -1;
+      for (int r = 1 + lane; r <= R; r += 64) c.rows()[r] = chain_v0 + r - 1;
+      WSYNC();
+    }
+    win_build_desc(c, R, lane, m2, ma, cpl != 0);
+  }
 #ifdef C3_PHASE_PROF
   dbg[5] += __builtin_readcyclecounter() - bd_t1;
 #endif
@@ -1192,10 +1322,11 @@ __global__ __launch_bounds__(64, C3_WIN_WAVES) void k_window(WinArgs a) {
         c.n_in()[i] = i > 0; c.n_out()[i] = i + 1 < blen;
         if (i > 0) { c.in_from()[EI(i, 0)] = i - 1; c.in_w()[EI(i, 0)] = 0; }
         if (i + 1 < blen) { c.out_to()[EI(i, 0)] = i + 1; c.out_w()[EI(i, 0)] = 0; }
+        if (!a.no_chain) { c.gfirst()[i] = i; c.glast()[i] = i; }         // every block a single node: w_blocks in closed form
       }
       c.n = blen;
       WSYNC();
-      w_blocks(c, lane);
+      if (a.no_chain) w_blocks(c, lane);
       PH_MARK(0)
       // ---- stable order of the layers by begin position (tiny; every lane computes it)
       const int offset = (int)(0.01 * (double)blen);
@@ -1216,8 +1347,11 @@ __global__ __launch_bounds__(64, C3_WIN_WAVES) void k_window(WinArgs a) {
         const WLayer l = lay[li];
         const int Q = l.len;
         const bool full = l.begin < offset && l.end > blen - offset;
+        // the first layer meets the backbone chain: closed-form graph phases (see win_chain_desc)
+        const bool chain = t == 0 && !a.no_chain && c.n == blen && l.begin >= 0 && l.begin <= l.end && l.end < blen;
+        const int chain_v0 = full ? 0 : l.begin;
         // ---- rows of this alignment (masked sub-graph or everything)
-        if (!full) {
+        if (!full && !chain) {
           // spoa Graph::subgraph(begin, end): nodes with id >= begin that reach backbone node `end`
           // through edges / aligned-block links.  Computed as a shrinking fixpoint over whole aligned
           // blocks (the block graph is a DAG, so greatest == least fixpoint); a few parallel sweeps.
@@ -1274,11 +1408,11 @@ __global__ __launch_bounds__(64, C3_WIN_WAVES) void k_window(WinArgs a) {
           }
         }
         PH_MARK(1)
-        int R = 0;
+        int R = chain ? (full ? blen : l.end - l.begin + 1) : 0;         // (a range of the chain: no mask, no compaction)
 #ifdef C3_EXP_X2_COMP
-        for (int rep_ = 0; rep_ < 2; ++rep_) { R = 0;
+        for (int rep_ = 0; rep_ < 2; ++rep_) { if (!chain) R = 0;
 #endif
-        for (int i0 = 0; i0 < c.n; i0 += 64 * WU) {   // order-preserving compaction, WU chunks of 64 positions per iteration
+        for (int i0 = 0; i0 < c.n && !chain; i0 += 64 * WU) {   // order-preserving compaction, WU chunks of 64 positions per iteration
           int v[WU]; bool in[WU];
 #pragma unroll
           for (int u = 0; u < WU; ++u) { const int i = i0 + 64 * u + lane; v[u] = i < c.n ? c.order()[i] : -1; }
@@ -1312,7 +1446,7 @@ __global__ __launch_bounds__(64, C3_WIN_WAVES) void k_window(WinArgs a) {
         for (int attempt = 0; attempt < 4; ++attempt) {
           unsigned long long dbg_[6] = {0, 0, 0, 0, 0, 0};
           int nblocks = 0;
-          if (win_rows_dispatch(c, P, pk, l.qbeg, Q, R, lane, &cpl, &RS, dbg_, m2bits, mabits, d0bits, d1bits, ring_off, lds_ints, l.begin, l.end, blen, &cb, &nblocks) < 0) { fail = SECOND ? 1 : 2; break; }      // (2: the layer needs more DP scratch than this launch has -- the window goes to the full-size launch)
+          if (win_rows_dispatch(c, P, pk, l.qbeg, Q, R, lane, &cpl, &RS, dbg_, m2bits, mabits, d0bits, d1bits, ring_off, lds_ints, l.begin, l.end, blen, &cb, &nblocks, chain ? bb : nullptr, chain_v0, MW) < 0) { fail = SECOND ? 1 : 2; break; }      // (2: the layer needs more DP scratch than this launch has -- the window goes to the full-size launch)
 #ifdef C3_PHASE_PROF
           ph_acc_[10] += dbg_[0]; ph_acc_[11] += dbg_[1];
 #endif
@@ -1466,6 +1600,11 @@ __global__ __launch_bounds__(64, C3_WIN_WAVES) void k_window(WinArgs a) {
 #endif
         // ---- fusion, parallel over the query bases (every graph node is touched by at most one base)
         const int n_old = c.n;
+        int nn;
+        if (chain) {
+          nn = win_chain_fuse(c.I, c.E, c.B8, c.K, c.Ncap, bb, pk, qual, l.qbeg, Q, chain_v0, blen, ring_off);
+          if (nn > c.Ncap) { fail = 1; break; }
+        } else {
         int carry_anchor = -1, carry_new = 0;
         // (two 64-base chunks per turn, the loads of one level for both chunks issued together -- rows -> group + base -> block
         // extent -- then the scans and the stores chunk by chunk, in order: the carries run along the path)
@@ -1518,7 +1657,7 @@ __global__ __launch_bounds__(64, C3_WIN_WAVES) void k_window(WinArgs a) {
             if (act) tq.set(q, tgt);
           }
         }
-        const int nn = n_old + carry_new;
+        nn = n_old + carry_new;
         if (nn > c.Ncap) { fail = 1; break; }
         WSYNC();
         const int K = c.K;
@@ -1565,9 +1704,10 @@ __global__ __launch_bounds__(64, C3_WIN_WAVES) void k_window(WinArgs a) {
           }
         }
         WSYNC();
+        }
         c.n = nn;
         PH_MARK(6)
-        w_reorder(c, n_old, lane, lds_dyn, lds_ints);     // the whole dynamic LDS is idle between traceback and consensus
+        w_reorder(c, n_old, lane, lds_dyn, lds_ints, chain);     // the whole dynamic LDS is idle between traceback and consensus
         PH_MARK(7)
       }
       if (!fail) {

@@ -179,6 +179,53 @@ __device__ int win_build_desc_band(WCtx& c, int R, int Q, int begin, int end, in
   return !bad;
 }
 
+// The same descriptors for the FIRST layer of a window, when the graph is still the backbone chain: DP row r is backbone node
+// v0 + r - 1, its only predecessor the row above (row 1: the virtual start row), its only successor the row below (row R: an end
+// row), every aligned block a single node (bidx = r, R blocks).  Word for word what win_build_desc_band writes for that graph --
+// descriptors, m2 / ma / d0 / d1 -- with the base bytes of the backbone as the only loads.  A real call with scalar arguments
+// (as the rows are): k_window's own registers do not pay for it.
+__device__ __attribute__((noinline)) int win_chain_desc_band(uint4* crdesc, const uint8_t* bb_, int v0_, int R_, int Q_, int begin_, int end_, int CB_, int mw_) {
+  uint4* const rdesc = uni_ptr(crdesc);
+  const uint8_t* const bb = uni_ptr(bb_);
+  const int v0 = uni32(v0_), R = uni32(R_), Q = uni32(Q_), begin = uni32(begin_), end = uni32(end_), CB = uni32(CB_), MW = uni32(mw_);
+  const int lane = wave_lane();
+  extern __shared__ int lds_dyn[];
+  unsigned long long* m2 = (unsigned long long*)lds_dyn; unsigned long long* ma = m2 + MW;
+  unsigned long long* d0 = ma + MW; unsigned long long* d1 = d0 + MW;
+  const int BW = 64 * CB, WLf = wb_left(CB), span = end - begin + 1, lomax = Q + 1 - BW;
+  if (R >= 16000 || Q > 1000) return 0;
+  int loc = 0, bad = 0;
+  for (int rb = 1; rb <= R; rb += 64) {
+    const int r = rb + lane;
+    const bool live = r <= R;
+    const unsigned vb = live ? (unsigned)GP(const uint8_t, bb)[v0 + r - 1] & 3u : 0u;
+    // backbone position reached so far (rows past R of the last step carry row R's, as the scan of the general builder does)
+    const int bbs = max(v0 + min(r, R) - 1, begin - 1);
+    const int cen = (int)(((long long)(bbs - begin + 1) * Q + span / 2) / span);
+    const int lo = min(max(cen - WLf, 0), lomax);
+    const int lop = wave_shr1(lo, loc);
+    loc = wave_bcast(lo, 63);
+    const int dl = live ? lo - lop : 0;
+    if (dl > 3) bad = 1;
+    const unsigned has = live && r < R;
+    const unsigned fast = has && dl <= 1;
+    const unsigned fastn = (unsigned)__builtin_amdgcn_update_dpp(0, (int)fast, 0x130, 0xf, 0xf, false);       // wave_shl:1
+    if (live) {
+      const unsigned wr = has & (fastn ^ 1u);
+      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+      u32x4 d;
+      d.x = vb * 8u | (1u << 8) | ((has ^ 1u) << 18) | (1u << 19) | (fast << 20) | ((fast ? (unsigned)dl : 0u) << 22) | (wr << 23) | ((unsigned)(r == 1) << 24);
+      d.y = (unsigned)(r - 1); d.z = 0; d.w = (unsigned)lo | (has << 10) | ((unsigned)r << 18);
+      GP(u32x4, rdesc)[r] = d;
+    }
+    const unsigned long long bl = __ballot(live), bd0 = __ballot(dl & 1), bd1 = __ballot((dl & 2) != 0);
+    if (lane == 0) { m2[rb >> 6] = bl; ma[rb >> 6] = bl; d0[rb >> 6] = bd0; d1[rb >> 6] = bd1; }
+  }
+  bad = __ballot(bad) != 0;
+  WSYNC();
+  return !bad;
+}
+
 // three lanes (0, 1, 63) park their cells of the row in LDS: EXEC is narrowed by hand (the compiler's version of the same
 // `if` costs two compares and an and/or dance per row)
 template <int CB>
