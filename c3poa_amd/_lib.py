@@ -34,7 +34,8 @@ EXPORTS = ["c3_default_config", "c3_version", "c3_device_count", "c3_warm_device
            "c3_post_emit", "c3_post_emit_host", "c3_post_emit_timing",
            "c3_fasta_parse", "c3_fasta_parse_host", "c3_demux_emit", "c3_demux_emit_host", "c3_demux_emit_timing",
            "c3_emit_group", "c3_emit_group_host", "c3_batch_emit_snapshot", "c3_batch_emit_fetch", "c3_emit_timing_get", "c3_append_streams",
-           "c3_fastx_strict_parse_host", "c3_post_emit_text", "c3_post_text_reset", "c3_post_text_timing_get"]
+           "c3_fastx_strict_parse_host", "c3_post_emit_text", "c3_post_text_reset", "c3_post_text_timing_get",
+           "c3_demux_emit_text", "c3_demux_emit_text_host", "c3_demux_text_reset", "c3_demux_text_timing_get"]
 
 
 ZERO_MAX_CELLS = 16777216       # c3_default_config's zero_max_cells: largest front * tail the zero-repeat rescue takes
@@ -93,6 +94,24 @@ class DemuxInfo(C.Structure):
 class DemuxTiming(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("ms_parse", "ms_demux", "ms_emit", "ms_call")] + \
                [(n, C.c_int64) for n in ("n_records", "n_kept", "in_bytes", "out_bytes")]
+
+
+class DemuxSetsStruct(C.Structure):       # c3_demux_sets
+    _fields_ = [(k + f, t) for k in "ab" for f, t in (("_n", C.c_int), ("_cat", C.c_void_p), ("_off", C.c_void_p), ("_names", C.c_void_p), ("_name_off", C.c_void_p))]
+
+
+class DemuxTextInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_records", "n_kept", "consumed", "text_bytes", "out_bytes")] + \
+               [(k, C.c_int32) for k in ("departed", "kind", "n_streams")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _t in self._fields_}
+
+
+class DemuxTextTiming(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("ms_inflate", "ms_parse", "ms_demux", "ms_split", "ms_emit", "ms_bgzf", "ms_call")] + \
+               [(n, C.c_int64) for n in ("n_records", "n_kept", "in_bytes", "text_bytes", "out_bytes")] + \
+               [(n, C.c_int32) for n in ("n_streams", "n_waits")]
 
 
 class FastqInfo(C.Structure):
@@ -266,6 +285,12 @@ def load():
                                       C.POINTER(PostTextInfo)]
     lib.c3_post_text_reset.argtypes = [vp]
     lib.c3_post_text_timing_get.argtypes = [vp, C.POINTER(PostTextTiming)]
+    dt = [vp, C.c_int64, C.c_int]
+    dt2 = [C.c_int, C.POINTER(DemuxSetsStruct), vp, C.c_int64, vp, vp, C.c_int64, C.POINTER(DemuxTextInfo)]
+    lib.c3_demux_emit_text.argtypes = [vp] + dt + dt2
+    lib.c3_demux_emit_text_host.argtypes = dt + [C.c_int] + dt2
+    lib.c3_demux_text_reset.argtypes = [vp]
+    lib.c3_demux_text_timing_get.argtypes = [vp, C.POINTER(DemuxTextTiming)]
     _lib = lib
     return lib
 
@@ -609,6 +634,22 @@ class Handle:
         out.arena = arena[g:g + used["arena"]]
         out.hashes = hashes[g:g + used["hashes"]].view(np.uint64).copy()
         return out
+
+    def demux_emit_text(self, sets, piece, at_eof=False, flags=0, cap=None, max_records=None, bufs=None):
+        """c3_demux_emit_text: the next piece of a read file (bytes or a uint8 array; whole BGZF members with DEMUX_IN_BGZF)
+        through parse, k_demux, k_dsplit and k_bgzf on the device.  sets: a DemuxSets.  Returns a DemuxText (_demux_text_call)."""
+        return _demux_text_call(lambda *a: self.lib.c3_demux_emit_text(self.h, *a), lambda: self.lib.c3_last_error(self.h), sets, piece, at_eof,
+                                None, flags, cap, max_records, bufs)
+
+    def demux_text_reset(self):
+        """c3_demux_text_reset: drops the tail the demultiplexer's text path keeps between two pieces and forgets the file's kind"""
+        self._chk(self.lib.c3_demux_text_reset(self.h))
+
+    def demux_text_timing(self):
+        """c3_demux_text_timing_get: times, counts and stream waits of the last demux_emit_text"""
+        t = DemuxTextTiming()
+        self._chk(self.lib.c3_demux_text_timing_get(self.h, C.byref(t)))
+        return {f[0]: getattr(t, f[0]) for f in DemuxTextTiming._fields_}
 
     def post_text_reset(self):
         """c3_post_text_reset: drops the tail the text path keeps between two pieces and forgets the file's kind"""
@@ -1592,6 +1633,16 @@ class DemuxSets:
         """bytes c3_demux_emit can return at most for a text of n bytes"""
         return n + (n // 302 + 1) * (5 + self.max_name[0] + self.max_name[1]) + 16
 
+    @property
+    def struct(self):
+        """the sets as a c3_demux_sets"""
+        return DemuxSetsStruct(*self.args)
+
+    @property
+    def n_split_streams(self):
+        """streams of c3_demux_emit_text with DEMUX_SPLIT: (n_a + 1) * (n_b + 1)"""
+        return (self.args[0] + 1) * (self.args[5] + 1)
+
 
 class DemuxEmit:
     """result of c3_demux_emit / c3_demux_emit_host: info (dict), out (bytes), hashes (uint64 array of n_records),
@@ -1624,6 +1675,71 @@ def demux_emit_host(text, sets, at_eof=True, cap=None, max_records=None):
     """c3_demux_emit_host: the host statement of Handle.demux_emit (same arguments and results)"""
     lib = load()
     return _demux_emit_call(lib.c3_demux_emit_host, lambda: lib.c3_last_error(None), text, sets, at_eof, cap, max_records)
+
+
+# ---- Sample demultiplexer, pieces of text in / per-sample streams out (C3POa_demux.py --parse gpu; DESIGN.md 5.10) ----
+DEMUX_IN_BGZF, DEMUX_OUT_BGZF, DEMUX_KEEP_QUALS, DEMUX_SPLIT = 1, 2, 4, 8     # flags of c3_demux_emit_text
+DEMUX_MAX_STREAMS = 4096
+
+
+class DemuxText:
+    """result of c3_demux_emit_text / c3_demux_emit_text_host: info (dict), arena (uint8 array), stream_off (int64 array of
+    S + 1), hashes (uint64 array of n_records), guards_intact, untouched_beyond_results"""
+
+    def streams(self):
+        so = self.stream_off
+        return [self.arena[so[s]:so[s + 1]].tobytes() for s in range(len(so) - 1)]
+
+
+def _demux_text_call(fn, err, sets, piece, at_eof, kind, flags, cap, max_records, bufs=None):
+    """one c3_demux_emit_text (kind None) or c3_demux_emit_text_host call.  cap / max_records: instead of sizes found by asking
+    again; C3Error (code, .info, .stream_off, .guards_intact, .untouched) on a refusal.  bufs: a dict the call keeps its output
+    arrays in from one piece to the next (no guard bytes then; the results are views that the next call overwrites)."""
+    src = piece if isinstance(piece, np.ndarray) else np.frombuffer(_bytes(piece), dtype=np.uint8)
+    n = len(src)
+    S = sets.n_split_streams if flags & DEMUX_SPLIT else 1
+    so = np.full(min(S, DEMUX_MAX_STREAMS) + 1 + 2, -0x5A5A5A5A5A5A5A5B, dtype=np.int64)         # a guard word either side
+    st = sets.struct
+    info = DemuxTextInfo()
+    ask = cap is None and max_records is None
+    in_z = bool(flags & DEMUX_IN_BGZF)
+    cap = (24 if in_z else 3) * n + 65536 if cap is None else int(cap)
+    max_records = (8 if in_z else 1) * (n // 8) + 16 if max_records is None else int(max_records)
+    g = FASTA_GUARD if bufs is None else 0
+    for _try in range(3):
+        if bufs is None:
+            arena, hashes = np.full(cap + 2 * g, 0xA5, dtype=np.uint8), np.full(8 * max_records + 2 * g, 0xA5, dtype=np.uint8)
+        else:
+            if len(bufs.get("arena", ())) < cap:
+                bufs["arena"] = np.empty(cap, dtype=np.uint8)
+            if len(bufs.get("hashes", ())) < 8 * max_records:
+                bufs["hashes"] = np.empty(8 * max_records, dtype=np.uint8)
+            arena, hashes, cap, max_records = bufs["arena"], bufs["hashes"], len(bufs["arena"]), len(bufs["hashes"]) // 8
+        args = (src.ctypes.data if n else None, n, int(bool(at_eof))) + (() if kind is None else (int(kind),)) + \
+               (int(flags), C.byref(st), arena.ctypes.data + g, cap, so.ctypes.data + 8, hashes.ctypes.data + g, max_records, C.byref(info))
+        rc = fn(*args)
+        if ask and rc == E_LIMIT and S <= DEMUX_MAX_STREAMS and (so[S + 1] > cap or info.n_records > max_records):
+            cap, max_records = max(cap, int(so[S + 1])), max(max_records, int(info.n_records))
+            continue
+        break
+    out = DemuxText()
+    out.info, out.stream_off = info.as_dict(), so[1:-1]
+    used = {"arena": int(so[S + 1]), "hashes": 8 * int(info.n_records)} if rc == 0 else {"arena": 0, "hashes": 0}
+    out.guards_intact, out.untouched_beyond_results = _guarded({"arena": arena, "hashes": hashes}, used) if bufs is None else (True, True)
+    out.guards_intact = out.guards_intact and so[0] == so[-1] == -0x5A5A5A5A5A5A5A5B
+    if rc != 0:
+        e = C3Error("c3 error %d: %s" % (rc, err().decode()))
+        e.code, e.info, e.stream_off, e.guards_intact, e.untouched = rc, out.info, out.stream_off, out.guards_intact, out.untouched_beyond_results
+        raise e
+    out.arena = arena[g:g + used["arena"]]
+    out.hashes = hashes[g:g + used["hashes"]].view(np.uint64).copy()
+    return out
+
+
+def demux_emit_text_host(sets, text, at_eof=True, kind=2, flags=0, cap=None, max_records=None):
+    """c3_demux_emit_text_host: the host statement of Handle.demux_emit_text for one plain text of a stated kind"""
+    lib = load()
+    return _demux_text_call(lib.c3_demux_emit_text_host, lambda: lib.c3_last_error(None), sets, text, at_eof, kind, flags, cap, max_records)
 
 
 class PinnedBytes:

@@ -20,6 +20,9 @@ int c3_fasta_check_args(const char* who, const char* text, int64_t n, const char
 int c3_demux_emit_check_args(const char* who, const char* text, int64_t n, int n_a, const char* a_names, const int64_t* a_name_off,
                              int n_b, const char* b_names, const int64_t* b_name_off, const char* out, int64_t cap,
                              const uint64_t* name_hash, int64_t max_records, c3_demux_info* info);                    // c3_fasta.cpp
+int c3_demux_text_check_args(const char* who, const char* src, int64_t n, int flags, const c3_demux_sets* sets, const char* arena,
+                             int64_t cap, const int64_t* stream_off, const uint64_t* name_hash, int64_t max_records,
+                             c3_demux_text_info* info, int* S, uint8_t* tab, int* n_codes);                          // c3_dsplit.cpp
 int c3_bgzf_data_error(const char* who, int64_t member, int st);                                                      // c3_inflate.cpp
 
 // the reader's device stretches (c3_stream.hip, called by c3_io.cpp; not part of the public interface)

@@ -68,6 +68,10 @@ C3_FA_HD inline int64_t c3_fasta_consumed(const C3FaVerdict& v, int64_t H, int a
 C3_FA_HD inline int64_t c3_demux_rec_len(int64_t name_len, int64_t seq_len, int64_t a_len, int64_t b_len) {
   return 1 + name_len + 1 + a_len + 1 + b_len + 1 + seq_len + 1;
 }
+// ... and with qualities (C3_DEMUX_KEEP_QUALS): '@' name '|' A '_' B '\n' sequence '\n' '+' '\n' quality '\n'
+C3_FA_HD inline int64_t c3_demux_rec_len(int64_t name_len, int64_t seq_len, int64_t a_len, int64_t b_len, int quals) {
+  return c3_demux_rec_len(name_len, seq_len, a_len, b_len) + (quals ? 2 + seq_len + 1 : 0);
+}
 
 // what k_fasta leaves for the host after its scans (c3_scans.hip reads it back)
 struct C3FaHdr {

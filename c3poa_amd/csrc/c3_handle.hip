@@ -170,6 +170,7 @@ extern "C" void c3_destroy(c3_handle* h) {
   if (h->h_emit_sizes) (void)hipHostFree(h->h_emit_sizes);
   if (h->h_fa_hdr) (void)hipHostFree(h->h_fa_hdr);
   c3h::post_text_free(h);
+  c3h::demux_text_free(h);
   if (h->h_tot) (void)hipHostFree(h->h_tot);
   delete h;
 }

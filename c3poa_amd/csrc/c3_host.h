@@ -8,6 +8,7 @@
 #include "c3_emit.h"
 #include "c3_post.h"
 #include "c3_fastx.h"
+#include "c3_dsplit.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -31,6 +32,16 @@ int post_write(c3_handle* h, PostArgs& p, int64_t need);
 int adapters_device(c3_handle* h, const C3Batch& b, int64_t max_len, int32_t* d_out);
 int bgzf_inflate_to_device(c3_bgzf* z, const char* src, int64_t n, int64_t nm, uint8_t* d_dst, int64_t* out_len);    // c3_stream.hip
 void post_text_free(c3_handle* h);                                                                                     // c3_text.hip
+// k_fasta on a text that lies on the device, the gather of its records, the index sets of a search (c3_scans.hip)
+namespace fa { enum { FA_TEXT, FA_CNT, FA_NL, FA_LSE, FA_LDST, FA_BSUM, FA_HDR, FA_OFF, FA_NOFF, FA_RECL, FA_HASH, FA_NAMES, FA_SEQS, FA_KREC, FA_ROFF,
+                      FA_OUT, FA_ANAMES, FA_ANO, FA_BNAMES, FA_BNO, FA_N }; }      // the slots of c3_handle::d_fa
+int fasta_parse_resident(c3_handle* h, const uint8_t* d_text, int64_t n, int at_eof, int kept, FaArgs* a);
+int fasta_gather_resident(c3_handle* h, FaArgs* a);
+int demux_sets_device(c3_handle* h, const c3_demux_sets* st, const uint8_t* tab, int K, int64_t nk, FaArgs* a);
+struct ZStage;
+// one device-resident stream compressed by k_bgzf as one text into the host arena at *out (c3_text.hip)
+int bgzf_stream_device(c3_handle* h, ZStage& z, const char* d_src, int64_t len, char* arena, int64_t cap, int64_t* out);
+void demux_text_free(c3_handle* h);                                                                                    // c3_dtext.hip
 }
 
 #define BGZF_CHUNK_BLOCKS 2048                   // BGZF blocks per device chunk of a compression (c3_stream.hip, c3_batch_emit_fetch)
@@ -75,13 +86,27 @@ struct c3h::EmitBufs { DBuf work, offs, arena; hipEvent_t ev[5] = {}; };
 
 // the text path of the post-processing step (c3_text.hip): text[cur] holds the text of the last call, its bytes
 // [tail_from, text_n) being the unconsumed tail that goes in front of the next piece; the passes' tables and arenas; the inflater
+// staging of a compression by chunks (c3h::bgzf_stream_device): the chunk, k_bgzf's slots, member sizes and packed members;
+// the page-locked copy of the sizes (BGZF_CHUNK_BLOCKS ints, allocated by the owner)
+struct c3h::ZStage { DBuf zin, zslots, zsizes, zpacked; int* h_sizes = nullptr; };
 struct PostText {
   DBuf text[2]; int cur = 0, kind = 0; int64_t text_n = 0, tail_from = 0;
   DBuf cnt, nl, slen, nlen, bsum, hdr, lhdr, off, name_off, woff, src, hash, names, seqs, quals, pk, table;
-  DBuf zin, zslots, zsizes, zpacked;
-  C3FxHdr* h_hdr = nullptr; C3FqHdr* h_lhdr = nullptr; int* h_sizes = nullptr; c3_bgzf* z = nullptr;
+  c3h::ZStage zs;
+  C3FxHdr* h_hdr = nullptr; C3FqHdr* h_lhdr = nullptr; c3_bgzf* z = nullptr;
   hipEvent_t ev[8] = {};
   c3_post_text_timing tm = {};
+};
+// the text path of the demultiplexer (c3_dtext.hip): the double text buffer as in PostText; the FASTQ parse tables and arenas (a FASTA
+// text is parsed into c3_handle::d_fa); the placement tables of k_dsplit and the output arena; staging, inflater, read-backs
+struct DemuxText {
+  DBuf text[2]; int cur = 0, kind = 0; int64_t text_n = 0, tail_from = 0;
+  DBuf cnt, nl, slen, nlen, bsum, hdr, lhdr, off, name_off, woff, src, hash, names, seqs, quals;
+  DBuf krec, kb, nkept, key, rank, base, soff, out;
+  c3h::ZStage zs;
+  C3FxHdr* h_hdr = nullptr; C3FqHdr* h_lhdr = nullptr; int64_t* h_soff = nullptr; c3_bgzf* z = nullptr;
+  hipEvent_t ev[6] = {};
+  c3_demux_text_timing tm = {};
 };
 
 struct Summary { int status, n_sub, max_sub, sum_sub, max_dang, front, tail, n_peaks; };
@@ -115,6 +140,7 @@ struct c3_handle {
   hipEvent_t ev_qv[2] = {nullptr, nullptr}; c3_qv_timing qtm = {}; bool snap_qv = false;
   DBuf d_post[16]; hipEvent_t ev_post[5] = {}; c3_post_timing ptm = {};       // k_post: inputs, descriptors, pass buffers, arena; event times of the last call
   PostText pt;
+  DemuxText dx; std::vector<uint32_t> dmx_meta_host;      // ... of the demultiplexer; k_demux's meta while its upload is queued
   // k_fasta: text, tables, arenas, output; event times of the last c3_demux_emit; page-locked copy of the device header
   DBuf d_fa[20]; hipEvent_t ev_fa[10] = {}; c3_demux_timing dtm = {}; struct C3FaHdr* h_fa_hdr = nullptr;
   // k_emit: inputs of c3_emit_group and its pass buffers; times of the last c3_emit_group / delivered emit snapshot

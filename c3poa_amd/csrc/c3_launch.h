@@ -1,13 +1,13 @@
 // c3_launch.h -- the one declaration of every kernel launcher and kernel query.  The host units call through it, and every k_*.hip
 // that defines a launcher includes it too, so a prototype that drifts from its definition fails to compile in the kernel's own
-// translation unit.  Declarations only: the argument blocks are named, not defined (c3_args.h, c3_post.h, c3_inflate.h, c3_fastq.h, c3_fasta.h, c3_emit.h, c3_fastx.h).
+// translation unit.  Declarations only: the argument blocks are named, not defined (c3_args.h, c3_post.h, c3_inflate.h, c3_fastq.h, c3_fasta.h, c3_emit.h, c3_fastx.h, c3_dsplit.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 struct ConkArgs; struct AdapterArgs; struct PostArgs; struct PeaksArgs; struct PoaArgs; struct PrepArgs; struct WinArgs; struct StitchArgs;
-struct ZeroArgs; struct QvArgs; struct C3BgzfMember; struct C3FqHdr; struct FaArgs; struct EmitArgs; struct FxArgs;
+struct ZeroArgs; struct QvArgs; struct C3BgzfMember; struct C3FqHdr; struct FaArgs; struct EmitArgs; struct FxArgs; struct DsArgs;
 
 extern "C" {
 void c3k_launch_conk(const ConkArgs*, int, int, int, hipStream_t);                                                          // k_conk.hip
@@ -49,5 +49,8 @@ void c3k_launch_emit_write(const EmitArgs*, hipStream_t);
 void c3k_launch_fastx_high(const FxArgs*, hipStream_t);                                                                    // k_fastx.hip
 void c3k_launch_fastx_records(const FxArgs*, hipStream_t);
 void c3k_launch_fastx_gather(const FxArgs*, hipStream_t);
+void c3k_launch_dsplit_krec(const DsArgs*, hipStream_t);                                                                   // k_dsplit.hip
+void c3k_launch_dsplit_place(const DsArgs*, hipStream_t);
+void c3k_launch_dsplit_emit(const DsArgs*, hipStream_t);
 void c3k_launch_pack(const uint8_t*, const int64_t*, const int64_t*, int, uint32_t*, int, hipStream_t);                    // c3_handle.hip
 }

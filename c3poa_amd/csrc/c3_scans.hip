@@ -246,8 +246,7 @@ extern "C" int c3_demux_indexes(c3_handle* h, int n, const char* heads, int n_a,
 // ---- FASTA text parsed, demultiplexed and formatted on the device (k_fasta.hip; host statements c3_fasta.cpp) ----
 // One parse = two waits: the terminator count (sizes nl[] and the line and record tables), the header (sizes the arenas and
 // answers the capacity question before any byte is gathered).  c3_demux_emit waits once more for the output size.
-enum { FA_TEXT, FA_CNT, FA_NL, FA_LSE, FA_LDST, FA_BSUM, FA_HDR, FA_OFF, FA_NOFF, FA_RECL, FA_HASH, FA_NAMES, FA_SEQS, FA_KREC, FA_ROFF,
-       FA_OUT, FA_ANAMES, FA_ANO, FA_BNAMES, FA_BNO, FA_N };
+using namespace c3h::fa;                         // FA_TEXT .. FA_N: the slots of c3_handle::d_fa (c3_host.h)
 static_assert(FA_N <= sizeof(c3_handle::d_fa) / sizeof(DBuf), "c3_handle::d_fa is too short");
 
 static int fa_read_hdr(c3_handle* h) {
@@ -256,19 +255,26 @@ static int fa_read_hdr(c3_handle* h) {
   return C3_E_OK;
 }
 
-// the text (n > 0) uploaded and parsed: line and record tables and the header on the device and in h->h_fa_hdr; no byte gathered
-// yet.  kept: krec[] and n_kept as well.
+// the text (n > 0) uploaded and parsed (c3h::fasta_parse_resident)
 static int fa_parse_device(c3_handle* h, const char* text, int64_t n, int at_eof, int kept, FaArgs* a) {
+  HIPCHK(hipSetDevice(h->cfg.device));
+  HIPCHK(h->d_fa[FA_TEXT].ensure((size_t)n + 256));
+  HIPCHK(hipMemcpyAsync(h->d_fa[FA_TEXT].p, text, (size_t)n, hipMemcpyHostToDevice, h->stream));
+  return c3h::fasta_parse_resident(h, h->d_fa[FA_TEXT].as<uint8_t>(), n, at_eof, kept, a);
+}
+
+// The text d_text[0, n) (n > 0; on the device, queued on h->stream, 256-aligned with 256 bytes of slack behind it) parsed: line and
+// record tables and the header on the device and in h->h_fa_hdr; no byte gathered yet.  kept: krec[] and n_kept as well.
+int c3h::fasta_parse_resident(c3_handle* h, const uint8_t* d_text, int64_t n, int at_eof, int kept, FaArgs* a) {
   memset(a, 0, sizeof *a);
   HIPCHK(hipSetDevice(h->cfg.device));
   if (!h->h_fa_hdr) HIPCHK(hipHostMalloc((void**)&h->h_fa_hdr, sizeof(C3FaHdr), hipHostMallocDefault));
   for (hipEvent_t& ev : h->ev_fa) if (!ev) HIPCHK(hipEventCreate(&ev));
   DBuf* d = h->d_fa;
   const size_t tiles = ((size_t)n + 65535) / 65536;
-  HIPCHK(d[FA_TEXT].ensure((size_t)n + 256)); HIPCHK(d[FA_HDR].ensure(sizeof(C3FaHdr))); HIPCHK(d[FA_CNT].ensure(tiles * 4 * sizeof(int32_t)));
-  HIPCHK(hipMemcpyAsync(d[FA_TEXT].p, text, (size_t)n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(d[FA_HDR].ensure(sizeof(C3FaHdr))); HIPCHK(d[FA_CNT].ensure(tiles * 4 * sizeof(int32_t)));
   HIPCHK(hipMemsetAsync(d[FA_HDR].p, 0xFF, 12, h->stream));           // first_high, first_headless: none; rec_of_high: -1
-  a->buf = d[FA_TEXT].as<uint8_t>(); a->hi = (uint32_t)n; a->at_eof = at_eof ? 1 : 0;
+  a->buf = d_text; a->hi = (uint32_t)n; a->at_eof = at_eof ? 1 : 0;
   a->cnt = d[FA_CNT].as<int32_t>(); a->hdr = d[FA_HDR].as<C3FaHdr>();
   HIPCHK(hipEventRecord(h->ev_fa[0], h->stream));
   c3k_launch_fasta_count(a, h->stream);
@@ -302,7 +308,7 @@ static int fa_parse_device(c3_handle* h, const char* text, int64_t n, int at_eof
 }
 
 // names and sequences of the delivered records gathered into the arenas (queued, not waited for)
-static int fa_gather_device(c3_handle* h, FaArgs* a) {
+int c3h::fasta_gather_resident(c3_handle* h, FaArgs* a) {
   const C3FaHdr& f = *h->h_fa_hdr;
   HIPCHK(h->d_fa[FA_NAMES].ensure((size_t)f.name_bytes + 256)); HIPCHK(h->d_fa[FA_SEQS].ensure((size_t)f.base_bytes + 256));
   a->names = h->d_fa[FA_NAMES].as<uint8_t>(); a->seqs = h->d_fa[FA_SEQS].as<uint8_t>();
@@ -324,7 +330,7 @@ extern "C" int c3_fasta_parse(c3_handle* h, const char* text, int64_t n, int at_
   if (f.n_records > max_records || f.name_bytes > names_cap || f.base_bytes > bases_cap)
     return c3_fail(h, C3_E_LIMIT, "c3_fasta_parse: capacity too small (needed sizes in info)");
   if (f.n_records == 0) { name_off[0] = 0; off[0] = 0; return C3_E_OK; }
-  if ((rc = fa_gather_device(h, &a)) != C3_E_OK) return rc;
+  if ((rc = c3h::fasta_gather_resident(h, &a)) != C3_E_OK) return rc;
   const size_t R = (size_t)f.n_records;
   HIPCHK(hipMemcpyAsync(off, a.off, (R + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(name_off, a.name_off, (R + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
@@ -332,6 +338,23 @@ extern "C" int c3_fasta_parse(c3_handle* h, const char* text, int64_t n, int at_
   if (f.name_bytes) HIPCHK(hipMemcpyAsync(names, a.names, (size_t)f.name_bytes, hipMemcpyDeviceToHost, h->stream));
   if (f.base_bytes) HIPCHK(hipMemcpyAsync(seqs, a.seqs, (size_t)f.base_bytes, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  return C3_E_OK;
+}
+
+// the index sets of a search over nk kept records on the device: k_demux's meta (kept in the handle until the next call, so the
+// upload needs no wait), the index names and their offsets, room for the heads and the winners; a's pointers to them filled
+int c3h::demux_sets_device(c3_handle* h, const c3_demux_sets* st, const uint8_t* tab, int K, int64_t nk, FaArgs* a) {
+  DBuf* d = h->d_fa;
+  h->dmx_meta_host = dmx_meta(st->n_a, st->a_cat, st->a_off, st->n_b, st->b_cat, st->b_off, tab, K + 1);
+  const size_t anb = (size_t)st->a_name_off[st->n_a], bnb = (size_t)st->b_name_off[st->n_b];
+  HIPCHK(h->d_dmx_heads.ensure((size_t)nk * C3_DEMUX_HEAD + 16)); HIPCHK(h->d_dmx_out.ensure(sizeof(int32_t) * 2 * (size_t)nk));
+  HIPCHK(h->d_dmx_meta.put(h->dmx_meta_host.data(), sizeof(uint32_t) * h->dmx_meta_host.size(), h->stream));
+  HIPCHK(d[FA_ANAMES].ensure(anb + 16)); HIPCHK(d[FA_BNAMES].ensure(bnb + 16));
+  if (anb) HIPCHK(hipMemcpyAsync(d[FA_ANAMES].p, st->a_names, anb, hipMemcpyHostToDevice, h->stream));
+  if (bnb) HIPCHK(hipMemcpyAsync(d[FA_BNAMES].p, st->b_names, bnb, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(d[FA_ANO].put(st->a_name_off, sizeof(int64_t) * (size_t)(st->n_a + 1), h->stream)); HIPCHK(d[FA_BNO].put(st->b_name_off, sizeof(int64_t) * (size_t)(st->n_b + 1), h->stream));
+  a->heads = h->d_dmx_heads.as<uint8_t>(); a->win = h->d_dmx_out.as<int32_t>();
+  a->a_names = d[FA_ANAMES].as<uint8_t>(); a->a_no = d[FA_ANO].as<int64_t>(); a->b_names = d[FA_BNAMES].as<uint8_t>(); a->b_no = d[FA_BNO].as<int64_t>();
   return C3_E_OK;
 }
 
@@ -357,20 +380,14 @@ extern "C" int c3_demux_emit(c3_handle* h, const char* text, int64_t n, int at_e
   float ms[5] = {0, 0, 0, 0, 0};
   if (nk > 0) {
     DBuf* d = h->d_fa;
-    const int I = n_a + n_b, K1 = K + 1;
-    const std::vector<uint32_t> meta = dmx_meta(n_a, a_cat, a_off, n_b, b_cat, b_off, tab, K1);
+    const int K1 = K + 1;
+    const c3_demux_sets st = {n_a, a_cat, a_off, a_names, a_name_off, n_b, b_cat, b_off, b_names, b_name_off};
+    if ((rc = c3h::demux_sets_device(h, &st, tab, K, nk, &a)) != C3_E_OK) return rc;
     const size_t anb = (size_t)a_name_off[n_a], bnb = (size_t)b_name_off[n_b];
-    HIPCHK(h->d_dmx_heads.ensure((size_t)nk * C3_DEMUX_HEAD + 16)); HIPCHK(h->d_dmx_out.ensure(sizeof(int32_t) * 2 * (size_t)nk));
-    HIPCHK(h->d_dmx_meta.put(meta.data(), sizeof(uint32_t) * meta.size(), h->stream));
-    HIPCHK(d[FA_ANAMES].ensure(anb + 16)); HIPCHK(d[FA_BNAMES].ensure(bnb + 16));
-    if (anb) HIPCHK(hipMemcpyAsync(d[FA_ANAMES].p, a_names, anb, hipMemcpyHostToDevice, h->stream));
-    if (bnb) HIPCHK(hipMemcpyAsync(d[FA_BNAMES].p, b_names, bnb, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(d[FA_ANO].put(a_name_off, sizeof(int64_t) * (size_t)(n_a + 1), h->stream)); HIPCHK(d[FA_BNO].put(b_name_off, sizeof(int64_t) * (size_t)(n_b + 1), h->stream));
     HIPCHK(d[FA_ROFF].ensure(sizeof(int64_t) * ((size_t)nk + 1)));
-    a.heads = h->d_dmx_heads.as<uint8_t>(); a.win = h->d_dmx_out.as<int32_t>(); a.roff = d[FA_ROFF].as<int64_t>();
-    a.a_names = d[FA_ANAMES].as<uint8_t>(); a.a_no = d[FA_ANO].as<int64_t>(); a.b_names = d[FA_BNAMES].as<uint8_t>(); a.b_no = d[FA_BNO].as<int64_t>();
+    a.roff = d[FA_ROFF].as<int64_t>();
     HIPCHK(hipEventRecord(h->ev_fa[4], h->stream));
-    if ((rc = fa_gather_device(h, &a)) != C3_E_OK) return rc;
+    if ((rc = c3h::fasta_gather_resident(h, &a)) != C3_E_OK) return rc;
     c3k_launch_demux_heads(&a, h->stream);
     HIPCHK(hipEventRecord(h->ev_fa[5], h->stream));
     c3k_launch_demux(a.heads, (int)nk, h->d_dmx_meta.as<uint8_t>(), n_a, n_b, K1, h->d_dmx_out.as<int32_t>(), nullptr, h->stream);
@@ -378,7 +395,7 @@ extern "C" int c3_demux_emit(c3_handle* h, const char* text, int64_t n, int at_e
     c3k_launch_demux_len(&a, h->stream);
     HIPCHK(hipEventRecord(h->ev_fa[7], h->stream));
     HIPCHK(hipGetLastError());
-    if ((rc = fa_read_hdr(h)) != C3_E_OK) return rc;           // (meta is a host vector of this frame: the wait covers its upload)
+    if ((rc = fa_read_hdr(h)) != C3_E_OK) return rc;
     const int64_t need = f.out_bytes;
     // a record is at least its five literals and 301 sequence bytes, at most everything the text holds plus two index names
     if (need < nk * (C3_DEMUX_HEAD + 6) || need > n + nk * (int64_t)(5 + anb + bnb)) return c3_fail(h, C3_E_HIP, "k_fasta: output size out of range");

@@ -14,10 +14,10 @@ void c3h::post_text_free(c3_handle* h) {
   PostText& t = h->pt;
   if (t.h_hdr) (void)hipHostFree(t.h_hdr);
   if (t.h_lhdr) (void)hipHostFree(t.h_lhdr);
-  if (t.h_sizes) (void)hipHostFree(t.h_sizes);
+  if (t.zs.h_sizes) (void)hipHostFree(t.zs.h_sizes);
   for (hipEvent_t ev : t.ev) if (ev) (void)hipEventDestroy(ev);
   if (t.z) c3_bgzf_destroy(t.z);
-  t.h_hdr = nullptr; t.h_lhdr = nullptr; t.h_sizes = nullptr; t.z = nullptr;
+  t.h_hdr = nullptr; t.h_lhdr = nullptr; t.zs.h_sizes = nullptr; t.z = nullptr;
 }
 
 extern "C" int c3_post_text_reset(c3_handle* h) {
@@ -34,8 +34,7 @@ extern "C" int c3_post_text_timing_get(c3_handle* h, c3_post_text_timing* t) {
 
 // stream [src, src + len) of the device arena compressed as one text into arena + *out (k_bgzf in chunks of BGZF_CHUNK_BLOCKS
 // blocks, staged 4-byte aligned with 256 bytes of slack, as c3_batch_emit_fetch does)
-static int text_bgzf_stream(c3_handle* h, const char* src, int64_t len, char* arena, int64_t cap, int64_t* out) {
-  PostText& t = h->pt;
+int c3h::bgzf_stream_device(c3_handle* h, ZStage& t, const char* src, int64_t len, char* arena, int64_t cap, int64_t* out) {
   const int64_t CH = (int64_t)BGZF_CHUNK_BLOCKS * BGZF_BLOCK;
   for (int64_t c0 = 0; c0 < len; c0 += CH) {
     const int64_t cn = std::min(CH, len - c0);
@@ -89,7 +88,7 @@ extern "C" int c3_post_emit_text(c3_handle* h, const char* src, int64_t n, int a
   HIPCHK(hipSetDevice(h->cfg.device));
   if (!t.h_hdr) HIPCHK(hipHostMalloc((void**)&t.h_hdr, sizeof(C3FxHdr), hipHostMallocDefault));
   if (!t.h_lhdr) HIPCHK(hipHostMalloc((void**)&t.h_lhdr, sizeof(C3FqHdr), hipHostMallocDefault));
-  if (!t.h_sizes) HIPCHK(hipHostMalloc((void**)&t.h_sizes, BGZF_CHUNK_BLOCKS * sizeof(int), hipHostMallocDefault));
+  if (!t.zs.h_sizes) HIPCHK(hipHostMalloc((void**)&t.zs.h_sizes, BGZF_CHUNK_BLOCKS * sizeof(int), hipHostMallocDefault));
   for (hipEvent_t& ev : t.ev) if (!ev) HIPCHK(hipEventCreate(&ev));
   t.tm = c3_post_text_timing{};
   for (int s = 0; s <= S; ++s) stream_off[s] = 0;
@@ -212,7 +211,7 @@ extern "C" int c3_post_emit_text(c3_handle* h, const char* src, int64_t n, int a
     for (int s = 0; s < S; ++s) {
       stream_off[s] = out;
       const int64_t len = so[s + 1] - so[s];
-      if (s < n_z) { if ((rc = text_bgzf_stream(h, d_arena + so[s], len, arena, cap, &out)) != C3_E_OK) return rc; }
+      if (s < n_z) { if ((rc = c3h::bgzf_stream_device(h, t.zs, d_arena + so[s], len, arena, cap, &out)) != C3_E_OK) return rc; }
       else if (len) { HIPCHK(hipMemcpyAsync(arena + out, d_arena + so[s], (size_t)len, hipMemcpyDeviceToHost, h->stream)); out += len; }
     }
     stream_off[S] = out;

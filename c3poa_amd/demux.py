@@ -7,8 +7,10 @@ when its distance is < 4 and the runner-up's is more than 1 further away, otherw
 is k_demux (c3_demux_indexes) in batches of bounded size; c3_demux_host is its host statement.  read_fasta,
 demultiplex and write_fasta_file keep the reference's function shapes.
 """
+import gzip
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -24,14 +26,14 @@ class DemuxError(ValueError):
     """an input the reference cannot process (it crashes on all of these)"""
 
 
-def read_fasta(path):
+def read_fasta(path, opener=open):
     """{header: sequence} as the reference's read_fasta: the header is the whole line after '>' (rstrip only), sequence
     lines are rstrip-ped and joined, blank lines are skipped, a repeated header keeps its first position and takes the
     last record's sequence.  Text mode with universal newlines, as the reference opens the file.  A sequence line before
-    the first header raises DemuxError."""
+    the first header raises DemuxError.  opener: what opens `path` as text (the .gz inputs of --parse gpu)."""
     reads = {}
     last = None
-    with open(path) as f:
+    with opener(path) as f:
         for n, line in enumerate(f, 1):
             line = line.rstrip()
             if not line:
@@ -223,5 +225,234 @@ def run_emit_gpu(input_fasta, output_path, nextera_file, tso_file, chunk=EMIT_CH
             state["out"].close()
         if state["buf"] is not None:
             state["buf"].close()
+        if state["own"] is not None:
+            state["own"].close()
+
+
+# ---- --parse gpu: text, FASTQ or BGZF in; one file or one per sample, plain or BGZF, out (c3_demux_emit_text) ----
+MAX_OPEN_PARTS = 256    # .part files of --split kept open at a time; further ones are opened and closed for every append, so that
+                        # a run that reaches thousands of samples stays below the usual limit of 1024 open files
+NO_QUALS = "--keep-quals: the records of %s have no quality line"      # the message of C3POa_postprocessing.py --keep-quals
+
+
+def sample_files(a_names, b_names):
+    """{(A, B): '<A>_<B>'} over the whole (n_a + 1) * (n_b + 1) name table of --split ('' = no call), checked before any
+    work: a '/' or NUL in an index name, or two pairs with one file name, is a DemuxError"""
+    for n in list(a_names) + list(b_names):
+        if "/" in n or "\0" in n:
+            raise DemuxError("--split: index name %r holds '/' or NUL and cannot name a file" % n)
+    table, seen = {}, {}
+    for a in list(a_names) + [""]:
+        for b in list(b_names) + [""]:
+            f = a + "_" + b
+            if f in seen:
+                raise DemuxError("--split: the index pairs %r and %r give the same file name %r" % (seen[f], (a, b), f))
+            seen[f] = (a, b)
+            table[(a, b)] = f
+    return table
+
+
+def _out_names(split, keep_quals, bgzf):
+    ext = (".fastq" if keep_quals else ".fasta") + (".gz" if bgzf else "")
+    return ("samples" if split else "Indexed_reads" + ext), ext
+
+
+def _is_gzip(path):
+    with open(path, "rb") as fh:
+        return fh.read(2) == b"\x1f\x8b"
+
+
+def _bgzf_file_host(path):
+    """path -> path.gz as postprocess._bgzf_file writes it, through the host statement of k_bgzf: whole members piece by
+    piece, then the EOF member; the plain file goes"""
+    piece_bytes = 1024 * _lib.BGZF_BLOCK
+    with open(path, "rb") as src, open(path + ".gz", "wb") as dst:
+        while True:
+            piece = src.read(piece_bytes)
+            if not piece:
+                break
+            dst.write(_lib.bgzf_compress_host(piece))
+        dst.write(_lib.BGZF_EOF)
+    os.remove(path)
+
+
+def run_text_host(input_file, output_path, nextera_file, tso_file, split=False, keep_quals=False, bgzf=False, host_search=False, stats=None):
+    """The host path of C3POa_demux.py --parse gpu (and the oracle of its tests): plain Python, no record limit.  The input is
+    FASTA (read_fasta) or FASTQ (seqio.fastx_read, in the dict semantics of read_fasta), by its first byte, through gzip.open
+    when it is gzip; demultiplex() as it stands (host_search: c3_demux_host instead of k_demux); then the one file or the
+    per-sample files, compressed by the host statement of k_bgzf under bgzf.  Returns (reads written, reads in the file)."""
+    from c3poa_amd import seqio
+    stats = {} if stats is None else stats
+    a_names, _a = load_indexes(nextera_file)
+    b_names, _b = load_indexes(tso_file)
+    if split:
+        sample_files(a_names, b_names)
+    gz = _is_gzip(input_file)
+    opener = (lambda p: gzip.open(p, "rt")) if gz else open
+    with opener(input_file) as fh:
+        first = fh.read(1)
+    quals = None
+    if first == "@":
+        reads, quals = {}, {}
+        try:
+            for name, seq, q in seqio.fastx_read(input_file, fh=opener(input_file)):
+                if name not in reads:
+                    reads[name] = ""
+                reads[name], quals[name] = seq, q
+        except ValueError as e:
+            raise DemuxError("%s: %s" % (input_file, e))
+        if keep_quals and any(q is None for q in quals.values()):
+            sys.exit(NO_QUALS % input_file)
+    else:
+        if keep_quals:
+            sys.exit(NO_QUALS % input_file)
+        reads = read_fasta(input_file, opener)
+    indexed = demultiplex(reads, nextera_file, tso_file, host=host_search)
+    kept = [name for name, seq in reads.items() if len(seq) > HEAD]
+    if len(kept) != len(indexed):
+        raise DemuxError("%s: two reads get the same name" % input_file)
+    first_dir, ext = _out_names(split, keep_quals, False)
+    os.makedirs(output_path, exist_ok=True)
+
+    def record(name, new, seq):
+        return "@%s\n%s\n+\n%s\n" % (new, seq, quals[name]) if keep_quals else ">%s\n%s\n" % (new, seq)
+
+    written = []
+    if split:
+        d = os.path.join(output_path, "samples")
+        os.makedirs(d, exist_ok=True)
+        per = {}
+        for name, (new, seq) in zip(kept, indexed.items()):
+            per.setdefault(new[len(name) + 1:], []).append(record(name, new, seq))
+        for sample, recs in per.items():
+            written.append(os.path.join(d, sample + ext))
+            with open(written[-1], "w") as out:
+                out.write("".join(recs))
+    else:
+        written.append(os.path.join(output_path, "Indexed_reads" + ext))
+        with open(written[-1], "w") as out:
+            items = list(zip(kept, indexed.items()))
+            for i in range(0, len(items), 4096):
+                out.write("".join(record(name, new, seq) for name, (new, seq) in items[i:i + 4096]))
+    if bgzf:
+        for p in written:
+            _bgzf_file_host(p)
+    stats["files"] = len(written)
+    return len(indexed), len(reads)
+
+
+def run_text_gpu(input_file, output_path, nextera_file, tso_file, split=False, keep_quals=False, bgzf=False, inflate_gpu=False,
+                 chunk=EMIT_CHUNK, handle=None, stats=None):
+    """C3POa_demux.py --emit gpu --parse gpu: the input goes to the device as text (or, with inflate_gpu, as BGZF members) in
+    pieces of `chunk` bytes (postprocess._text_pieces); c3_demux_emit_text parses, searches, places and formats there and returns
+    one stream, or one per sample under split, whose bytes are appended to .part files that take their names at the end.
+    Returns (reads written, reads in the file), or None after a one-line note on stderr where the host path has to take over
+    (nothing is left behind then); stats (a dict) receives chunks, records_device, inflated_bytes, streams, files, append_seconds
+    (host time spent appending to the .part files) and fallback."""
+    from c3poa_amd import postprocess
+    stats = {} if stats is None else stats
+    stats.update(chunks=0, records_device=0, inflated_bytes=0, streams=1, files=0, append_seconds=0.0, fallback=None)
+    a_names, a_seqs = load_indexes(nextera_file)
+    b_names, b_seqs = load_indexes(tso_file)
+    table = sample_files(a_names, b_names) if split else None
+    first_name, ext = _out_names(split, keep_quals, bgzf)
+    made_dir = not os.path.isdir(output_path)
+    sample_dir = os.path.join(output_path, "samples")
+    made_samples = split and not os.path.isdir(sample_dir)
+    files, state = {}, {"own": None}                             # target path -> its open .part file, or None (opened per append)
+
+    def append(target, data):
+        if target not in files:
+            os.makedirs(os.path.dirname(target), exist_ok=True)
+            keep = sum(fh is not None for fh in files.values()) < MAX_OPEN_PARTS
+            files[target] = open(target + ".part", "wb") if keep else None
+            if not keep:
+                open(target + ".part", "wb").close()
+        if files[target] is not None:
+            files[target].write(data)
+        else:
+            with open(target + ".part", "ab") as fh:
+                fh.write(data)
+
+    def discard():
+        for target, fh in files.items():
+            if fh is not None:
+                fh.close()
+            os.remove(target + ".part")
+        files.clear()
+        for d, made in ((sample_dir, made_samples), (output_path, made_dir)):
+            if made and os.path.isdir(d):
+                try:
+                    os.rmdir(d)
+                except OSError:
+                    pass
+
+    def fallback(reason):
+        discard()
+        stats["fallback"] = reason
+        print("C3POa_demux: --parse gpu falls back to the host path: %s" % reason, file=sys.stderr)
+        return None
+
+    if not _plain(a_names + a_seqs + b_names + b_seqs):
+        return fallback("an index name or sequence holds '|' or a byte >= 0x80")
+    sets = _lib.DemuxSets(a_names, a_seqs, b_names, b_seqs)
+    if split:
+        stats["streams"] = sets.n_split_streams
+        if sets.n_split_streams > _lib.DEMUX_MAX_STREAMS:
+            return fallback("%d sample streams; the device takes %d" % (sets.n_split_streams, _lib.DEMUX_MAX_STREAMS))
+        pairs = [(a, b) for a in a_names + [""] for b in b_names + [""]]           # stream a * (n_b + 1) + b
+        targets = [os.path.join(sample_dir, table[p] + ext) for p in pairs]
+    else:
+        targets = [os.path.join(output_path, first_name)]
+    flags = (_lib.DEMUX_SPLIT if split else 0) | (_lib.DEMUX_KEEP_QUALS if keep_quals else 0) | (_lib.DEMUX_OUT_BGZF if bgzf else 0)
+    if handle is None:
+        handle = state["own"] = _lib.Handle(device=0)
+    written, collected, bufs, tail = 0, [], {}, 0
+    try:
+        handle.demux_text_reset()
+        for piece, at_eof, in_bgzf in postprocess._text_pieces(input_file, max(1, int(chunk)), inflate_gpu):
+            try:
+                res = handle.demux_emit_text(sets, piece, at_eof=at_eof, flags=flags | (_lib.DEMUX_IN_BGZF if in_bgzf else 0), bufs=bufs)
+            except _lib.C3Error as e:
+                if keep_quals and "C3_DEMUX_KEEP_QUALS on a FASTA text" in str(e):
+                    discard()
+                    sys.exit(NO_QUALS % input_file)
+                return fallback("c3_demux_emit_text: %s" % str(e).split(": ", 1)[-1])
+            info = res.info
+            stats["chunks"] += 1
+            stats["records_device"] += info["n_records"]
+            stats["inflated_bytes"] += info["text_bytes"] - tail
+            tail = info["text_bytes"] - info["consumed"]
+            if info["departed"]:
+                return fallback("the input departs from the %s rule behind record %d" % ("FASTA" if info["kind"] == 2 else "strict FASTQ", stats["records_device"]))
+            written += info["n_kept"]
+            if info["n_records"]:
+                collected.append(res.hashes)
+            so = res.stream_off
+            t_w = time.perf_counter()
+            for s in np.flatnonzero(so[1:] > so[:-1]).tolist():
+                append(targets[s], res.arena[int(so[s]):int(so[s + 1])].data)
+            stats["append_seconds"] = round(stats["append_seconds"] + time.perf_counter() - t_w, 4)
+        allh = np.concatenate(collected) if collected else np.empty(0, dtype=np.uint64)
+        if np.unique(allh).size != allh.size:
+            return fallback("repeated names in the input (the host path keeps one record per name)")
+        os.makedirs(sample_dir if split else output_path, exist_ok=True)
+        if not split and not files:
+            append(targets[0], b"")
+        for target, fh in files.items():
+            if bgzf:
+                append(target, _lib.BGZF_EOF)
+            if fh is not None:
+                fh.close()
+            os.replace(target + ".part", target)
+        stats["files"] = len(files)
+        files.clear()
+        return written, int(allh.size)
+    except _lib.C3Error as e:                                    # (the piece cutter: a BGZF file that ends inside a member)
+        return fallback(str(e))
+    except BaseException:
+        discard()
+        raise
+    finally:
         if state["own"] is not None:
             state["own"].close()

@@ -19,9 +19,10 @@ def _open(path):
     return open(path, "r")
 
 
-def fastx_read(path, read_comment=False):
-    """Yield (name, seq, qual) like mappy.fastx_read; qual is None for FASTA records."""
-    with _open(path) as fh:
+def fastx_read(path, read_comment=False, fh=None):
+    """Yield (name, seq, qual) like mappy.fastx_read; qual is None for FASTA records.  fh: an open text file to read instead
+    of opening `path`."""
+    with (fh if fh is not None else _open(path)) as fh:
         line = fh.readline()
         while line:
             if not line.strip():

@@ -655,6 +655,56 @@ int c3_post_emit_text(c3_handle* h, const char* src, int64_t n, int at_eof, int 
 int c3_post_text_reset(c3_handle* h);
 int c3_post_text_timing_get(c3_handle* h, c3_post_text_timing* t);
 
+/* ---- Sample demultiplexer, pieces of text in / per-sample streams out (C3POa_demux.py --parse gpu) ----
+ * c3_demux_emit_text: consecutive pieces of one read file in, the renamed records out, with nothing visiting the host in
+ * between.  src holds plain text, or with C3_DEMUX_IN_BGZF whole BGZF members (inflated by k_inflate under the rules of "BGZF
+ * input": C3_E_DATA on a damaged member).  The handle keeps the unconsumed tail of the (inflated) text on the device and puts
+ * it in front of the next piece; at_eof != 0 ends the file; c3_demux_text_reset drops the tail and forgets the file's kind.
+ * The kind is the one the first byte of the text announces: '>' = 2, FASTA under the rule of c3_demux_emit (whole-line names,
+ * wrapped sequences, the strip set, departures 1 and 2); '@' = 4, FASTQ under the strict four-line rule ("Strict FASTA /
+ * FASTQ records": name = header up to the first blank or tab, departed = 1); any other first byte is a departure (departed = 1,
+ * nothing consumed).  Every record with more than C3_DEMUX_HEAD sequence bytes is searched (c3_demux_indexes) and written as
+ * '>' name '|' A '_' B '\n' sequence '\n', or with C3_DEMUX_KEEP_QUALS (kind 4 only; on kind 2: C3_E_ARG) as
+ * '@' name '|' A '_' B '\n' sequence '\n' '+' '\n' quality '\n'.
+ * Output: S streams in arena, stream s at [stream_off[s], stream_off[s + 1]).  S = 1 without C3_DEMUX_SPLIT: every record in
+ * input order (for a FASTA text exactly the bytes of c3_demux_emit).  With C3_DEMUX_SPLIT S = (n_a + 1) * (n_b + 1) and a record
+ * goes to stream a * (n_b + 1) + b, a = the winner of set A (n_a where there is none), b likewise; records keep their input
+ * order within a stream.  S > C3_DEMUX_MAX_STREAMS: C3_E_LIMIT.  With C3_DEMUX_OUT_BGZF every non-empty stream is compressed
+ * by k_bgzf as one text (byte for byte c3_bgzf_compress_host of that stream; no EOF member) and stream_off describes what is
+ * delivered.  Too small a cap: C3_E_LIMIT with stream_off filled (stream_off[S] = bytes needed; with C3_DEMUX_OUT_BGZF the sum
+ * of c3_bgzf_bound over the non-empty streams) and the arena left alone.  name_hash[n_records]: the 64-bit FNV-1a of every
+ * delivered record's name, kept or not; n_records > max_records: C3_E_LIMIT with info->n_records = the need.
+ * info: n_records delivered, n_kept written, text_bytes = tail + (inflated) piece, consumed = how many of them the delivered
+ * records cover, out_bytes, departed, kind (0 while no byte was seen), n_streams = S.  A departure delivers the records in front
+ * of it.  Every refusal happens before anything is written to arena and leaves the kept tail as it was, so the same piece can be
+ * passed again.
+ * c3_demux_emit_text_host is the host statement for ONE plain text of a stated kind (no tail, no inflation):
+ * c3_fasta_parse_host or c3_fastx_strict_parse_host, then c3_demux_host, then the same streams, with C3_DEMUX_OUT_BGZF through
+ * c3_bgzf_compress_host; C3_DEMUX_IN_BGZF and a kind other than 2 or 4 are C3_E_ARG.  Errors through c3_last_error(NULL).
+ * c3_demux_text_timing_get: times of the last call -- host time of the inflation and of the compression loop, hipEvent times of
+ * the parse (with its read-backs and the gather), k_demux (with the head copies), the placement (k_dsplit_key, _tile, _cols,
+ * _offs) and k_dsplit_emit, host time of the call with its copies, and the number of stream waits of the call. */
+#define C3_DEMUX_IN_BGZF 1
+#define C3_DEMUX_OUT_BGZF 2
+#define C3_DEMUX_KEEP_QUALS 4
+#define C3_DEMUX_SPLIT 8
+#define C3_DEMUX_MAX_STREAMS 4096
+typedef struct {                  /* the ten index arguments of c3_demux_emit */
+  int n_a; const char* a_cat; const int64_t* a_off; const char* a_names; const int64_t* a_name_off;
+  int n_b; const char* b_cat; const int64_t* b_off; const char* b_names; const int64_t* b_name_off;
+} c3_demux_sets;
+typedef struct { int64_t n_records, n_kept, consumed, text_bytes, out_bytes; int32_t departed, kind, n_streams; } c3_demux_text_info;
+typedef struct { float ms_inflate, ms_parse, ms_demux, ms_split, ms_emit, ms_bgzf, ms_call;
+                 int64_t n_records, n_kept, in_bytes, text_bytes, out_bytes; int32_t n_streams, n_waits; } c3_demux_text_timing;
+int c3_demux_emit_text(c3_handle* h, const char* src, int64_t n, int at_eof, int flags, const c3_demux_sets* sets,
+                       char* arena, int64_t cap, int64_t* stream_off, uint64_t* name_hash, int64_t max_records,
+                       c3_demux_text_info* info);
+int c3_demux_emit_text_host(const char* text, int64_t n, int at_eof, int kind, int flags, const c3_demux_sets* sets,
+                            char* arena, int64_t cap, int64_t* stream_off, uint64_t* name_hash, int64_t max_records,
+                            c3_demux_text_info* info);
+int c3_demux_text_reset(c3_handle* h);
+int c3_demux_text_timing_get(c3_handle* h, c3_demux_text_timing* t);
+
 #ifdef __cplusplus
 }
 #endif
