@@ -35,7 +35,8 @@ EXPORTS = ["c3_default_config", "c3_version", "c3_device_count", "c3_warm_device
            "c3_fasta_parse", "c3_fasta_parse_host", "c3_demux_emit", "c3_demux_emit_host", "c3_demux_emit_timing",
            "c3_emit_group", "c3_emit_group_host", "c3_batch_emit_snapshot", "c3_batch_emit_fetch", "c3_emit_timing_get", "c3_append_streams",
            "c3_fastx_strict_parse_host", "c3_post_emit_text", "c3_post_text_reset", "c3_post_text_timing_get",
-           "c3_demux_emit_text", "c3_demux_emit_text_host", "c3_demux_text_reset", "c3_demux_text_timing_get"]
+           "c3_demux_emit_text", "c3_demux_emit_text_host", "c3_demux_text_reset", "c3_demux_text_timing_get",
+           "c3_reader_stage_on_device", "c3_reader_device_group", "c3_reader_stage_stats"]
 
 
 ZERO_MAX_CELLS = 16777216       # c3_default_config's zero_max_cells: largest front * tail the zero-repeat rescue takes
@@ -162,6 +163,10 @@ class EmitTiming(C.Structure):
 class HostBatchStruct(C.Structure):
     _fields_ = [("n", C.c_int32), ("n_short", C.c_int64), ("names", C.c_void_p), ("name_off", C.c_void_p),
                 ("seqs", C.c_void_p), ("quals", C.c_void_p), ("off", C.c_void_p)]
+
+
+class DeviceBatchStruct(C.Structure):      # c3_device_batch
+    _fields_ = [("d_seqs", C.c_void_p), ("d_quals", C.c_void_p), ("device", C.c_int32), ("bytes", C.c_int64)]
 
 
 _lib = None
@@ -291,6 +296,9 @@ def load():
     lib.c3_demux_emit_text_host.argtypes = dt + [C.c_int] + dt2
     lib.c3_demux_text_reset.argtypes = [vp]
     lib.c3_demux_text_timing_get.argtypes = [vp, C.POINTER(DemuxTextTiming)]
+    lib.c3_reader_stage_on_device.argtypes = [vp, C.c_int]
+    lib.c3_reader_device_group.argtypes = [vp, C.c_int, C.POINTER(DeviceBatchStruct)]
+    lib.c3_reader_stage_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _lib = lib
     return lib
 
@@ -1121,13 +1129,16 @@ class HostBatch:
 class Reader:
     """native streaming FASTA/FASTQ(.gz) reader (c3_reader_*): mm.fastx_read replacement that yields SoA groups"""
 
-    def __init__(self, path, n_sets=3, names_only=False, byte_range=None, inflate_device=None, parse_device=False):
+    def __init__(self, path, n_sets=3, names_only=False, byte_range=None, inflate_device=None, parse_device=False, stage_device=False):
         """byte_range = (beg, end): only the records that START inside [beg, end) (plain files; c3_reader_open_range)
         inflate_device = d: a BGZF file is inflated by k_inflate on device d (c3_reader_open_inflate; whole-file readers)
         parse_device: ... and its records are parsed there too (k_fastq; c3_reader_parse_on_device).  C3Error with code
-        E_STATE when the reader is not one of a BGZF file with inflate_device"""
+        E_STATE when the reader is not one of a BGZF file with inflate_device
+        stage_device: ... and the bases and qualities of its groups stay there (c3_reader_stage_on_device): a device group has
+        hb.dev (c3_device_batch) and no seqs / quals; after a departure the groups are host groups (hb.dev is None)"""
         self.lib = load()
         self.r = C.c_void_p()
+        self.n_sets, self._cur = max(1, int(n_sets)), -1
         if inflate_device is not None:
             if byte_range is not None:
                 raise ValueError("inflate_device goes with a whole-file reader")
@@ -1149,6 +1160,15 @@ class Reader:
                 e.code = rc
                 self.close()
                 raise e
+        self.stage_device = False
+        if stage_device:
+            rc = self.lib.c3_reader_stage_on_device(self.r, 1)
+            if rc != 0:
+                e = C3Error("c3_reader_stage_on_device failed (%d): %s" % (rc, self.lib.c3_reader_error(self.r).decode()))
+                e.code = rc
+                self.close()
+                raise e
+            self.stage_device = True
 
     def next(self, max_reads, min_len=0, max_bases=0, set_index=None):
         """next group; set_index names the buffer set to fill (caller-managed free list), None = round-robin"""
@@ -1157,11 +1177,23 @@ class Reader:
             rc = self.lib.c3_reader_next(self.r, int(max_reads), int(max_bases), int(min_len), C.byref(c))
         else:
             rc = self.lib.c3_reader_next_set(self.r, int(set_index), int(max_reads), int(max_bases), int(min_len), C.byref(c))
+        cur = self._set_of(set_index)
         if rc != 0:
             raise ValueError("c3_reader_next: %s" % self.lib.c3_reader_error(self.r).decode())
         hb = HostBatch(c, self)
         hb.set_index = set_index
+        hb.dev = None
+        if self.stage_device and hb.n > 0 and not c.seqs:        # a device group: its bases lie in the reader's device set
+            d = DeviceBatchStruct()
+            if self.lib.c3_reader_device_group(self.r, cur, C.byref(d)) != 0:
+                raise ValueError("c3_reader_device_group failed")
+            hb.dev = d if d.d_seqs else None
         return hb
+
+    def _set_of(self, set_index):
+        """the buffer set the call just made filled: the one named, or the next one round-robin (c3_reader_next's rule)"""
+        self._cur = int(set_index) if set_index is not None else (self._cur + 1) % self.n_sets
+        return self._cur
 
     def noqual(self):
         """records without a quality line read so far (FASTA)"""
@@ -1179,6 +1211,13 @@ class Reader:
         parse_device reader: c3_reader_parse_stats"""
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         self.lib.c3_reader_parse_stats(self.r, C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value, c.value
+
+    def stage_stats(self):
+        """(groups delivered on the device, groups delivered on the host, bytes of bases + qualities brought to the host) of a
+        stage_device reader: c3_reader_stage_stats"""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self.lib.c3_reader_stage_stats(self.r, C.byref(a), C.byref(b), C.byref(c))
         return a.value, b.value, c.value
 
     def range_lost(self):

@@ -31,3 +31,10 @@ extern "C" int c3_bgzf_stretch_parse(c3_bgzf* z, int slot, const char* comp, int
                                      int at_eof, c3_fq_stretch* out);
 extern "C" int c3_bgzf_stretch_fetch(c3_bgzf* z, int slot, int64_t r0, int64_t r1, char* names, char* seqs, char* quals);
 extern "C" int c3_bgzf_stretch_text(c3_bgzf* z, int slot, int64_t from, int64_t len, char* dst);
+// the reader's device buffer sets (c3_reader_stage_on_device): n_sets pairs of grow-only device buffers; _reserve grows set
+// `set` to `bytes` per array keeping its first `keep`; _stretch_stage = _stretch_fetch with the bases and qualities copied
+// device to device into the set at byte `at` instead of to the host; _set_get: the set's pointers and device
+extern "C" int c3_bgzf_sets_create(c3_bgzf* z, int n_sets);
+extern "C" int c3_bgzf_set_reserve(c3_bgzf* z, int set, int64_t bytes, int64_t keep);
+extern "C" int c3_bgzf_stretch_stage(c3_bgzf* z, int slot, int64_t r0, int64_t r1, char* names, int set, int64_t at);
+extern "C" int c3_bgzf_set_get(const c3_bgzf* z, int set, const char** d_seqs, const char** d_quals, int* device);

@@ -230,4 +230,7 @@ struct c3_bgzf {
   DBuf d_cnt, d_nl, d_slen, d_nlen, d_bsum, d_hdr;
   C3FqHdr* h_hdr = nullptr;
   hipStream_t copy_stream = nullptr;
+  // the reader's device buffer sets (c3_reader_stage_on_device): the home of a device group, filled from the slots on copy_stream
+  struct DevSet { DBuf seqs, quals; };
+  std::vector<DevSet> dsets;
 };

@@ -65,6 +65,7 @@ struct BatchSet {
   HostBuf names, seqs, quals;
   std::vector<int64_t> name_off, off;
   size_t n_names = 0, n_bases = 0;
+  bool on_dev = false;                      // the group it holds is a device group: its bases lie in the reader's device set (c3_reader_stage_on_device)
 };
 
 }  // namespace
@@ -103,6 +104,9 @@ struct Bgzf {
   bool parse_req = false, parse_on = false, dev_active = false;
   int64_t carry_from = 0, carry_len = 0;    // the next load starts with these bytes of the current stretch's text
   std::atomic<int64_t> n_dev{0}, n_host{0}, rec_dev{0};
+  // c3_reader_stage_on_device: while dev_active, groups stay on the device (one device set per host set, held by dev)
+  bool stage_on = false;
+  int64_t grp_dev = 0, grp_host = 0, host_bytes = 0;
 };
 
 struct c3_reader {
@@ -452,6 +456,39 @@ extern "C" int c3_reader_parse_on_device(c3_reader* r, int on) {
   return C3_E_OK;
 }
 
+extern "C" int c3_reader_stage_on_device(c3_reader* r, int on) {
+  if (!r) return C3_E_ARG;
+  if (!r->bz || !r->bz->dev || !r->bz->parse_req) { r->err = "c3_reader_stage_on_device: needs c3_reader_parse_on_device(r, 1) in force"; return C3_E_STATE; }
+  if (r->started) { r->err = "c3_reader_stage_on_device: after the first c3_reader_next"; return C3_E_STATE; }
+  if (on) {
+    const int rc = c3_bgzf_sets_create(r->bz->dev, (int)r->sets.size());
+    if (rc != C3_E_OK) { r->err = c3_last_error(nullptr); return rc; }
+  }
+  r->bz->stage_on = on != 0;
+  return C3_E_OK;
+}
+
+extern "C" int c3_reader_device_group(const c3_reader* r, int set, c3_device_batch* out) {
+  if (!r || !out || set < 0 || set >= (int)r->sets.size()) return C3_E_ARG;
+  out->d_seqs = out->d_quals = nullptr; out->device = -1; out->bytes = 0;
+  const BatchSet& s = r->sets[(size_t)set];
+  if (!s.on_dev) return C3_E_OK;                                  // a host group (or none): no device pointers
+  int dev = -1;
+  const int rc = c3_bgzf_set_get(r->bz->dev, set, &out->d_seqs, &out->d_quals, &dev);
+  if (rc != C3_E_OK) return rc;
+  out->device = dev; out->bytes = (int64_t)s.n_bases;
+  return C3_E_OK;
+}
+
+extern "C" int c3_reader_stage_stats(const c3_reader* r, int64_t* groups_device, int64_t* groups_host, int64_t* host_bytes) {
+  if (!r) return C3_E_ARG;
+  const Bgzf* b = r->bz;
+  if (groups_device) *groups_device = b ? b->grp_dev : 0;
+  if (groups_host) *groups_host = b ? b->grp_host : 0;
+  if (host_bytes) *host_bytes = b ? b->host_bytes : 0;
+  return C3_E_OK;
+}
+
 extern "C" int c3_reader_parse_stats(const c3_reader* r, int64_t* stretches_device, int64_t* stretches_host, int64_t* records_device) {
   if (!r) return C3_E_ARG;
   const Bgzf* b = r->bz;
@@ -504,6 +541,8 @@ int device_fill(c3_reader* r, BatchSet& s, int max_reads, int64_t max_bases, int
   Bgzf* b = r->bz;
   int n = *pn; size_t nn = *pnn, nb = *pnb; int64_t n_short = *pshort;
   int rc = C3_E_OK;
+  const bool stage = b->stage_on && !r->names_only;              // the bases stay on the device, in the set of the same number
+  const int set = (int)(&s - r->sets.data());
   while (n < max_reads && (max_bases <= 0 || (int64_t)nb < max_bases)) {
     BgzfStretch* c = &b->st[b->cur];
     if (!c->on_dev || c->next_rec == c->fq.info.n_kept) {
@@ -551,13 +590,16 @@ int device_fill(c3_reader* r, BatchSet& s, int max_reads, int64_t max_bases, int
         for (BatchSet& o : r->sets) if (&o != &s) {
           if (left == 0) break;
           const size_t w2 = std::min(want, left + 4096);
-          if (!o.seqs.reserve(w2, 0) || !o.quals.reserve(w2, 0)) return C3_E_NOMEM;
+          if (stage) { if (c3_bgzf_set_reserve(b->dev, (int)(&o - r->sets.data()), (int64_t)w2, 0) != C3_E_OK) { r->err = c3_last_error(nullptr); return C3_E_NOMEM; } }
+          else if (!o.seqs.reserve(w2, 0) || !o.quals.reserve(w2, 0)) return C3_E_NOMEM;
           left -= std::min(left, w2);
         }
       }
-      if (!s.seqs.reserve(want, nb0) || !s.quals.reserve(want, nb0)) return C3_E_NOMEM;
+      if (stage) { if (c3_bgzf_set_reserve(b->dev, set, (int64_t)want, (int64_t)nb0) != C3_E_OK) { r->err = c3_last_error(nullptr); return C3_E_NOMEM; } }
+      else if (!s.seqs.reserve(want, nb0) || !s.quals.reserve(want, nb0)) return C3_E_NOMEM;
     }
-    rc = c3_bgzf_stretch_fetch(b->dev, b->cur, j0, j, s.names.p + nn0, r->names_only ? nullptr : s.seqs.p + nb0, r->names_only ? nullptr : s.quals.p + nb0);
+    rc = stage ? c3_bgzf_stretch_stage(b->dev, b->cur, j0, j, s.names.p + nn0, set, (int64_t)nb0)
+               : c3_bgzf_stretch_fetch(b->dev, b->cur, j0, j, s.names.p + nn0, r->names_only ? nullptr : s.seqs.p + nb0, r->names_only ? nullptr : s.quals.p + nb0);
     if (rc != C3_E_OK) { b->why = c3_last_error(nullptr); b->bad = true; b->dev_active = false; break; }
     r->n_records += j - j0; b->rec_dev += j - j0;
     c->next_rec = j;
@@ -582,10 +624,15 @@ extern "C" int c3_reader_next_set(c3_reader* r, int set, int max_reads, int64_t 
   r->cur = set;
   BatchSet& s = r->sets[(size_t)r->cur];
   s.name_off.assign(1, 0); s.off.assign(1, 0);
+  s.on_dev = false;
+  // c3_reader_stage_on_device: while the device parser hands out records the group is built in the device set of this number
+  const bool stage_rd = r->bz && r->bz->stage_on && !r->names_only;
+  const bool try_dev = stage_rd && r->bz->dev_active;
   if (!r->names_only && r->hint_bases) {
     // later sets are allocated once, with the size the previous groups needed (growth by copying only for the first)
     const size_t want = r->hint_bases + r->hint_bases / 8 + 4096;
-    if (!s.seqs.reserve(want, 0) || !s.quals.reserve(want, 0)) return C3_E_NOMEM;
+    if (try_dev) { if (c3_bgzf_set_reserve(r->bz->dev, set, (int64_t)want, 0) != C3_E_OK) { r->err = c3_last_error(nullptr); return C3_E_NOMEM; } }
+    else if (!stage_rd && (!s.seqs.reserve(want, 0) || !s.quals.reserve(want, 0))) return C3_E_NOMEM;
   }
   size_t nn = 0, nb = 0; int n = 0; int64_t n_short = 0;
   const char* p; size_t l;
@@ -594,10 +641,19 @@ extern "C" int c3_reader_next_set(c3_reader* r, int set, int max_reads, int64_t 
     const int rc = device_fill(r, s, max_reads, max_bases, min_len, &n, &nn, &nb, &n_short);
     if (rc != C3_E_OK) return rc;
   }                                                               // ... and after a departure the loop below goes on with the same group
-  while (n < max_reads && (max_bases <= 0 || (int64_t)nb < max_bases)) {
+  // ... unless it is a device group: that one ends in front of the departure (or at the end of the device's records) when it
+  // holds a record; when it holds none the call goes on as an ordinary host group, in the page-locked set
+  const bool dev_group = try_dev && n > 0;
+  bool size_host_set = stage_rd && !dev_group && r->hint_bases;   // ... sized like a later set, but only once the text does hold a record
+  while (!dev_group && n < max_reads && (max_bases <= 0 || (int64_t)nb < max_bases)) {
     if (!next_line(r, &p, &l)) break;
     if (l == 0) continue;
     if (p[0] != '>' && p[0] != '@') return fail(r, "not FASTA/FASTQ: record does not start with '>' or '@'");
+    if (size_host_set) {
+      size_host_set = false;
+      const size_t want = r->hint_bases + r->hint_bases / 8 + 4096;
+      if (!s.seqs.reserve(want, 0) || !s.quals.reserve(want, 0)) return C3_E_NOMEM;
+    }
     if (r->range_end >= 0 && r->buf_off + (int64_t)(p - r->buf.data()) >= r->range_end) { r->eof = true; r->beg = r->end; break; }   // next range's record
     // name = header up to the first blank (read_comment=False)
     size_t nl = 1; while (nl < l && p[nl] != ' ' && p[nl] != '\t') ++nl;
@@ -666,6 +722,8 @@ extern "C" int c3_reader_next_set(c3_reader* r, int set, int max_reads, int64_t 
   out->n = n; out->n_short = n_short;
   out->names = s.names.p; out->name_off = s.name_off.data();
   out->seqs = s.seqs.p; out->quals = s.quals.p; out->off = s.off.data();
+  if (dev_group) { s.on_dev = true; out->seqs = out->quals = nullptr; ++r->bz->grp_dev; }
+  else if (r->bz && r->bz->stage_on && n > 0) { ++r->bz->grp_host; r->bz->host_bytes += 2 * (int64_t)nb; }
   return C3_E_OK;
 }
 

@@ -319,6 +319,61 @@ extern "C" int c3_bgzf_stretch_fetch(c3_bgzf* z, int slot, int64_t r0, int64_t r
   return C3_E_OK;
 }
 
+// ---- the reader's device buffer sets (c3_reader_stage_on_device) ----------
+extern "C" int c3_bgzf_sets_create(c3_bgzf* z, int n_sets) {
+  if (!z || n_sets < 1) return host_fail(C3_E_ARG, "c3_bgzf_sets_create: bad arguments");
+  if (z->dsets.size() < (size_t)n_sets) z->dsets.resize((size_t)n_sets);
+  return C3_E_OK;
+}
+
+// grow-only; the first `keep` bytes of both arrays survive a growth (a group that outgrows its set while it is being filled)
+extern "C" int c3_bgzf_set_reserve(c3_bgzf* z, int set, int64_t bytes, int64_t keep) {
+  if (!z || set < 0 || (size_t)set >= z->dsets.size() || bytes < 0 || keep < 0) return host_fail(C3_E_ARG, "c3_bgzf_set_reserve: bad arguments");
+  c3_bgzf::DevSet& d = z->dsets[(size_t)set];
+  if ((size_t)bytes <= d.seqs.cap && (size_t)bytes <= d.quals.cap) return C3_E_OK;
+  if ((size_t)keep > std::min(d.seqs.cap, d.quals.cap)) return host_fail(C3_E_ARG, "c3_bgzf_set_reserve: keep beyond the set");
+  ZCHK(hipSetDevice(z->device), "hipSetDevice");
+  if (!z->copy_stream) ZCHK(hipStreamCreateWithFlags(&z->copy_stream, hipStreamNonBlocking), "device set");
+  const size_t want = keep ? std::max((size_t)bytes, d.seqs.cap + d.seqs.cap / 2) : (size_t)bytes;
+  for (DBuf* b : {&d.seqs, &d.quals}) {
+    DBuf nb;
+    ZCHK(nb.ensure(want), "device set");
+    if (keep) {
+      ZCHK(hipMemcpyAsync(nb.p, b->p, (size_t)keep, hipMemcpyDeviceToDevice, z->copy_stream), "device set");
+      ZCHK(hipStreamSynchronize(z->copy_stream), "device set");
+    }
+    *b = std::move(nb);                                              // (the old allocation goes with nb)
+  }
+  return C3_E_OK;
+}
+
+// records [r0, r1) of the slot's stretch into a device group: names to the host (at the place of record r0), bases and
+// qualities device to device into set `set` from byte `at` on.  Runs on copy_stream and has landed on return, so the slot may
+// be loaded again and another stream may read the set without an event.
+extern "C" int c3_bgzf_stretch_stage(c3_bgzf* z, int slot, int64_t r0, int64_t r1, char* names, int set, int64_t at) {
+  if (!z || slot < 0 || slot > 1 || !names || set < 0 || (size_t)set >= z->dsets.size() || at < 0) return host_fail(C3_E_ARG, "c3_bgzf_stretch_stage: bad arguments");
+  const c3_bgzf::FqSlot& sl = z->fq[slot];
+  if (r0 < 0 || r1 < r0 || r1 > sl.n_rec) return host_fail(C3_E_ARG, "c3_bgzf_stretch_stage: records outside the stretch");
+  if (r0 == r1) return C3_E_OK;
+  c3_bgzf::DevSet& d = z->dsets[(size_t)set];
+  const int64_t nb = sl.h_name_off[r0], ne = sl.h_name_off[r1], sb = sl.h_off[r0], se = sl.h_off[r1];
+  if ((size_t)(at + (se - sb)) > std::min(d.seqs.cap, d.quals.cap)) return host_fail(C3_E_ARG, "c3_bgzf_stretch_stage: run beyond the set");
+  ZCHK(hipSetDevice(z->device), "hipSetDevice");
+  if (ne > nb) ZCHK(hipMemcpyAsync(names, sl.names.as<char>() + nb, (size_t)(ne - nb), hipMemcpyDeviceToHost, z->copy_stream), "stretch stage");
+  if (se > sb) {
+    ZCHK(hipMemcpyAsync(d.seqs.as<char>() + at, sl.seqs.as<char>() + sb, (size_t)(se - sb), hipMemcpyDeviceToDevice, z->copy_stream), "stretch stage");
+    ZCHK(hipMemcpyAsync(d.quals.as<char>() + at, sl.quals.as<char>() + sb, (size_t)(se - sb), hipMemcpyDeviceToDevice, z->copy_stream), "stretch stage");
+  }
+  ZCHK(hipStreamSynchronize(z->copy_stream), "stretch stage");
+  return C3_E_OK;
+}
+
+extern "C" int c3_bgzf_set_get(const c3_bgzf* z, int set, const char** d_seqs, const char** d_quals, int* device) {
+  if (!z || set < 0 || (size_t)set >= z->dsets.size() || !d_seqs || !d_quals || !device) return host_fail(C3_E_ARG, "c3_bgzf_set_get: bad arguments");
+  *d_seqs = z->dsets[(size_t)set].seqs.as<char>(); *d_quals = z->dsets[(size_t)set].quals.as<char>(); *device = z->device;
+  return C3_E_OK;
+}
+
 // text [from, from + len) of the slot's stretch copied to the host (a departure: the host parser takes over from there)
 extern "C" int c3_bgzf_stretch_text(c3_bgzf* z, int slot, int64_t from, int64_t len, char* dst) {
   if (!z || slot < 0 || slot > 1 || from < 0 || len < 0 || (len > 0 && !dst)) return host_fail(C3_E_ARG, "c3_bgzf_stretch_text: bad arguments");

@@ -705,6 +705,42 @@ int c3_demux_emit_text_host(const char* text, int64_t n, int at_eof, int kind, i
 int c3_demux_text_reset(c3_handle* h);
 int c3_demux_text_timing_get(c3_handle* h, c3_demux_text_timing* t);
 
+/* ---- Groups kept on the device ----
+ * With c3_reader_parse_on_device the bases and qualities of every read are gathered on the device, copied down into the
+ * reader's page-locked sets, from where a caller that works on the device has to copy them straight back up.  These calls leave
+ * them where they are and hand out device pointers.
+ *
+ * c3_reader_stage_on_device(r, on != 0): valid only on a reader with c3_reader_parse_on_device(r, 1) in force that has not
+ * delivered its first group; otherwise C3_E_STATE with a c3_reader_error text (null reader: C3_E_ARG).  Such a reader keeps
+ * one DEVICE buffer set per host set (owned, grow-only, on the reader's device, sized as the host sets are); the page-locked
+ * seqs / quals blocks of its host sets are not allocated while its groups stay on the device (c3_reader_reserved_bytes counts
+ * host memory only and shows that).  A DEVICE GROUP is formed by the group rule of c3_reader_next_set, unchanged; each run of
+ * records that enters it is copied device to device into the set named by the call, at the group's fill offsets, and the
+ * copies have landed when the call returns.  names, name_off, off, n and n_short come to the host as ever; seqs == quals ==
+ * NULL in the c3_host_batch.  c3_reader_device_group(r, set, out) describes the group set `set` holds: d_seqs / d_quals
+ * (off[] of the c3_host_batch indexes them), the device ordinal and bytes = off[n].  For a set that holds a host group, or none,
+ * it returns C3_E_OK with d_seqs == d_quals == NULL, device = -1 and bytes = 0.  A set is overwritten only when the caller names
+ * it again.
+ * DEPARTURE (see "FASTQ records on the GPU"): a device group that meets the first record that is not strict ends in front of
+ * it when it holds at least one record -- group boundaries may therefore differ from the host parser's there; the
+ * concatenation of all groups does not.  When it holds none the same call goes on as an ordinary HOST GROUP (non-NULL seqs /
+ * quals in the page-locked set), so n == 0 still means the end of the file.  From then on every group is
+ * a host group.  The text that the last stretch leaves over at the end of the file (a record without its final newline) is
+ * handed over in the same way.  names_only readers deliver no bases either way and are not affected.
+ * c3_reader_stage_stats: groups (n > 0) delivered on the device / on the host since c3_reader_stage_on_device(r, 1), and the
+ * bytes of bases and qualities that host groups brought to the host (0 while no departure occurred).
+ * A caller reads a device group with kernels or copies of its own on the group's device; the group's set must stay unnamed
+ * for as long as it does. */
+typedef struct {
+  const char* d_seqs;        /* device pointers; read i at [off[i], off[i + 1]) of both */
+  const char* d_quals;
+  int32_t device;            /* HIP device ordinal the group lies on */
+  int64_t bytes;             /* bytes of each array = off[n] */
+} c3_device_batch;
+int c3_reader_stage_on_device(c3_reader* r, int on);
+int c3_reader_device_group(const c3_reader* r, int set, c3_device_batch* out);
+int c3_reader_stage_stats(const c3_reader* r, int64_t* groups_device, int64_t* groups_host, int64_t* host_bytes);
+
 #ifdef __cplusplus
 }
 #endif
