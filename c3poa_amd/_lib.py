@@ -74,22 +74,28 @@ class Timing(C.Structure):
                [(n, C.c_int64) for n in ("cells_polish_computed", "n_band_layers", "n_band_fallback", "n_band_mismatch", "n_win_redo", "n_poa_redo16")]
 
 
+def _fields_dict(t):
+    """a timing structure as a dict of its fields"""
+    return {f[0]: getattr(t, f[0]) for f in t._fields_}
+
+
+class _Info(C.Structure):
+    """base of the *_info structures of include/c3poa.h: all integers"""
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _t in self._fields_}
+
+
 class QvTiming(C.Structure):
     _fields_ = [("ms_qv", C.c_float)] + [(n, C.c_int64) for n in ("n_reads", "n_pieces", "n_skipped", "band_cells", "edge_hits")]
 
 
-class FastaInfo(C.Structure):
+class FastaInfo(_Info):
     _fields_ = [(k, C.c_int64) for k in ("n_records", "consumed", "name_bytes", "base_bytes")] + [("departed", C.c_int32)]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _t in self._fields_}
 
-
-class DemuxInfo(C.Structure):
+class DemuxInfo(_Info):
     _fields_ = [(k, C.c_int64) for k in ("n_records", "n_kept", "consumed", "out_bytes")] + [("departed", C.c_int32)]
-
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _t in self._fields_}
 
 
 class DemuxTiming(C.Structure):
@@ -101,12 +107,9 @@ class DemuxSetsStruct(C.Structure):       # c3_demux_sets
     _fields_ = [(k + f, t) for k in "ab" for f, t in (("_n", C.c_int), ("_cat", C.c_void_p), ("_off", C.c_void_p), ("_names", C.c_void_p), ("_name_off", C.c_void_p))]
 
 
-class DemuxTextInfo(C.Structure):
+class DemuxTextInfo(_Info):
     _fields_ = [(k, C.c_int64) for k in ("n_records", "n_kept", "consumed", "text_bytes", "out_bytes")] + \
                [(k, C.c_int32) for k in ("departed", "kind", "n_streams")]
-
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _t in self._fields_}
 
 
 class DemuxTextTiming(C.Structure):
@@ -115,25 +118,16 @@ class DemuxTextTiming(C.Structure):
                [(n, C.c_int32) for n in ("n_streams", "n_waits")]
 
 
-class FastqInfo(C.Structure):
+class FastqInfo(_Info):
     _fields_ = [(k, C.c_int64) for k in ("n_records", "n_kept", "n_short", "consumed", "name_bytes", "base_bytes")] + [("departed", C.c_int32)]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _t in self._fields_}
 
-
-class FastxInfo(C.Structure):
+class FastxInfo(_Info):
     _fields_ = [(k, C.c_int64) for k in ("n_records", "consumed", "name_bytes", "base_bytes")] + [("departed", C.c_int32)]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _t in self._fields_}
 
-
-class PostTextInfo(C.Structure):
+class PostTextInfo(_Info):
     _fields_ = [(k, C.c_int64) for k in ("n_records", "n_kept", "consumed", "text_bytes", "out_bytes")] + [("departed", C.c_int32)]
-
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _t in self._fields_}
 
 
 class PostTextTiming(C.Structure):
@@ -446,7 +440,7 @@ class Handle:
         """c3_batch_qv_timing: k_qv figures of the last run with STAGE_QV"""
         t = QvTiming()
         self._chk(self.lib.c3_batch_qv_timing(self.h, C.byref(t)))
-        return {f[0]: getattr(t, f[0]) for f in QvTiming._fields_}
+        return _fields_dict(t)
 
     def results_raw(self, into=None):
         """(results structured array, consensus byte buffer, cons_off[n+1]) without building Python strings.
@@ -506,7 +500,7 @@ class Handle:
     def timing(self):
         t = Timing()
         self._chk(self.lib.c3_batch_timing(self.h, C.byref(t)))
-        return {f[0]: getattr(t, f[0]) for f in Timing._fields_}
+        return _fields_dict(t)
 
     # ---- probes
     def track(self, i):
@@ -605,47 +599,14 @@ class Handle:
         (uint64 array of n_records), guards_intact.  cap / max_records: instead of sizes found by asking again; C3Error (code,
         .info, .stream_off, .guards_intact, .untouched) on a refusal.  bufs: a dict the call keeps its output arrays in from one
         piece to the next (no guard bytes then; the results are views that the next call overwrites)."""
-        src = piece if isinstance(piece, np.ndarray) else np.frombuffer(_bytes(piece), dtype=np.uint8)
-        n = len(src)
         flags = (POST_IN_BGZF if in_bgzf else 0) | (POST_OUT_BGZF if out_bgzf else 0) | (POST_KEEP_QUALS if keep_quals else 0)
         a = _post_args(plan, 0, None, None, None, None, None, None)
-        S = plan.n_streams
-        so = np.zeros(S + 1, dtype=np.int64)
-        info = PostTextInfo()
-        ask = cap is None and max_records is None
-        cap = (24 if in_bgzf else 3) * n + 65536 if cap is None else int(cap)
-        max_records = (8 if in_bgzf else 1) * (n // 8) + 16 if max_records is None else int(max_records)
-        g = FASTA_GUARD if bufs is None else 0
-        for _try in range(3):
-            if bufs is None:
-                arena, hashes = np.full(cap + 2 * g, 0xA5, dtype=np.uint8), np.full(8 * max_records + 2 * g, 0xA5, dtype=np.uint8)
-            else:
-                if len(bufs.get("arena", ())) < cap:
-                    bufs["arena"] = np.empty(cap, dtype=np.uint8)
-                if len(bufs.get("hashes", ())) < 8 * max_records:
-                    bufs["hashes"] = np.empty(8 * max_records, dtype=np.uint8)
-                arena, hashes, cap, max_records = bufs["arena"], bufs["hashes"], len(bufs["arena"]), len(bufs["hashes"]) // 8
-            rc = self.lib.c3_post_emit_text(self.h, src.ctypes.data if n else None, n, int(bool(at_eof)), flags, C.byref(a), arena.ctypes.data + g, cap,
-                                            so.ctypes.data, hashes.ctypes.data + g, max_records, C.byref(info))
-            if ask and rc == E_LIMIT and (so[S] > cap or info.n_records > max_records):
-                cap, max_records = max(cap, int(so[S])), max(max_records, int(info.n_records))
-                continue
-            break
-        out = PostText()
-        out.info, out.stream_off = info.as_dict(), so
-        used = {"arena": int(so[S]), "hashes": 8 * int(info.n_records)} if rc == 0 else {"arena": 0, "hashes": 0}
-        out.guards_intact, out.untouched_beyond_results = _guarded({"arena": arena, "hashes": hashes}, used) if bufs is None else (True, True)
-        if rc != 0:
-            e = C3Error("c3 error %d: %s" % (rc, self.lib.c3_last_error(self.h).decode()))
-            e.code, e.info, e.stream_off, e.guards_intact, e.untouched = rc, out.info, so, out.guards_intact, out.untouched_beyond_results
-            raise e
-        out.arena = arena[g:g + used["arena"]]
-        out.hashes = hashes[g:g + used["hashes"]].view(np.uint64).copy()
-        return out
+        return _text_call(lambda *x: self.lib.c3_post_emit_text(self.h, *x), lambda: self.lib.c3_last_error(self.h), piece,
+                          (int(bool(at_eof)), flags, C.byref(a)), plan.n_streams, PostTextInfo(), in_bgzf, cap, max_records, bufs)
 
     def demux_emit_text(self, sets, piece, at_eof=False, flags=0, cap=None, max_records=None, bufs=None):
         """c3_demux_emit_text: the next piece of a read file (bytes or a uint8 array; whole BGZF members with DEMUX_IN_BGZF)
-        through parse, k_demux, k_dsplit and k_bgzf on the device.  sets: a DemuxSets.  Returns a DemuxText (_demux_text_call)."""
+        through parse, k_demux, k_dsplit and k_bgzf on the device.  sets: a DemuxSets.  Returns a DemuxText (_text_call)."""
         return _demux_text_call(lambda *a: self.lib.c3_demux_emit_text(self.h, *a), lambda: self.lib.c3_last_error(self.h), sets, piece, at_eof,
                                 None, flags, cap, max_records, bufs)
 
@@ -657,7 +618,7 @@ class Handle:
         """c3_demux_text_timing_get: times, counts and stream waits of the last demux_emit_text"""
         t = DemuxTextTiming()
         self._chk(self.lib.c3_demux_text_timing_get(self.h, C.byref(t)))
-        return {f[0]: getattr(t, f[0]) for f in DemuxTextTiming._fields_}
+        return _fields_dict(t)
 
     def post_text_reset(self):
         """c3_post_text_reset: drops the tail the text path keeps between two pieces and forgets the file's kind"""
@@ -667,13 +628,13 @@ class Handle:
         """c3_post_text_timing_get: times of the last post_emit_text"""
         t = PostTextTiming()
         self._chk(self.lib.c3_post_text_timing_get(self.h, C.byref(t)))
-        return {f[0]: getattr(t, f[0]) for f in PostTextTiming._fields_}
+        return _fields_dict(t)
 
     def post_emit_timing(self):
         """c3_post_emit_timing: event times of the three passes of the last post_emit and the call with its copies"""
         t = PostTiming()
         self._chk(self.lib.c3_post_emit_timing(self.h, C.byref(t)))
-        return {f[0]: getattr(t, f[0]) for f in PostTiming._fields_}
+        return _fields_dict(t)
 
     def emit_group(self, hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, zero=True, cap=None, arena=None):
         """c3_emit_group (k_emit): the file bytes of write_group (+ write_consensus_fastq with qv_buf) for one group, as an
@@ -706,7 +667,7 @@ class Handle:
         """c3_emit_timing_get: event times of the last emit_group, or of the snapshot the last emit_fetch delivered"""
         t = EmitTiming()
         self._chk(self.lib.c3_emit_timing_get(self.h, C.byref(t)))
-        return {f[0]: getattr(t, f[0]) for f in EmitTiming._fields_}
+        return _fields_dict(t)
 
     def demux_indexes(self, heads, set_a, set_b, return_dist=False):
         """c3_demux_indexes (k_demux): winners (n, 2) int32 of index sets A and B (index number or -1) for every head
@@ -735,7 +696,7 @@ class Handle:
         the call with its copies"""
         t = DemuxTiming()
         self._chk(self.lib.c3_demux_emit_timing(self.h, C.byref(t)))
-        return {f[0]: getattr(t, f[0]) for f in DemuxTiming._fields_}
+        return _fields_dict(t)
 
     def consensus_qv(self, cons, pieces):
         """c3_consensus_qv (k_qv): Phred+33 QV string of `cons` from pieces = [(seq, qual, mode)], mode QV_GLOBAL /
@@ -850,12 +811,60 @@ def _ptr(x):
 POST_IN_BGZF, POST_OUT_BGZF, POST_KEEP_QUALS = 1, 2, 4       # flags of c3_post_emit_text
 
 
-class PostText:
-    """result of c3_post_emit_text: info (dict), arena (uint8 array), stream_off (int64 array of S + 1), hashes (uint64 array)"""
+class TextResult:
+    """result of c3_post_emit_text, c3_demux_emit_text and c3_demux_emit_text_host: info (dict), arena (uint8 array), stream_off
+    (int64 array of S + 1), hashes (uint64 array of n_records), guards_intact, untouched_beyond_results"""
 
     def streams(self):
         so = self.stream_off
         return [self.arena[int(so[s]):int(so[s + 1])].tobytes() for s in range(len(so) - 1)]
+
+
+PostText = DemuxText = TextResult
+_SO_GUARD = -0x5A5A5A5A5A5A5A5B
+
+
+def _text_call(fn, err, piece, mid, S, info, in_z, cap, max_records, bufs=None, s_max=None):
+    """one "text in, file bytes out" call: fn(src, n, *mid, arena, cap, stream_off, hashes, max_records, info) with S streams (the C
+    side refuses more than s_max).  piece: bytes or a uint8 array.  cap / max_records: instead of sizes found by asking again;
+    C3Error (code, .info, .stream_off, .guards_intact, .untouched) on a refusal.  bufs: a dict the call keeps its output arrays in
+    from one piece to the next (no guard bytes then; the results are views that the next call overwrites)."""
+    src = piece if isinstance(piece, np.ndarray) else np.frombuffer(_bytes(piece), dtype=np.uint8)
+    n = len(src)
+    s_ok = s_max is None or S <= s_max
+    so = np.zeros((S if s_ok else s_max) + 1 + 2, dtype=np.int64)
+    so[0] = so[-1] = _SO_GUARD                                           # a guard word either side
+    ask = cap is None and max_records is None
+    cap = (24 if in_z else 3) * n + 65536 if cap is None else int(cap)
+    max_records = (8 if in_z else 1) * (n // 8) + 16 if max_records is None else int(max_records)
+    g = FASTA_GUARD if bufs is None else 0
+    for _try in range(3):
+        if bufs is None:
+            arena, hashes = np.full(cap + 2 * g, 0xA5, dtype=np.uint8), np.full(8 * max_records + 2 * g, 0xA5, dtype=np.uint8)
+        else:
+            if len(bufs.get("arena", ())) < cap:
+                bufs["arena"] = np.empty(cap, dtype=np.uint8)
+            if len(bufs.get("hashes", ())) < 8 * max_records:
+                bufs["hashes"] = np.empty(8 * max_records, dtype=np.uint8)
+            arena, hashes, cap, max_records = bufs["arena"], bufs["hashes"], len(bufs["arena"]), len(bufs["hashes"]) // 8
+        rc = fn(src.ctypes.data if n else None, n, *mid, arena.ctypes.data + g, cap, so.ctypes.data + 8, hashes.ctypes.data + g, max_records,
+                C.byref(info))
+        if ask and rc == E_LIMIT and s_ok and (so[S + 1] > cap or info.n_records > max_records):
+            cap, max_records = max(cap, int(so[S + 1])), max(max_records, int(info.n_records))
+            continue
+        break
+    out = TextResult()
+    out.info, out.stream_off = info.as_dict(), so[1:-1]
+    used = {"arena": int(so[S + 1]), "hashes": 8 * int(info.n_records)} if rc == 0 else {"arena": 0, "hashes": 0}
+    out.guards_intact, out.untouched_beyond_results = _guarded({"arena": arena, "hashes": hashes}, used) if bufs is None else (True, True)
+    out.guards_intact = bool(out.guards_intact and so[0] == so[-1] == _SO_GUARD)
+    if rc != 0:
+        e = C3Error("c3 error %d: %s" % (rc, err().decode()))
+        e.code, e.info, e.stream_off, e.guards_intact, e.untouched = rc, out.info, out.stream_off, out.guards_intact, out.untouched_beyond_results
+        raise e
+    out.arena = arena[g:g + used["arena"]]
+    out.hashes = hashes[g:g + used["hashes"]].view(np.uint64).copy()
+    return out
 
 
 def _post_args(plan, n, names, name_off, seqs, quals, off, table):
@@ -1721,58 +1730,12 @@ DEMUX_IN_BGZF, DEMUX_OUT_BGZF, DEMUX_KEEP_QUALS, DEMUX_SPLIT = 1, 2, 4, 8     # 
 DEMUX_MAX_STREAMS = 4096
 
 
-class DemuxText:
-    """result of c3_demux_emit_text / c3_demux_emit_text_host: info (dict), arena (uint8 array), stream_off (int64 array of
-    S + 1), hashes (uint64 array of n_records), guards_intact, untouched_beyond_results"""
-
-    def streams(self):
-        so = self.stream_off
-        return [self.arena[so[s]:so[s + 1]].tobytes() for s in range(len(so) - 1)]
-
-
 def _demux_text_call(fn, err, sets, piece, at_eof, kind, flags, cap, max_records, bufs=None):
-    """one c3_demux_emit_text (kind None) or c3_demux_emit_text_host call.  cap / max_records: instead of sizes found by asking
-    again; C3Error (code, .info, .stream_off, .guards_intact, .untouched) on a refusal.  bufs: a dict the call keeps its output
-    arrays in from one piece to the next (no guard bytes then; the results are views that the next call overwrites)."""
-    src = piece if isinstance(piece, np.ndarray) else np.frombuffer(_bytes(piece), dtype=np.uint8)
-    n = len(src)
-    S = sets.n_split_streams if flags & DEMUX_SPLIT else 1
-    so = np.full(min(S, DEMUX_MAX_STREAMS) + 1 + 2, -0x5A5A5A5A5A5A5A5B, dtype=np.int64)         # a guard word either side
+    """one c3_demux_emit_text (kind None) or c3_demux_emit_text_host call through _text_call"""
     st = sets.struct
-    info = DemuxTextInfo()
-    ask = cap is None and max_records is None
-    in_z = bool(flags & DEMUX_IN_BGZF)
-    cap = (24 if in_z else 3) * n + 65536 if cap is None else int(cap)
-    max_records = (8 if in_z else 1) * (n // 8) + 16 if max_records is None else int(max_records)
-    g = FASTA_GUARD if bufs is None else 0
-    for _try in range(3):
-        if bufs is None:
-            arena, hashes = np.full(cap + 2 * g, 0xA5, dtype=np.uint8), np.full(8 * max_records + 2 * g, 0xA5, dtype=np.uint8)
-        else:
-            if len(bufs.get("arena", ())) < cap:
-                bufs["arena"] = np.empty(cap, dtype=np.uint8)
-            if len(bufs.get("hashes", ())) < 8 * max_records:
-                bufs["hashes"] = np.empty(8 * max_records, dtype=np.uint8)
-            arena, hashes, cap, max_records = bufs["arena"], bufs["hashes"], len(bufs["arena"]), len(bufs["hashes"]) // 8
-        args = (src.ctypes.data if n else None, n, int(bool(at_eof))) + (() if kind is None else (int(kind),)) + \
-               (int(flags), C.byref(st), arena.ctypes.data + g, cap, so.ctypes.data + 8, hashes.ctypes.data + g, max_records, C.byref(info))
-        rc = fn(*args)
-        if ask and rc == E_LIMIT and S <= DEMUX_MAX_STREAMS and (so[S + 1] > cap or info.n_records > max_records):
-            cap, max_records = max(cap, int(so[S + 1])), max(max_records, int(info.n_records))
-            continue
-        break
-    out = DemuxText()
-    out.info, out.stream_off = info.as_dict(), so[1:-1]
-    used = {"arena": int(so[S + 1]), "hashes": 8 * int(info.n_records)} if rc == 0 else {"arena": 0, "hashes": 0}
-    out.guards_intact, out.untouched_beyond_results = _guarded({"arena": arena, "hashes": hashes}, used) if bufs is None else (True, True)
-    out.guards_intact = out.guards_intact and so[0] == so[-1] == -0x5A5A5A5A5A5A5A5B
-    if rc != 0:
-        e = C3Error("c3 error %d: %s" % (rc, err().decode()))
-        e.code, e.info, e.stream_off, e.guards_intact, e.untouched = rc, out.info, out.stream_off, out.guards_intact, out.untouched_beyond_results
-        raise e
-    out.arena = arena[g:g + used["arena"]]
-    out.hashes = hashes[g:g + used["hashes"]].view(np.uint64).copy()
-    return out
+    mid = (int(bool(at_eof)),) + (() if kind is None else (int(kind),)) + (int(flags), C.byref(st))
+    return _text_call(fn, err, piece, mid, sets.n_split_streams if flags & DEMUX_SPLIT else 1, DemuxTextInfo(), bool(flags & DEMUX_IN_BGZF),
+                      cap, max_records, bufs, DEMUX_MAX_STREAMS)
 
 
 def demux_emit_text_host(sets, text, at_eof=True, kind=2, flags=0, cap=None, max_records=None):

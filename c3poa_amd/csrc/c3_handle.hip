@@ -167,7 +167,6 @@ extern "C" void c3_destroy(c3_handle* h) {
   for (hipEvent_t ev : h->ev_fa) if (ev) (void)hipEventDestroy(ev);
   for (c3h::EmitBufs* eb : {&h->emit_sa, &h->emit_snap}) for (hipEvent_t ev : eb->ev) if (ev) (void)hipEventDestroy(ev);
   if (h->ev_emit_dn) (void)hipEventDestroy(h->ev_emit_dn);
-  if (h->h_emit_sizes) (void)hipHostFree(h->h_emit_sizes);
   if (h->h_fa_hdr) (void)hipHostFree(h->h_fa_hdr);
   c3h::post_text_free(h);
   c3h::demux_text_free(h);
@@ -432,7 +431,7 @@ extern "C" int c3_batch_results(c3_handle* h, c3_read_result* res, char* cons, i
 //                           and formats from the resident buffers into the snapshot's own arena: the consensus and QV bytes of
 //                           read i lie at d_cons / d_qv + off[i], their length is the record's.  One 8 * (S + 2)-byte read back.
 //   c3_batch_emit_fetch     copies the streams out on the download stream; with C3_EMIT_BGZF each stream goes through k_bgzf
-//                           first (chunks of BGZF_CHUNK_BLOCKS blocks, staged 4-byte aligned with 256 bytes of slack behind them).
+//                           first (c3h::bgzf_chunks, c3_stream.hip; the packed members of the last chunks land at the wait that ends the call).
 extern "C" int c3_batch_emit_snapshot(c3_handle* h, const char* names, const int64_t* name_off, int zero, int flags) {
   if (!h || h->n <= 0 || !names || !name_off || (flags & ~C3_EMIT_BGZF)) return C3_E_ARG;
   if (h->emit_pending.load(std::memory_order_acquire)) return c3_fail(h, C3_E_STATE, "c3_batch_emit_snapshot: the previous emit snapshot has not been fetched");
@@ -495,35 +494,15 @@ extern "C" int c3_batch_emit_fetch(c3_handle* h, char* arena, int64_t cap, int64
     out = need;
   } else {
     const double t_z = dbg_now_ms();
-    const int64_t CH = (int64_t)BGZF_CHUNK_BLOCKS * BGZF_BLOCK;
     int64_t longest = 0;
     for (int x = 0; x < S; ++x) longest = std::max(longest, so[(size_t)x + 1] - so[(size_t)x]);
-    const int64_t first = std::min(CH, longest);
-    const int nb_max = (int)((first + BGZF_BLOCK - 1) / BGZF_BLOCK);
-    if (!h->h_emit_sizes) DNCHK(hipHostMalloc((void**)&h->h_emit_sizes, BGZF_CHUNK_BLOCKS * sizeof(int), hipHostMallocDefault));
-    DNCHK(h->d_emit_zin.ensure((size_t)first + 256)); DNCHK(h->d_emit_zslots.ensure((size_t)nb_max * BGZF_SLOT));
-    DNCHK(h->d_emit_zsizes.ensure((size_t)nb_max * sizeof(int))); DNCHK(h->d_emit_zpacked.ensure((size_t)nb_max * BGZF_MAX_MEMBER));
+    DNCHK(h->emit_zs.reserve(longest));
     for (int x = 0; x < S; ++x) {
       stream_off[x] = out;
-      const int64_t len = so[(size_t)x + 1] - so[(size_t)x];
-      for (int64_t c0 = 0; c0 < len; c0 += CH) {
-        const int64_t cn = std::min(CH, len - c0);
-        const int nb = (int)((cn + BGZF_BLOCK - 1) / BGZF_BLOCK);
-        DNCHK(hipMemcpyAsync(h->d_emit_zin.p, src + so[(size_t)x] + c0, (size_t)cn, hipMemcpyDeviceToDevice, dn));
-        c3k_launch_bgzf(h->d_emit_zin.as<uint8_t>(), (long long)cn, nb, h->d_emit_zslots.as<uint8_t>(), h->d_emit_zsizes.as<int>(), h->d_emit_zpacked.as<uint8_t>(), dn);
-        DNCHK(hipGetLastError());
-        DNCHK(hipMemcpyAsync(h->h_emit_sizes, h->d_emit_zsizes.p, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, dn));
-        DNCHK(hipStreamSynchronize(dn));
-        int64_t tot = 0;
-        for (int b = 0; b < nb; ++b) {
-          const int sz = h->h_emit_sizes[b];
-          if (sz < BGZF_HDR + 13 || sz > BGZF_MAX_MEMBER) { h->emit_pending.store(false, std::memory_order_release); return C3_E_HIP; }
-          tot += sz;
-        }
-        if (out + tot > cap) { h->emit_pending.store(false, std::memory_order_release); return C3_E_HIP; }      // (cannot be: cap >= the sum of the bounds)
-        DNCHK(hipMemcpyAsync(arena + out, h->d_emit_zpacked.p, (size_t)tot, hipMemcpyDeviceToHost, dn));
-        out += tot;
-      }
+      const char* sx = src + so[(size_t)x];
+      const c3h::ZStatus st = c3h::bgzf_chunks(h->emit_zs, dn, so[(size_t)x + 1] - so[(size_t)x], [&](char* d_zin, int64_t c0, int64_t cn) {
+        return hipMemcpyAsync(d_zin, sx + c0, (size_t)cn, hipMemcpyDeviceToDevice, dn); }, arena, cap, &out, false);
+      if (st.e != hipSuccess || st.bad) { h->emit_pending.store(false, std::memory_order_release); return C3_E_HIP; }
     }
     stream_off[S] = out;
     DNCHK(hipStreamSynchronize(dn));

@@ -1,5 +1,6 @@
-// c3_host.h -- what the HIP host units share (c3_handle.hip, c3_stages.hip, c3_calls.hip, c3_scans.hip, c3_stream.hip): the two
-// handles, the owned device buffer, the error idioms and the few helpers that cross units.  Host only; no kernel includes it.
+// c3_host.h -- what the HIP host units share (c3_handle.hip, c3_stages.hip, c3_calls.hip, c3_scans.hip, c3_stream.hip, and the text
+// paths: c3_tfront.hip -- the front that c3_text.hip and c3_dtext.hip share): the two handles, the owned device buffer, the
+// error idioms and the few helpers that cross units.  Host only; no kernel includes it.
 #pragma once
 #include "c3_dev.h"
 #include "c3_args.h"
@@ -9,6 +10,7 @@
 #include "c3_post.h"
 #include "c3_fastx.h"
 #include "c3_dsplit.h"
+#include "c3_bgzf.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -16,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -31,20 +34,47 @@ int post_sizes(c3_handle* h, const c3_post_args* a, PostArgs& p, std::vector<int
 int post_write(c3_handle* h, PostArgs& p, int64_t need);
 int adapters_device(c3_handle* h, const C3Batch& b, int64_t max_len, int32_t* d_out);
 int bgzf_inflate_to_device(c3_bgzf* z, const char* src, int64_t n, int64_t nm, uint8_t* d_dst, int64_t* out_len);    // c3_stream.hip
-void post_text_free(c3_handle* h);                                                                                     // c3_text.hip
 // k_fasta on a text that lies on the device, the gather of its records, the index sets of a search (c3_scans.hip)
 namespace fa { enum { FA_TEXT, FA_CNT, FA_NL, FA_LSE, FA_LDST, FA_BSUM, FA_HDR, FA_OFF, FA_NOFF, FA_RECL, FA_HASH, FA_NAMES, FA_SEQS, FA_KREC, FA_ROFF,
                       FA_OUT, FA_ANAMES, FA_ANO, FA_BNAMES, FA_BNO, FA_N }; }      // the slots of c3_handle::d_fa
 int fasta_parse_resident(c3_handle* h, const uint8_t* d_text, int64_t n, int at_eof, int kept, FaArgs* a);
 int fasta_gather_resident(c3_handle* h, FaArgs* a);
 int demux_sets_device(c3_handle* h, const c3_demux_sets* st, const uint8_t* tab, int K, int64_t nk, FaArgs* a);
+// ---- one BGZF chunk loop (c3_stream.hip) ----
 struct ZStage;
-// one device-resident stream compressed by k_bgzf as one text into the host arena at *out (c3_text.hip)
-int bgzf_stream_device(c3_handle* h, ZStage& z, const char* d_src, int64_t len, char* arena, int64_t cap, int64_t* out);
+// how a compression by chunks ended: a HIP error at step `what`, or a member size out of range / members beyond the arena's
+// cap; waits = the stream waits it made.  Each caller maps it to its own error channel.
+struct ZStatus { hipError_t e = hipSuccess; enum { OK, MEMBER_SIZE, BEYOND_BOUND } bad = OK; const char* what = ""; int waits = 0; };
+// queues bytes [c0, c0 + cn) of a compression's source into the staging input d_zin on the loop's stream
+typedef std::function<hipError_t(char* d_zin, int64_t c0, int64_t cn)> ZStageIn;
+// len source bytes compressed by k_bgzf as one text into the host arena at *out, a chunk of blocks at a time (BGZF_CHUNK_BLOCKS, or
+// the test hook C3_BGZF_CHUNK = 1 .. 2048: members are cut every BGZF_BLOCK bytes whatever the chunk).  wait_after_copy_out:
+// wait for every chunk's packed members to land; otherwise the last copies are still queued on s at return.
+ZStatus bgzf_chunks(ZStage& z, hipStream_t s, int64_t len, const ZStageIn& stage_in, char* arena, int64_t cap, int64_t* out, bool wait_after_copy_out);
+// ---- the text front that c3_post_emit_text and c3_demux_emit_text share (c3_tfront.hip) ----
+struct TextFront;
+struct TextLoad { int nxt = 0, kind = 0, waits = 0; int64_t total = 0; float ms_inflate = 0; };       // what text_load made
+void text_free(TextFront& t);
+void text_reset(TextFront& t);
+// the kept tail + the piece in text[cur ^ 1] (copied up, or inflated in place), the file's kind; who / keep_flag: the entry point
+// and its keep-quals flag, for the messages; ev[n_ev]: the caller's events, created with the page-locked buffers on first use
+int text_load(c3_handle* h, TextFront& t, const char* src, int64_t n, bool in_z, bool keep_q, const char* who, const char* keep_flag,
+              hipEvent_t* ev, int n_ev, TextLoad* ld);
+// k_fastq_count .. k_fastx_records over the loaded text: f filled, the checked header in t.h_hdr (zero when no record pass ran);
+// *waits (optional) grows by the stream waits made; ev_begin / ev_records (optional) are recorded in front of k_fastq_count / directly after k_fastx_records
+int text_tables(c3_handle* h, TextFront& t, const TextLoad& ld, int at_eof, FxArgs& f, int* waits, hipEvent_t ev_begin = nullptr, hipEvent_t ev_records = nullptr);
+// names / seqs / quals sized by the header, k_fastx_gather queued (ev_begin, optional, recorded in front of it)
+int text_gather(c3_handle* h, TextFront& t, FxArgs& f, bool keep_q, hipEvent_t ev_begin = nullptr);
+// the switch: this call's text becomes the kept one (the last thing a successful call does)
+void text_commit(TextFront& t, const TextLoad& ld, int64_t consumed, int at_eof);
+// one device-resident stream compressed as one text into the host arena at *out (bgzf_chunks on h->stream, errors into h->err);
+// *waits grows by the stream waits made
+int bgzf_stream_device(c3_handle* h, ZStage& z, const char* d_src, int64_t len, char* arena, int64_t cap, int64_t* out, int* waits = nullptr);
+void post_text_free(c3_handle* h);                                                                                     // c3_text.hip
 void demux_text_free(c3_handle* h);                                                                                    // c3_dtext.hip
 }
 
-#define BGZF_CHUNK_BLOCKS 2048                   // BGZF blocks per device chunk of a compression (c3_stream.hip, c3_batch_emit_fetch)
+#define BGZF_CHUNK_BLOCKS 2048                   // BGZF blocks per device chunk of a compression (c3h::bgzf_chunks)
 
 static inline double dbg_now_ms() { using namespace std::chrono; return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count(); }
 // C3_DEBUG=1: progress lines on stderr, each stamped with the host clock (ms) -- shows the host gaps between the stages
@@ -84,27 +114,44 @@ struct DBuf {                                   // owns one device allocation (m
 // k_emit_len / the scans / k_emit_write
 struct c3h::EmitBufs { DBuf work, offs, arena; hipEvent_t ev[5] = {}; };
 
-// the text path of the post-processing step (c3_text.hip): text[cur] holds the text of the last call, its bytes
-// [tail_from, text_n) being the unconsumed tail that goes in front of the next piece; the passes' tables and arenas; the inflater
-// staging of a compression by chunks (c3h::bgzf_stream_device): the chunk, k_bgzf's slots, member sizes and packed members;
-// the page-locked copy of the sizes (BGZF_CHUNK_BLOCKS ints, allocated by the owner)
-struct c3h::ZStage { DBuf zin, zslots, zsizes, zpacked; int* h_sizes = nullptr; };
-struct PostText {
+// staging of a compression by chunks (c3h::bgzf_chunks): the chunk, k_bgzf's slots, member sizes and packed members; the
+// page-locked copy of the sizes.  Owned by c3_bgzf, c3_handle (the emit snapshot's fetch) and TextFront.
+struct c3h::ZStage {
+  DBuf zin, zslots, zsizes, zpacked; int* h_sizes = nullptr;
+  ~ZStage() { if (h_sizes) (void)hipHostFree(h_sizes); }
+  hipError_t pin() { return h_sizes ? hipSuccess : hipHostMalloc((void**)&h_sizes, BGZF_CHUNK_BLOCKS * sizeof(int), hipHostMallocDefault); }
+  // room for one chunk of cn bytes, 4-byte aligned with 256 bytes of slack (k_bgzf reads up to 8 bytes past a chunk's end:
+  // realigned dword loads); callers with several streams size it once for min(longest, a full chunk)
+  hipError_t reserve(int64_t cn) {
+    cn = std::min(cn, (int64_t)BGZF_CHUNK_BLOCKS * BGZF_BLOCK);
+    const size_t nb = (size_t)((cn + BGZF_BLOCK - 1) / BGZF_BLOCK);
+    hipError_t e = pin();
+    if (e == hipSuccess) e = zin.ensure((size_t)cn + 256);
+    if (e == hipSuccess) e = zslots.ensure(nb * BGZF_SLOT);
+    if (e == hipSuccess) e = zsizes.ensure(nb * sizeof(int));
+    if (e == hipSuccess) e = zpacked.ensure(nb * BGZF_MAX_MEMBER);
+    return e;
+  }
+};
+// what the two text paths share (c3_tfront.hip): text[cur] holds the text of the last call, its bytes [tail_from, text_n) being
+// the unconsumed tail that goes in front of the next piece; the FASTQ/FASTX parse tables and arenas; staging, inflater, read-backs
+struct c3h::TextFront {
   DBuf text[2]; int cur = 0, kind = 0; int64_t text_n = 0, tail_from = 0;
-  DBuf cnt, nl, slen, nlen, bsum, hdr, lhdr, off, name_off, woff, src, hash, names, seqs, quals, pk, table;
-  c3h::ZStage zs;
+  DBuf cnt, nl, slen, nlen, bsum, hdr, lhdr, off, name_off, woff, src, hash, names, seqs, quals;
+  ZStage zs;
   C3FxHdr* h_hdr = nullptr; C3FqHdr* h_lhdr = nullptr; c3_bgzf* z = nullptr;
+};
+// the text path of the post-processing step (c3_text.hip): the front, the 2-bit pack and k_adapter's table
+struct PostText : c3h::TextFront {
+  DBuf pk, table;
   hipEvent_t ev[8] = {};
   c3_post_text_timing tm = {};
 };
-// the text path of the demultiplexer (c3_dtext.hip): the double text buffer as in PostText; the FASTQ parse tables and arenas (a FASTA
-// text is parsed into c3_handle::d_fa); the placement tables of k_dsplit and the output arena; staging, inflater, read-backs
-struct DemuxText {
-  DBuf text[2]; int cur = 0, kind = 0; int64_t text_n = 0, tail_from = 0;
-  DBuf cnt, nl, slen, nlen, bsum, hdr, lhdr, off, name_off, woff, src, hash, names, seqs, quals;
+// the text path of the demultiplexer (c3_dtext.hip): the front (a FASTA text is parsed into c3_handle::d_fa instead of its
+// tables); the placement tables of k_dsplit and the output arena; the page-locked stream offsets
+struct DemuxText : c3h::TextFront {
   DBuf krec, kb, nkept, key, rank, base, soff, out;
-  c3h::ZStage zs;
-  C3FxHdr* h_hdr = nullptr; C3FqHdr* h_lhdr = nullptr; int64_t* h_soff = nullptr; c3_bgzf* z = nullptr;
+  int64_t* h_soff = nullptr;
   hipEvent_t ev[6] = {};
   c3_demux_text_timing tm = {};
 };
@@ -146,8 +193,8 @@ struct c3_handle {
   // k_emit: inputs of c3_emit_group and its pass buffers; times of the last c3_emit_group / delivered emit snapshot
   DBuf d_emit[10]; c3h::EmitBufs emit_sa; c3_emit_timing etm = {};
   // emit snapshot in flight (c3_batch_emit_snapshot .. _fetch): names, pass buffers + arena, BGZF staging of the fetch
-  c3h::EmitBufs emit_snap; DBuf d_emit_names, d_emit_noff, d_emit_zin, d_emit_zslots, d_emit_zsizes, d_emit_zpacked;
-  hipEvent_t ev_emit_dn = nullptr; int* h_emit_sizes = nullptr;
+  c3h::EmitBufs emit_snap; DBuf d_emit_names, d_emit_noff; c3h::ZStage emit_zs;
+  hipEvent_t ev_emit_dn = nullptr;
   std::atomic<bool> emit_pending{false}; int emit_S = 0, emit_flags = 0; std::vector<int64_t> emit_so; c3_emit_timing emit_tm = {};
   std::vector<Summary> sum; std::vector<int> work;
   int res_prefix = 0;            // entries of peaks[] / sub_beg[] / sub_end[] that any read of the resident batch uses (0: unknown)
@@ -216,8 +263,8 @@ static inline C3Params dev_params(const c3_config& c) {
 
 // the stream handle (c3_stream.hip): BGZF compress / inflate, FASTQ parse, the reader's stretches
 struct c3_bgzf {
-  int device = 0; hipStream_t stream = nullptr; int* h_sizes = nullptr;
-  DBuf d_in, d_slots, d_sizes, d_packed;
+  int device = 0; hipStream_t stream = nullptr;
+  c3h::ZStage zs;                                                // BGZF output; zs.zin also stages k_inflate's input
   C3BgzfMember* h_mem = nullptr; int2* h_res = nullptr;         // k_inflate: descriptors in, (status, CRC) out; first use
   DBuf d_mem, d_res, d_out;
   // k_fastq (first use): scratch of one parse, and two slots of text + finished records (the reader parses one stretch while

@@ -6,8 +6,39 @@
 #include "c3_inflate.h"
 
 // ---- BGZF output (k_bgzf.hip; host statement c3_bgzf.cpp) ---------------------------------
-// Input goes to the device in chunks of BGZF_CHUNK_BLOCKS blocks: copy in (the pieces land back to back), k_bgzf + k_bgzf_pack,
-// the member sizes back, then one copy of the packed members straight into the caller's buffer (BGZF_CHUNK_BLOCKS: c3_host.h).
+// Input goes to the device in chunks of BGZF_CHUNK_BLOCKS blocks: staged in (host pieces land back to back; a device stream is
+// copied device to device), k_bgzf + k_bgzf_pack, the member sizes back, then one copy of the packed members straight into the
+// caller's buffer.  One loop serves c3_bgzf_compress_pieces, the two text paths and c3_batch_emit_fetch.
+c3h::ZStatus c3h::bgzf_chunks(ZStage& z, hipStream_t s, int64_t len, const ZStageIn& stage_in, char* arena, int64_t cap, int64_t* out, bool wait_after_copy_out) {
+  ZStatus st;
+#define ZSTEP(x, w) do { if ((st.e = (x)) != hipSuccess) { st.what = w; return st; } } while (0)
+  const char* env = getenv("C3_BGZF_CHUNK");                          // test hook: the loop's later rounds at a small size
+  const int blocks = env ? atoi(env) : 0;
+  const int64_t CH = (int64_t)(blocks >= 1 && blocks <= BGZF_CHUNK_BLOCKS ? blocks : BGZF_CHUNK_BLOCKS) * BGZF_BLOCK;
+  for (int64_t c0 = 0; c0 < len; c0 += CH) {
+    const int64_t cn = std::min(CH, len - c0);
+    const int nb = (int)((cn + BGZF_BLOCK - 1) / BGZF_BLOCK);
+    ZSTEP(z.reserve(cn), "staging buffers");
+    ZSTEP(stage_in(z.zin.as<char>(), c0, cn), "copy in");
+    c3k_launch_bgzf(z.zin.as<uint8_t>(), (long long)cn, nb, z.zslots.as<uint8_t>(), z.zsizes.as<int>(), z.zpacked.as<uint8_t>(), s);
+    ZSTEP(hipGetLastError(), "k_bgzf launch");
+    ZSTEP(hipMemcpyAsync(z.h_sizes, z.zsizes.p, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s), "k_bgzf");
+    ZSTEP(hipStreamSynchronize(s), "k_bgzf");
+    ++st.waits;
+    int64_t tot = 0;
+    for (int b = 0; b < nb; ++b) {
+      const int sz = z.h_sizes[b];
+      if (sz < BGZF_HDR + 13 || sz > BGZF_MAX_MEMBER) { st.bad = ZStatus::MEMBER_SIZE; return st; }
+      tot += sz;
+    }
+    if (*out + tot > cap) { st.bad = ZStatus::BEYOND_BOUND; return st; }      // (cannot be: cap >= the sum of the bounds)
+    ZSTEP(hipMemcpyAsync(arena + *out, z.zpacked.p, (size_t)tot, hipMemcpyDeviceToHost, s), "copy out");
+    if (wait_after_copy_out) { ZSTEP(hipStreamSynchronize(s), "copy out"); ++st.waits; }      // (zpacked is written again by the next chunk)
+    *out += tot;
+  }
+#undef ZSTEP
+  return st;
+}
 
 extern "C" int c3_bgzf_create(int device, c3_bgzf** out) {
   if (!out) return C3_E_ARG;
@@ -19,7 +50,7 @@ extern "C" int c3_bgzf_create(int device, c3_bgzf** out) {
   z->device = device;
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&z->h_sizes, BGZF_CHUNK_BLOCKS * sizeof(int), hipHostMallocDefault);
+  if (e == hipSuccess) e = z->zs.pin();
   if (e != hipSuccess) { c3_bgzf_destroy(z); return host_fail(C3_E_HIP, hipGetErrorString(e)); }
   *out = z;
   return C3_E_OK;
@@ -29,7 +60,6 @@ extern "C" void c3_bgzf_destroy(c3_bgzf* z) {
   if (!z) return;
   (void)hipSetDevice(z->device);
   if (z->stream) { (void)hipStreamSynchronize(z->stream); (void)hipStreamDestroy(z->stream); }
-  if (z->h_sizes) (void)hipHostFree(z->h_sizes);
   if (z->h_mem) (void)hipHostFree(z->h_mem);
   if (z->h_res) (void)hipHostFree(z->h_res);
   if (z->copy_stream) { (void)hipStreamSynchronize(z->copy_stream); (void)hipStreamDestroy(z->copy_stream); }
@@ -47,40 +77,22 @@ extern "C" int c3_bgzf_compress_pieces(c3_bgzf* z, const char* const* p, const i
   *out_len = 0;
   if (n == 0) return C3_E_OK;
   ZCHK(hipSetDevice(z->device), "hipSetDevice");
-  const int64_t CH = (int64_t)BGZF_CHUNK_BLOCKS * BGZF_BLOCK;
-  const int64_t first = std::min(CH, n);
-  const int nb_max = (int)((first + BGZF_BLOCK - 1) / BGZF_BLOCK);
-  // k_bgzf reads up to 8 bytes past a chunk's end (realigned dword loads): the input buffer has 256 bytes of slack
-  ZCHK(z->d_in.ensure((size_t)first + 256), "input buffer");
-  ZCHK(z->d_slots.ensure((size_t)nb_max * BGZF_SLOT), "slots");
-  ZCHK(z->d_sizes.ensure((size_t)nb_max * sizeof(int)), "sizes");
-  ZCHK(z->d_packed.ensure((size_t)nb_max * BGZF_MAX_MEMBER), "packed members");
-  int64_t o = 0;
+  ZCHK(z->zs.reserve(n), "staging buffers");
   int pi = 0; int64_t pin = 0;                                  // piece index / bytes of it already sent
-  for (int64_t c0 = 0; c0 < n; c0 += CH) {
-    const int64_t cn = std::min(CH, n - c0);
-    const int nb = (int)((cn + BGZF_BLOCK - 1) / BGZF_BLOCK);
-    int64_t at = 0;
-    while (at < cn) {
+  auto pieces_in = [&](char* d_zin, int64_t, int64_t cn) {
+    for (int64_t at = 0; at < cn;) {
       while (pi < np && pin == len[pi]) { ++pi; pin = 0; }
       const int64_t k = std::min(len[pi] - pin, cn - at);
-      ZCHK(hipMemcpyAsync(z->d_in.as<char>() + at, p[pi] + pin, (size_t)k, hipMemcpyHostToDevice, z->stream), "copy in");
+      const hipError_t e = hipMemcpyAsync(d_zin + at, p[pi] + pin, (size_t)k, hipMemcpyHostToDevice, z->stream);
+      if (e != hipSuccess) return e;
       at += k; pin += k;
     }
-    c3k_launch_bgzf(z->d_in.as<uint8_t>(), (long long)cn, nb, z->d_slots.as<uint8_t>(), z->d_sizes.as<int>(), z->d_packed.as<uint8_t>(), z->stream);
-    ZCHK(hipGetLastError(), "k_bgzf launch");
-    ZCHK(hipMemcpyAsync(z->h_sizes, z->d_sizes.p, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, z->stream), "k_bgzf");
-    ZCHK(hipStreamSynchronize(z->stream), "k_bgzf");
-    int64_t tot = 0;
-    for (int b = 0; b < nb; ++b) {
-      const int s = z->h_sizes[b];
-      if (s < BGZF_HDR + 13 || s > BGZF_MAX_MEMBER) return host_fail(C3_E_HIP, "k_bgzf: member size out of range");
-      tot += s;
-    }
-    ZCHK(hipMemcpyAsync(dst + o, z->d_packed.p, (size_t)tot, hipMemcpyDeviceToHost, z->stream), "copy out");
-    ZCHK(hipStreamSynchronize(z->stream), "copy out");
-    o += tot;
-  }
+    return hipSuccess;
+  };
+  int64_t o = 0;
+  const c3h::ZStatus st = c3h::bgzf_chunks(z->zs, z->stream, n, pieces_in, dst, cap, &o, true);
+  if (st.e != hipSuccess) return bgzf_fail(st.e, st.what);
+  if (st.bad) return host_fail(C3_E_HIP, st.bad == c3h::ZStatus::MEMBER_SIZE ? "k_bgzf: member size out of range" : "k_bgzf: members beyond their bound");
   *out_len = o;
   return C3_E_OK;
 }
@@ -121,11 +133,11 @@ static int bgzf_inflate_members(c3_bgzf* z, const char* src, int64_t n, int64_t 
       oo += m.isize; at += size;
     }
     const int64_t cn = at - c0;
-    ZCHK(z->d_in.ensure((size_t)cn + 256), "input buffer");
+    ZCHK(z->zs.zin.ensure((size_t)cn + 256), "input buffer");
     if (!d_dst) ZCHK(z->d_out.ensure((size_t)oo + 256), "output buffer");
-    ZCHK(hipMemcpyAsync(z->d_in.p, src + c0, (size_t)cn, hipMemcpyHostToDevice, z->stream), "copy in");
+    ZCHK(hipMemcpyAsync(z->zs.zin.p, src + c0, (size_t)cn, hipMemcpyHostToDevice, z->stream), "copy in");
     ZCHK(hipMemcpyAsync(z->d_mem.p, z->h_mem, (size_t)k * sizeof(C3BgzfMember), hipMemcpyHostToDevice, z->stream), "copy in");
-    c3k_launch_inflate(z->d_in.as<uint8_t>(), z->d_mem.as<C3BgzfMember>(), k, d_dst ? d_dst + o : z->d_out.as<uint8_t>(), z->d_res.as<int2>(), z->stream);
+    c3k_launch_inflate(z->zs.zin.as<uint8_t>(), z->d_mem.as<C3BgzfMember>(), k, d_dst ? d_dst + o : z->d_out.as<uint8_t>(), z->d_res.as<int2>(), z->stream);
     ZCHK(hipGetLastError(), "k_inflate launch");
     ZCHK(hipMemcpyAsync(z->h_res, z->d_res.p, (size_t)k * sizeof(int2), hipMemcpyDeviceToHost, z->stream), "k_inflate");
     ZCHK(hipStreamSynchronize(z->stream), "k_inflate");
