@@ -328,7 +328,9 @@ class Handle:
         self.h = C.c_void_p()
         rc = self.lib.c3_create(C.byref(self.cfg), C.byref(self.h))
         if rc != 0:
-            raise C3Error("c3_create failed (%d): %s" % (rc, self.lib.c3_last_error(None).decode()))
+            e = C3Error("c3_create failed (%d): %s" % (rc, self.lib.c3_last_error(None).decode()))
+            e.code = rc
+            raise e
         self.n = 0
         self.lens = None
 

@@ -116,9 +116,26 @@ static thread_local std::string g_create_err;
 extern "C" const char* c3_last_error(const c3_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 void c3_set_host_error(const char* msg) { g_create_err = msg; }     // handle-free calls (c3_demux_host) report here
 
+// POA scoring k_poa's 16-bit cells hold exactly or hand to the 32-bit pass (DESIGN.md 4.3 derives every bound from the constants
+// of k_poa.hip).  Pure arithmetic on the configuration: checked before a device is looked for.
+static int check_poa_scoring(const c3_config* cfg) {
+  const struct { const char* name; int v, lo, hi; } f[6] = {
+    {"poa_match", cfg->poa_match, 1, 64}, {"poa_mismatch", cfg->poa_mismatch, 0, 64},
+    {"poa_o1", cfg->poa_o1, 0, 64}, {"poa_e1", cfg->poa_e1, 0, 16}, {"poa_o2", cfg->poa_o2, 0, 64}, {"poa_e2", cfg->poa_e2, 0, 16}};
+  for (const auto& x : f) {
+    if (x.v < x.lo || x.v > x.hi) {
+      char buf[160];
+      snprintf(buf, sizeof buf, "%s = %d: must be %d..%d (the 16-bit cells of k_poa and their guard are exact in that range only)", x.name, x.v, x.lo, x.hi);
+      return host_fail(C3_E_ARG, buf);
+    }
+  }
+  return C3_E_OK;
+}
+
 extern "C" int c3_create(const c3_config* cfg, c3_handle** out) {
   if (!cfg || !out) return C3_E_ARG;
   *out = nullptr;
+  if (int rc = check_poa_scoring(cfg)) return rc;
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev <= 0) return host_fail(C3_E_NO_DEVICE, "no HIP device: the c3poa HIP backend has no CPU fallback");

@@ -49,7 +49,12 @@ class _MsaResult:
 
 
 class msa_aligner:
-    """pyabpoa.msa_aligner look-alike (only the parameters the reference sets are exposed)"""
+    """pyabpoa.msa_aligner look-alike (only the parameters the reference sets are exposed).
+
+    The defaults are pyabpoa's (match = 2); the reference passes match = 5.  Admitted scorings (c3_create refuses the rest with
+    C3_E_ARG, a C3Error here; include/c3poa.h): match 1..64, mismatch 0..64, gap_open1 and gap_open2 0..64,
+    gap_ext1 and gap_ext2 0..16, all given as non-negative numbers, no order required between the two gap pieces.  Inside these
+    ranges the MSA and the consensus equal the 32-bit computation of the same recurrences (tests/test_gpu_poa_scoring.py)."""
 
     def __init__(self, match=2, mismatch=4, gap_open1=4, gap_ext1=2, gap_open2=24, gap_ext2=1, extra_b=10, extra_f=0.01):
         self.cfg = dict(poa_match=match, poa_mismatch=mismatch, poa_o1=gap_open1, poa_e1=gap_ext1, poa_o2=gap_open2,

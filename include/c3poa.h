@@ -52,7 +52,15 @@ typedef struct {
   int sg_iters, sg_window, sg_order;            /* call_peaks(scores, d, 3, 41, 2): C3POa.py:111,124 */
   int mdistcutoff;                              /* -d: C3POa.py:45 */
   int poa_match, poa_mismatch;                  /* poa.msa_aligner(match=5): determine_consensus.py:30 */
-  int poa_o1, poa_e1, poa_o2, poa_e2;           /* abPOA defaults 4,2,24,1 */
+  int poa_o1, poa_e1, poa_o2, poa_e2;           /* abPOA defaults 4,2,24,1.  All six POA scores are penalties / rewards given as
+                                                   non-negative numbers.  Admitted: poa_match 1..64, poa_mismatch 0..64,
+                                                   poa_o1 and poa_o2 0..64, poa_e1 and poa_e2 0..16, no order between the two gap
+                                                   pieces; anything else makes c3_create fail with C3_E_ARG (the message names the
+                                                   field and its bounds).  Inside these ranges the result is the 32-bit result:
+                                                   the 16-bit cells of k_poa hold every value or hand the read to the 32-bit
+                                                   pass (DESIGN.md 4.3 derives the bounds).  That pass carries score * 512 in
+                                                   32 bits: alignment scores must stay inside (-524288, 4194304), which is
+                                                   poa_match * subread length < 4194304 at the top (65535 bases at match 64) */
   int poa_band_b; double poa_band_f;            /* abPOA defaults 10, 0.01 */
   int pol_match, pol_mismatch, pol_gap;         /* racon 3,-5,-4 */
   int pol_window, pol_q;                        /* racon window 500; -q 5: determine_consensus.py:92 */

@@ -46,6 +46,28 @@ def test_no_gpu_means_loud_failure_not_fallback():
     assert "no CPU fallback" in str(e.value)
 
 
+POA_RANGES = {"poa_match": (1, 64), "poa_mismatch": (0, 64), "poa_o1": (0, 64), "poa_e1": (0, 16), "poa_o2": (0, 64), "poa_e2": (0, 16)}
+
+
+@pytest.mark.parametrize("field", sorted(POA_RANGES))
+def test_create_refuses_poa_scoring_outside_the_exact_range(field):
+    """the ranges of DESIGN.md 4.3 / include/c3poa.h: the first value beyond either end of every POA scoring field is refused with
+    C3_E_ARG and a message naming the field and its bounds; the ends themselves are not (the scoring is checked before a device
+    is looked for, so this needs no GPU; that the ends compute what the oracle computes: tests/test_gpu_poa_scoring.py)"""
+    from c3poa_amd import _lib
+    lo, hi = POA_RANGES[field]
+    for v in (lo - 1, hi + 1, -1000, 1 << 20):
+        with pytest.raises(_lib.C3Error) as e:
+            _lib.Handle(**{field: v})
+        assert e.value.code == _lib.E_ARG, (field, v, str(e.value))
+        assert "%s = %d" % (field, v) in str(e.value) and "%d..%d" % (lo, hi) in str(e.value)
+    for v in (lo, hi):
+        try:
+            _lib.Handle(**{field: v}).close()
+        except _lib.C3Error as err:                       # without a GPU the accepted value gets as far as the device query
+            assert err.code != _lib.E_ARG and "no CPU fallback" in str(err), (field, v, str(err))
+
+
 def test_product_never_imports_the_oracle():
     """the oracle is test infrastructure: nothing under c3poa_amd/ or the CLI may reference it"""
     bad = []

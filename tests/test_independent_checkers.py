@@ -4,8 +4,8 @@ Nothing here is derived from oracle/*.c: the graph is rebuilt from the MSA ROWS 
 (column, base), one edge per pair of consecutive bases of a row), and
 
   * an unbanded, textbook sequence-to-DAG aligner with the two-piece ("convex") affine gap min(4+2k, 24+k), match +5,
-    mismatch -4 (pyabpoa defaults with match=5, bin/determine_consensus.py:30) gives the optimal global score of every
-    sequence against the graph of the sequences before it.  The oracle's adaptive-band DP can only lose against it; the
+    mismatch -4 (pyabpoa defaults with match=5, bin/determine_consensus.py:30; any other scoring through the `scoring`
+    argument) gives the optimal global score of every sequence against the graph of the sequences before it.  The oracle's adaptive-band DP can only lose against it; the
     test requires equality on well-behaved inputs and reports how often the band loses the optimum on ragged ones;
   * a naive heaviest-bundle walk over the rebuilt, weighted graph gives the consensus wherever no tie has to be broken;
   * the polish is checked through a property no alignment detail can fake: layers that agree outvote a wrong draft.
@@ -14,6 +14,7 @@ import os
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -22,7 +23,7 @@ from c3poa_amd import synth  # noqa: E402
 from oracle import oracle_py as O  # noqa: E402
 
 NEG = -10 ** 9
-MATCH, MISMATCH, O1, E1, O2, E2 = 5, -4, 4, 2, 24, 1
+DEFAULT_SCORING = (5, 4, 4, 2, 24, 1)         # (match, mismatch, o1, e1, o2, e2) as the configuration fields carry them: penalties positive
 
 
 class Dag:
@@ -57,15 +58,17 @@ class Dag:
         self.order = sorted(range(n), key=lambda v: self.col[v])      # columns are a topological order
 
 
-def gap(k):
-    return min(O1 + E1 * k, O2 + E2 * k)
+def gap(k, scoring=DEFAULT_SCORING):
+    _mt, _mm, o1, e1, o2, e2 = scoring
+    return min(o1 + e1 * k, o2 + e2 * k)
 
 
-def best_global_score(g, q):
+def best_global_score(g, q, scoring=DEFAULT_SCORING):
     """optimal global alignment score of q against any source->sink path of the DAG (no band), textbook recurrences"""
+    MATCH, MISMATCH, O1, E1, O2, E2 = scoring[0], -scoring[1], scoring[2], scoring[3], scoring[4], scoring[5]
     Q = len(q)
     qa = np.frombuffer(q.encode(), dtype=np.uint8)
-    srcH = np.array([0] + [-gap(k) for k in range(1, Q + 1)], dtype=np.int64)
+    srcH = np.array([0] + [-gap(k, scoring) for k in range(1, Q + 1)], dtype=np.int64)
     srcN = np.full(Q + 1, NEG, dtype=np.int64)
     H, EA, EB = {}, {}, {}
     for v in g.order:
@@ -98,15 +101,16 @@ def _mut(rng, s, **kw):
     return synth._mutate(rng, np.frombuffer(s.encode(), dtype=np.uint8), **kw)[0].decode()
 
 
-def _scores_vs_bruteforce(seqs):
-    _c, rows, _cells = O.poa_msa(seqs, out_cons=False, out_msa=True)
+def _scores_vs_bruteforce(seqs, scoring=DEFAULT_SCORING):
+    P = O.default_params(**dict(zip(("poa_match", "poa_mismatch", "poa_o1", "poa_e1", "poa_o2", "poa_e2"), scoring)))
+    _c, rows, _cells = O.poa_msa(seqs, out_cons=False, out_msa=True, params=P)
     got = O.poa_last_scores()
     assert len(got) == len(seqs) - 1
     for r, s in zip(rows, seqs):
         assert r.replace("-", "") == s
     out = []
     for k in range(1, len(seqs)):
-        out.append((got[k - 1], best_global_score(Dag(rows[:k]), seqs[k])))
+        out.append((got[k - 1], best_global_score(Dag(rows[:k]), seqs[k], scoring)))
     return out
 
 
@@ -122,6 +126,62 @@ def test_banded_graph_alignment_is_optimal_for_3_to_6_sequences():
             assert got == opt, (n, got, opt)
             checked += 1
     assert checked == 2 + 3 + 4 + 5
+
+
+def _three_to_six_copies():
+    """the inputs of test_banded_graph_alignment_is_optimal_for_3_to_6_sequences (same seed, same draws)"""
+    rng = np.random.default_rng(101)
+    out = []
+    for n in (3, 4, 5, 6):
+        truth = "".join("ACGT"[i] for i in rng.integers(0, 4, 140))
+        out.append([_mut(rng, truth) for _ in range(n)])
+    return out
+
+
+# the scorings the GPU parity tests of k_poa's non-default instances run (tests/test_gpu_poa_scoring.py): the oracle is a sound
+# reference there only if it still finds the unbanded optimum away from the default
+SCORINGS = [(5, 4, 4, 2, 24, 1), (2, 4, 4, 2, 24, 1), (1, 1, 1, 1, 1, 1), (3, 5, 6, 3, 30, 1), (10, 9, 8, 4, 48, 2),
+            (5, 4, 4, 2, 4, 2), (5, 4, 0, 3, 0, 3), (7, 2, 10, 1, 10, 1), (15, 15, 20, 5, 60, 2)]
+
+
+@pytest.mark.parametrize("scoring", SCORINGS, ids=lambda s: "-".join(map(str, s)))
+def test_banded_graph_alignment_is_optimal_under_other_scorings(scoring):
+    """the 14 alignments of the 3..6-copies experiment, scored with (match, mismatch, o1, e1, o2, e2): the oracle's banded score
+    equals the unbanded optimum of the parametrised brute force in all of them"""
+    checked = 0
+    for seqs in _three_to_six_copies():
+        for got, opt in _scores_vs_bruteforce(seqs, scoring):
+            assert got == opt, (scoring, len(seqs), got, opt)
+            checked += 1
+    assert checked == 14
+
+
+# the ends of the ranges c3_create admits (DESIGN.md 4.3): every field at its lower end (all ties: a path's score is its number of
+# matches), at its upper end, zero extensions (a gap costs its opening only), the two gap pieces in the other order
+RANGE_ENDS = [(1, 0, 0, 0, 0, 0), (64, 64, 64, 16, 64, 16), (5, 4, 4, 0, 24, 0), (3, 5, 30, 1, 6, 3)]
+
+
+@pytest.mark.parametrize("scoring", RANGE_ENDS, ids=lambda s: "-".join(map(str, s)))
+def test_banded_graph_alignment_is_optimal_at_the_ends_of_the_admitted_ranges(scoring):
+    n = 0
+    for seqs in _three_to_six_copies():
+        for got, opt in _scores_vs_bruteforce(seqs, scoring):
+            assert got == opt, (scoring, len(seqs), got, opt)
+            n += 1
+    assert n == 14
+
+
+def test_band_may_lose_under_a_mismatch_heavy_scoring_but_never_wins():
+    """(1, 9, 4, 2, 24, 1): a mismatch costs nine matches, alignments detour through gaps and the adaptive band loses the
+    optimum in 1 of the 14 alignments (measured); it never beats it"""
+    scoring = (1, 9, 4, 2, 24, 1)
+    lost = total = 0
+    for seqs in _three_to_six_copies():
+        for got, opt in _scores_vs_bruteforce(seqs, scoring):
+            assert got <= opt, (len(seqs), got, opt)
+            total += 1; lost += got < opt
+    print("band lost the optimum in %d of %d alignments under %s" % (lost, total, (scoring,)))
+    assert total == 14 and lost <= 1
 
 
 def test_band_never_beats_the_optimum_and_how_often_it_loses_on_ragged_input():
