@@ -6,6 +6,8 @@
 
 #define C3_NEG (-(1 << 28))    // out-of-band / unreachable score
 #define C3_NEG2 (-(1 << 30))   // "no left neighbour" of the horizontal-gap state
+#define C3_POL_MAX 8191        // |pol_match|, |pol_mismatch|, |pol_gap| admitted by c3_create
+#define C3_POL_KEY_RANGE (1LL << 28)   // bound of (4 * max|pol_*| + 3) * (2 * length + 4 * band) per batch: the distance of the polish rows' sentinels
 #define C3_MAX_SUB 250
 #define C3_SPLINT_MAX 512
 #define C3_JUMP_LEVELS 18   // binary-lifting levels of the consensus path (graphs up to 2^18 nodes)      // 64 lanes x 8 rows per lane in the conk kernel

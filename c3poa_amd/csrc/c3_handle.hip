@@ -132,10 +132,35 @@ static int check_poa_scoring(const c3_config* cfg) {
   return C3_E_OK;
 }
 
+// Polish scoring the 32-bit rows of k_window and k_prep hold exactly (DESIGN.md 4.6a derives the bound from the constants of
+// k_polish.hip; the 16-bit rows guard themselves per layer, the pieces and layers of a batch are checked against the scoring in
+// run_polish).  Every sign is admitted, one relation is not.  Pure arithmetic on the configuration: checked before a device is
+// looked for.
+static int check_pol_scoring(const c3_config* cfg) {
+  const struct { const char* name; int v; } f[3] = {{"pol_match", cfg->pol_match}, {"pol_mismatch", cfg->pol_mismatch}, {"pol_gap", cfg->pol_gap}};
+  for (const auto& x : f) {
+    if (x.v < -C3_POL_MAX || x.v > C3_POL_MAX) {
+      char buf[160];
+      snprintf(buf, sizeof buf, "%s = %d: must be %d..%d (the 32-bit cells of the polish rows and their sentinels are exact in that range only)", x.name, x.v, -C3_POL_MAX, C3_POL_MAX);
+      return host_fail(C3_E_ARG, buf);
+    }
+  }
+  // a matched pair has to beat two gaps: otherwise no layer aligns to the backbone, every layer adds all its bases as new nodes
+  // and no window fits the graph k_window has room for (3 * window + 40 per layer): every read would end as C3_ST_LIMIT
+  if (cfg->pol_match <= 2 * cfg->pol_gap) {
+    char buf[200];
+    snprintf(buf, sizeof buf, "pol_match = %d: must be above 2 * pol_gap = %d (a match that scores no more than two gaps makes every layer a chain of new nodes, beyond the window graph's capacity)",
+             cfg->pol_match, 2 * cfg->pol_gap);
+    return host_fail(C3_E_ARG, buf);
+  }
+  return C3_E_OK;
+}
+
 extern "C" int c3_create(const c3_config* cfg, c3_handle** out) {
   if (!cfg || !out) return C3_E_ARG;
   *out = nullptr;
   if (int rc = check_poa_scoring(cfg)) return rc;
+  if (int rc = check_pol_scoring(cfg)) return rc;
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev <= 0) return host_fail(C3_E_NO_DEVICE, "no HIP device: the c3poa HIP backend has no CPU fallback");

@@ -312,6 +312,16 @@ static int run_polish(c3_handle* h, float* ms_prep, float* ms_win, float* ms_st)
     max_ns = std::max(max_ns, h->sum[i].n_sub); max_q = std::max(max_q, h->sum[i].max_sub); max_dang = std::max(max_dang, h->sum[i].max_dang);
     wcap += (2 * h->sum[i].max_sub + WL - 1) / WL + 1;
   }
+  {
+    // the 32-bit keys of the extension rows and of the linear window rows against the longest piece and layer of this batch
+    // (DESIGN.md 4.6a): a cell is at most 2 * length + band steps of at most `kstep` from the origin, and every valid key has
+    // to stay 2^28 above the rows' sentinels.  The default scoring (kstep 23) passes up to 5.8 million bases.
+    const int pm = std::max({std::abs(h->cfg.pol_match), std::abs(h->cfg.pol_mismatch), std::abs(h->cfg.pol_gap)});
+    const long long kstep = 4LL * pm + 3, bw = 2LL * h->cfg.dang_band + 1;
+    if (kstep * (2LL * std::max(max_q, max_dang) + 4 * bw) >= C3_POL_KEY_RANGE)
+      return c3_fail(h, C3_E_LIMIT, "polish scoring times the longest subread or dangling piece of the batch leaves the 32-bit cells of the polish rows: "
+                                    "(4 * max|pol_*| + 3) * (2 * length + 4 * (2 * dang_band + 1)) must stay below 2^28");
+  }
   const int NLcap = max_ns + 2, NWcap = (2 * max_q + WL - 1) / WL + 1;
   // direction tags of one piece: one dword per lane and three rows, or two rows for a band that needs the wide rows (k_polish.hip:
   // ext_dir_bytes; 5 or 8 band offsets per lane; c3_create refuses a band beyond 64 * 8 offsets)

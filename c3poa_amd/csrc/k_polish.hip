@@ -1057,10 +1057,13 @@ __device__ int win_rows_dispatch(WCtx& c, const C3Params& P, const uint32_t* pk,
   // chain_bb != nullptr: the first layer of a window, the graph is the backbone chain and DP row r is node chain_v0 + r - 1
   const int need = (Q + 1 + 63) / 64;
   int cpl;
-  // 16-bit keys (score * 4 + type) of the register-blocked rows: |score| <= pm * max(R, Q), |score - g * j| <= (match + |g|) * Q,
-  // and the substitution scores live in signed bytes
+  // 16-bit keys (score * 4 + type) of the register-blocked rows: |score| <= pm * max(R, Q); the horizontal scan's score - g * j
+  // is at most (ups + |g|) * Q, ups = the larger substitution score (a column scores at most ups, gaps nothing, while g < 0) --
+  // |match| stands beside it for scorings without a positive score; and the substitution scores live in signed bytes
+  // 
   const int pm = max(max(abs(P.pol_match), abs(P.pol_mismatch)), abs(P.pol_gap));
-  const bool ok16 = !(4 * pm * (max(R, Q) + 4) >= 31000 || 4 * (abs(P.pol_match) + abs(P.pol_gap)) * (Q + 4) >= 31000 || pm > 30 || P.pol_gap >= 0);
+  const int ups = max(abs(P.pol_match), P.pol_mismatch);
+  const bool ok16 = !(4 * pm * (max(R, Q) + 4) >= 31000 || 4 * (ups + abs(P.pol_gap)) * (Q + 4) >= 31000 || pm > 30 || P.pol_gap >= 0);
   if (!ok16) cpl = 0;
 #ifdef C3_EXP_NOWIDE
   else if (need <= 2) cpl = 2; else if (need <= 4) cpl = 4; else cpl = 0;

@@ -62,7 +62,20 @@ typedef struct {
                                                    32 bits: alignment scores must stay inside (-524288, 4194304), which is
                                                    poa_match * subread length < 4194304 at the top (65535 bases at match 64) */
   int poa_band_b; double poa_band_f;            /* abPOA defaults 10, 0.01 */
-  int pol_match, pol_mismatch, pol_gap;         /* racon 3,-5,-4 */
+  int pol_match, pol_mismatch, pol_gap;         /* racon 3,-5,-4.  Scores as racon takes them (signed; a gap of zero or more, a
+                                                   match of zero or less and a mismatch above the match are admitted).  Admitted:
+                                                     pol_match    -8191..8191, and above 2 * pol_gap
+                                                     pol_mismatch -8191..8191
+                                                     pol_gap      -8191..8191 (so at most 4095, under pol_match 8191)
+                                                   anything else makes c3_create fail with C3_E_ARG (the message names the field
+                                                   and its bounds).  A match that scores no more than two gaps aligns no layer to
+                                                   its backbone: the window graphs outgrow their capacity and every read would
+                                                   end as C3_ST_LIMIT.  Inside the range the result is the exact one as long as
+                                                   (4 * max|pol_*| + 3) * (2 * length + 4 * (2 * dang_band + 1)) < 2^28 for the
+                                                   longest subread and dangling piece of a batch (5.8 million bases at the
+                                                   default scoring, 3 580 at 8191); c3_batch_run refuses a batch beyond that with
+                                                   C3_E_LIMIT.  The 16-bit rows of the window polish guard themselves per layer
+                                                   and hand what they cannot hold to the 32-bit rows. */
   int pol_window, pol_q;                        /* racon window 500; -q 5: determine_consensus.py:92 */
   int dang_band;                                /* half band of the dangling-piece extension, 128 */
   int slots_poa, slots_win;                     /* resident wave slots (0 = auto) */

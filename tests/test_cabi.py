@@ -68,6 +68,48 @@ def test_create_refuses_poa_scoring_outside_the_exact_range(field):
             assert err.code != _lib.E_ARG and "no CPU fallback" in str(err), (field, v, str(err))
 
 
+POL_MAX = 8191
+
+
+def _create(**cfg):
+    """None if c3_create gets past its argument checks (without a GPU: as far as the device query), else the C3_E_ARG error"""
+    from c3poa_amd import _lib
+    try:
+        _lib.Handle(**cfg).close()
+    except _lib.C3Error as err:
+        if err.code == _lib.E_ARG:
+            return err
+        assert "no CPU fallback" in str(err), (cfg, str(err))
+    return None
+
+
+@pytest.mark.parametrize("field", ["pol_gap", "pol_match", "pol_mismatch"])
+def test_create_refuses_polish_scoring_outside_the_exact_range(field):
+    """the range of DESIGN.md 4.6a / include/c3poa.h: the first value beyond either end of every polish scoring field is refused
+    with C3_E_ARG and a message naming the field and its bounds; the ends themselves are not (checked before a device is looked
+    for, so this needs no GPU; that the ends compute what the oracle computes: tests/test_gpu_pol_scoring.py).  The other two
+    fields are set so that the match stays above two gaps."""
+    other = {"pol_gap": dict(pol_match=POL_MAX), "pol_match": dict(pol_gap=-POL_MAX), "pol_mismatch": {}}[field]
+    for v in (-POL_MAX - 1, POL_MAX + 1, -1000000, 1000000, -(1 << 31), (1 << 31) - 1):
+        err = _create(**other, **{field: v})
+        assert err is not None, (field, v)
+        assert "%s = %d" % (field, v) in str(err) and "%d..%d" % (-POL_MAX, POL_MAX) in str(err), str(err)
+    lo, hi = {"pol_gap": (-POL_MAX, 4095), "pol_match": (-POL_MAX, POL_MAX), "pol_mismatch": (-POL_MAX, POL_MAX)}[field]
+    for v in (lo, hi, 0):
+        assert _create(**other, **{field: v}) is None, (field, v)
+
+
+@pytest.mark.parametrize("match,gap,ok", [(3, 1, True), (3, 2, False), (-7, -4, True), (-8, -4, False), (0, -1, True), (-2, -1, False),
+                                          (-14, -1, False), (3, 8191, False), (-8191, -4, False), (8191, 4095, True), (8191, 4096, False)])
+def test_create_refuses_a_match_that_does_not_beat_two_gaps(match, gap, ok):
+    """pol_match > 2 * pol_gap: with the other two fields at their defaults the last admitted values are
+    pol_gap = 1 and pol_match = -7"""
+    err = _create(pol_match=match, pol_gap=gap)
+    assert (err is None) == ok, (match, gap, str(err))
+    if err is not None:
+        assert "pol_match = %d" % match in str(err) and "2 * pol_gap = %d" % (2 * gap) in str(err), str(err)
+
+
 def test_product_never_imports_the_oracle():
     """the oracle is test infrastructure: nothing under c3poa_amd/ or the CLI may reference it"""
     bad = []

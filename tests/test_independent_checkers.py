@@ -267,7 +267,7 @@ def test_polish_layers_outvote_a_wrong_draft():
 # the brute-force optimum, its path must be a walk of the graph that re-scores to that optimum, and the two graphs must
 # stay identical layer after layer.
 
-PM, PX, PG = 3, -5, -4
+POL_DEFAULT = (3, -5, -4)             # polish match, mismatch, gap
 
 
 class WinGraph:
@@ -333,9 +333,10 @@ class WinGraph:
         assert len(out) == len(nodes)
         return out, succ
 
-    def best_score(self, nodes, query):
+    def best_score(self, nodes, query, scoring=POL_DEFAULT):
         """unbanded optimum of the global alignment of `query` against the induced sub-graph: the path may start at any node
         without predecessor inside and must end at a node without successor inside"""
+        PM, PX, PG = scoring
         order, succ = self.topo(nodes)
         nodes = set(nodes)
         Q = len(query)
@@ -353,8 +354,9 @@ class WinGraph:
             H[v] = np.maximum.accumulate(key - PG * j) + PG * j
         return max(int(H[v][Q]) for v in order if not succ[v])
 
-    def path_score(self, nodes, ops, query):
+    def path_score(self, nodes, ops, query, scoring=POL_DEFAULT):
         """re-score a reported path; checks that it is a walk of the sub-graph that consumes the whole query"""
+        PM, PX, PG = scoring
         nodes = set(nodes)
         score, prev, nq = 0, None, 0
         for node, q in ops:
@@ -373,11 +375,12 @@ class WinGraph:
         return score, prev
 
 
-def _check_windows(subs_quals, min_windows, front=None, tail=None):
+def _check_windows(subs_quals, min_windows, front=None, tail=None, scoring=POL_DEFAULT):
+    params = O.default_params(pol_match=scoring[0], pol_mismatch=scoring[1], pol_gap=scoring[2])
     O.win_capture(True)
     try:
         for subs, quals in subs_quals:
-            O.determine_consensus(subs, quals, front=front, tail=tail)
+            O.determine_consensus(subs, quals, front=front, tail=tail, params=params)
         als = O.win_captured()
     finally:
         O.win_capture(False)
@@ -392,9 +395,9 @@ def _check_windows(subs_quals, min_windows, front=None, tail=None):
         nodes = set(range(len(g.base))) if a["full"] else g.subgraph(a["begin"], a["end"])
         assert nodes == set(int(v) for v in np.nonzero(a["mask"])[0]), "sub-graph rule"
         q = a["query"]
-        opt = g.best_score(nodes, q)
+        opt = g.best_score(nodes, q, scoring)
         assert a["score"] == opt, (a["win"], a["layer"], a["score"], opt)
-        ps, last = g.path_score(nodes, [(int(x), int(y)) for x, y in a["ops"]], q)
+        ps, last = g.path_score(nodes, [(int(x), int(y)) for x, y in a["ops"]], q, scoring)
         assert ps == opt and last == a["end_node"]
         g.fuse([(int(x), int(y)) for x, y in a["ops"]], q)
         n_full += a["full"]; n_sub += not a["full"]
@@ -420,6 +423,34 @@ def test_window_dp_against_an_unbanded_brute_force():
     f2, s2 = _check_windows([(subs, quals)], 10, front=(fr, "5" * len(fr)), tail=(tl, "5" * len(tl)))
     assert n_full + f2 >= 12 and n_sub + s2 >= 10, (n_full, n_sub, f2, s2)
     assert n_full + n_sub + f2 + s2 >= 30
+
+
+# every polish scoring that tests/test_gpu_pol_scoring.py runs on the GPU: both sides of the 16-bit guard, the ends of the byte
+# range, gap >= 0, no positive substitution score, mismatch above match, the ends of the admitted range and the
+# scorings of the extension-row cases
+POL_SCORINGS = [(3, -15, -4), (3, -14, -4), (8, -8, -8), (14, -14, -1), (17, -17, -1), (1, -14, -14), (2, -3, -13), (30, -30, -30),
+                (31, -5, -4), (3, -31, -4), (3, -5, -31), (3, -5, 0), (3, -5, 1), (-1, -14, -1), (-14, -14, -1), (0, 0, -1), (3, 4, -4),
+                (1, -1, -1), (1, 14, -14), (1, 12, -12),
+                (8191, -5, -4), (-7, -5, -4), (-8191, -5, -4), (3, 8191, -4), (3, -8191, -4), (3, -5, 8191), (3, -5, -8191), (8191, -8191, 4095),
+                (2100, -3500, -2800), (8191, -8191, -8191), (-1, -1, -4), (3, 5, -4)]
+
+
+@pytest.mark.parametrize("scoring", POL_SCORINGS, ids=lambda s: "%d_%d_%d" % s)
+def test_window_dp_against_an_unbanded_brute_force_under_other_scorings(scoring):
+    """the oracle takes pol_match / pol_mismatch / pol_gap from its parameters; under each scoring its score is the unbanded
+    optimum of the independently rebuilt graph (64-bit), its path re-scores to it and spoa's sub-graph rule holds, on full-span
+    layers and on sub-graph layers (dangling pieces, a subread that misses a chunk)"""
+    rng = np.random.default_rng(78)
+    truth = "".join("ACGT"[i] for i in rng.integers(0, 4, 1080))
+    subs = [_mut(rng, truth) for _ in range(4)]
+    quals = ["".join(chr(33 + int(x)) for x in rng.integers(6, 30, len(s))) for s in subs]
+    n_full, n_sub = _check_windows([(subs, quals)], 6, scoring=scoring)
+    t2 = "".join("ACGT"[i] for i in rng.integers(0, 4, 560))
+    subs = [_mut(rng, t2), _mut(rng, t2[:200] + t2[260:]), _mut(rng, t2), _mut(rng, t2)]
+    quals = ["".join(chr(33 + int(x)) for x in rng.integers(6, 30, len(s))) for s in subs]
+    fr, tl = _mut(rng, t2[330:]), _mut(rng, t2[:240])
+    f2, s2 = _check_windows([(subs, quals)], 6, front=(fr, "5" * len(fr)), tail=(tl, "5" * len(tl)), scoring=scoring)
+    assert n_full + f2 >= 6 and n_sub + s2 >= 3, (n_full, n_sub, f2, s2)
 
 
 def test_window_rules_copy_and_tgs_trim():
