@@ -9,6 +9,9 @@
 #define C3_POL_MAX 8191        // |pol_match|, |pol_mismatch|, |pol_gap| admitted by c3_create
 #define C3_POL_KEY_RANGE (1LL << 28)   // bound of (4 * max|pol_*| + 3) * (2 * length + 4 * band) per batch: the distance of the polish rows' sentinels
 #define C3_MAX_SUB 250
+// pol_window admitted by c3_create: k_window's consensus keeps a node's predecessor in 16 bits with 0xffff for
+// "none", so a window graph may have at most 65 534 nodes: Ncap = 3 * pol_window + 40 * NLcap with NLcap <= C3_MAX_SUB + 4
+#define C3_POL_WINDOW_MAX ((65534 - 40 * (C3_MAX_SUB + 4)) / 3)
 #define C3_SPLINT_MAX 512
 #define C3_JUMP_LEVELS 18   // binary-lifting levels of the consensus path (graphs up to 2^18 nodes)      // 64 lanes x 8 rows per lane in the conk kernel
 

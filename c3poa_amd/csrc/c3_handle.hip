@@ -156,11 +156,29 @@ static int check_pol_scoring(const c3_config* cfg) {
   return C3_E_OK;
 }
 
+// Window length and extension band: run_polish divides by pol_window and sizes every capacity of the polish from
+// it; beyond C3_POL_WINDOW_MAX the node ids of a window graph leave the 16 bits k_window's consensus keeps them in.  A negative
+// dang_band is a band of negative width.  Pure arithmetic on the configuration: checked before a device is looked for.
+static int check_pol_window(const c3_config* cfg) {
+  char buf[200];
+  if (cfg->pol_window < 1 || cfg->pol_window > C3_POL_WINDOW_MAX) {
+    snprintf(buf, sizeof buf, "pol_window = %d: must be %d..%d (a window graph of 3 * pol_window + 40 nodes per layer has to stay below the 65535 node ids k_window's consensus holds)",
+             cfg->pol_window, 1, C3_POL_WINDOW_MAX);
+    return host_fail(C3_E_ARG, buf);
+  }
+  if (cfg->dang_band < 0) {
+    snprintf(buf, sizeof buf, "dang_band = %d: must be %d..%d (the half width of the extension band; 0 is the diagonal alone)", cfg->dang_band, 0, 255);
+    return host_fail(C3_E_ARG, buf);
+  }
+  return C3_E_OK;
+}
+
 extern "C" int c3_create(const c3_config* cfg, c3_handle** out) {
   if (!cfg || !out) return C3_E_ARG;
   *out = nullptr;
   if (int rc = check_poa_scoring(cfg)) return rc;
   if (int rc = check_pol_scoring(cfg)) return rc;
+  if (int rc = check_pol_window(cfg)) return rc;
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev <= 0) return host_fail(C3_E_NO_DEVICE, "no HIP device: the c3poa HIP backend has no CPU fallback");

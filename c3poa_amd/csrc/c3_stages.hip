@@ -369,13 +369,27 @@ static int run_polish(c3_handle* h, float* ms_prep, float* ms_win, float* ms_st)
     // a fifth of the worst case; a window with a layer beyond that is queued on the device and redone by a SECOND launch with
     // worst-case scratch on a few slots (no host round trip: it reads the count from device memory).  40 GB -> 10 GB of scratch
     // at cfg2 / cfg5 on 256 CUs: that much less to allocate and to touch for the first time in a fresh process.
-    const long long hcap_full = (long long)(Ncap + 1) * 64 * 12;
+    // (the worst case's columns: a layer of one window and a half of bases in one window, 12 groups of 64 at the default 500 --
+    // at a fixed 12 groups a window of thousands of bases had rows, but no columns, for its own layers: DESIGN.md 4.6b)
+    const long long hcap_full = (long long)(Ncap + 1) * 64 * std::max(12, (WL + WL / 2 + 64) / 64);
     const int R_typ = std::min(Ncap, WL + WL / 4 + 30 * NLcap + 64);
     long long hcap = std::min(hcap_full, (long long)(R_typ + R_typ / 2 + 4) * 256);      // (a window in the second launch runs alone on an idle device, ~1.5 ms: sized so that a usual batch has none -- at + R_typ / 4 one cfg2 window in 400 000 took it)
     if (const char* e = getenv("C3_DEBUG_HCAP_DIV")) hcap = std::max(4096LL, hcap_full / std::max(1, atoi(e)) / 64 * 64);       // test hook: smaller first-launch scratch (more windows take the second launch)
     const WinLayout L = c3_win_layout(Ncap, K, hcap), L2 = c3_win_layout(Ncap, K, hcap_full);
     const int slots = auto_slots(h, h->cfg.slots_win, L.total, n_win, 20);
-    const int slots2 = hcap < hcap_full ? std::min(slots, 256) : 0;
+    // (the second launch's worst-case cells grow with the square of the window length: its slots stay within a twelfth of the
+    // device memory -- 256 slots need 1.7 GB at the default -- and, where that is fewer than 256, within half of what is free;
+    // a window length whose single slot does not fit is refused here with a text, not by an allocation failing further down --
+    // DESIGN.md 4.6b)
+    const size_t budget = h->mem_total ? h->mem_total / 3 : ((size_t)64 << 30), per2 = L2.H + L2.D;
+    size_t budget2 = budget / 4;
+    if (hcap < hcap_full && per2 * 256 > budget2) {
+      size_t fr = 0, tot = 0;
+      if (hipMemGetInfo(&fr, &tot) == hipSuccess) budget2 = std::min(budget2, fr / 2); else (void)hipGetLastError();
+    }
+    if (L.total > budget || (hcap < hcap_full && per2 > budget2))
+      return c3_fail(h, C3_E_NOMEM, "pol_window: the scratch of one window (DP cells for 3 * pol_window + 40 nodes per layer, 1.5 * pol_window columns) does not fit the device memory set aside for it");
+    const int slots2 = hcap < hcap_full ? (int)std::min<size_t>(std::min(slots, 256), budget2 / per2) : 0;
     const size_t S = (size_t)slots, S2 = (size_t)slots2;
     HIPCHK(h->s_win_i.ensure(L.ints * S + 64)); HIPCHK(h->s_win_nk.ensure(L.edges * S));
     HIPCHK(h->s_win_h.ensure(L.H * S)); HIPCHK(h->s_win_d.ensure(L.D * S + 256));

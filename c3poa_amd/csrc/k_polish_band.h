@@ -6,7 +6,7 @@
 //     c(r) = (bb(r) - begin + 1) * Q / (end - begin + 1),   bb(r) = highest backbone node among the rows <= r,
 // lane owns band offsets CB*lane .. CB*lane + CB - 1 (column = lo(r) + offset), and the band slides right as the rows go down.
 //
-// EXACTNESS (DESIGN.md 4.6b).  Cells outside the band count as -infinity, so the banded optimum S_b is the best score of the
+// EXACTNESS (DESIGN.md 4.6c).  Cells outside the band count as -infinity, so the banded optimum S_b is the best score of the
 // paths that stay inside.  While the rows run, a certificate bound is accumulated: an upper bound of the score of EVERY path
 // with a cell outside the band.  Such a path leaves the band for the first time at a band-edge cell X whose banded value
 // bounds its prefix, and the rest is bounded by the moves that are left (every remaining column scores at most `ups` = the

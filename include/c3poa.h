@@ -76,8 +76,15 @@ typedef struct {
                                                    default scoring, 3 580 at 8191); c3_batch_run refuses a batch beyond that with
                                                    C3_E_LIMIT.  The 16-bit rows of the window polish guard themselves per layer
                                                    and hand what they cannot hold to the 32-bit rows. */
-  int pol_window, pol_q;                        /* racon window 500; -q 5: determine_consensus.py:92 */
-  int dang_band;                                /* half band of the dangling-piece extension, 128 */
+  int pol_window, pol_q;                        /* racon window 500; -q 5: determine_consensus.py:92.  Admitted: pol_window
+                                                   1..18458; anything else makes c3_create fail with C3_E_ARG (the message names
+                                                   the field and its bounds).  Below 1 there is no window to cut; above 18458 a
+                                                   window graph (3 * pol_window + 40 nodes per layer) outgrows the 16-bit node ids
+                                                   of the window consensus.  The scratch of the polish grows with
+                                                   the square of the window length: a run whose worst-case window does not fit
+                                                   the device memory ends with C3_E_NOMEM. */
+  int dang_band;                                /* half band of the dangling-piece extension, 128.  Admitted: 0 (the diagonal
+                                                   alone) .. 255; below 0 c3_create fails with C3_E_ARG, above 255 with C3_E_LIMIT */
   int slots_poa, slots_win;                     /* resident wave slots (0 = auto) */
   int zero;                                     /* args.zero (C3POa.py:48-49): attempt the zero-repeat rescue (default 1) */
   int64_t zero_max_cells;                       /* zero-repeat rescue only for pieces with front * tail <= this (default 16777216;

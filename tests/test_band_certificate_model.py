@@ -1,4 +1,4 @@
-"""The exactness certificate of k_window's banded rows (DESIGN.md 4.6b), checked WITHOUT a GPU and without any kernel code:
+"""The exactness certificate of k_window's banded rows (DESIGN.md 4.6c), checked WITHOUT a GPU and without any kernel code:
 the oracle's capture hook hands over real window alignments (graph, layer, optimal path of the FULL matrix); a plain-Python
 restatement of the band rules (band width by graph inflation, band start from the backbone position, cells outside = -inf, the
 oracle's tie order) fills the band, evaluates the certificate bound exactly as specified and walks back.  Claim under test:

@@ -110,6 +110,35 @@ def test_create_refuses_a_match_that_does_not_beat_two_gaps(match, gap, ok):
         assert "pol_match = %d" % match in str(err) and "2 * pol_gap = %d" % (2 * gap) in str(err), str(err)
 
 
+POL_WINDOW_MAX = 18458
+
+
+def test_create_refuses_a_window_length_outside_the_exact_range():
+    """the range of DESIGN.md 4.6b / include/c3poa.h: pol_window 1 .. 18 458.  Below it run_polish would divide by zero or size
+    negative capacities, above it a window graph's node ids leave the 16 bits k_window's consensus keeps them in.  Refused with
+    C3_E_ARG and a message naming the field and its bounds, before a device is looked for; the ends themselves are not (that
+    they compute what the oracle computes: tests/test_gpu_pol_window.py)"""
+    assert POL_WINDOW_MAX == (65534 - 40 * (250 + 4)) // 3
+    for v in (0, POL_WINDOW_MAX + 1, -1, -500, 100000, -(1 << 31), (1 << 31) - 1):
+        err = _create(pol_window=v)
+        assert err is not None, v
+        assert "pol_window = %d" % v in str(err) and "%d..%d" % (1, POL_WINDOW_MAX) in str(err), str(err)
+    for v in (1, POL_WINDOW_MAX, 500):
+        assert _create(pol_window=v) is None, v
+
+
+def test_create_refuses_a_negative_extension_band():
+    """dang_band 0 is the diagonal alone (a band of one offset, which the kernel's rows and the oracle both define); a negative
+    half width is no band.  Refused with C3_E_ARG before a device is looked for (the upper end, 255, is a capacity of k_prep
+    and refused with C3_E_LIMIT: tests/test_gpu_prep_rows.py)"""
+    for v in (-1, -128, -(1 << 31)):
+        err = _create(dang_band=v)
+        assert err is not None, v
+        assert "dang_band = %d" % v in str(err) and "0..255" in str(err), str(err)
+    for v in (0, 1, 128, 255):
+        assert _create(dang_band=v) is None, v
+
+
 def test_product_never_imports_the_oracle():
     """the oracle is test infrastructure: nothing under c3poa_amd/ or the CLI may reference it"""
     bad = []

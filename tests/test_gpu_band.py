@@ -1,4 +1,4 @@
-"""k_window's banded rows (DESIGN.md 4.6b): the band is an optimisation with a proof obligation, never a change of result.
+"""k_window's banded rows (DESIGN.md 4.6c): the band is an optimisation with a proof obligation, never a change of result.
 The oracle always fills the full matrix; the HIP path must equal it
   * with the band and its certificate (default),
   * with the band switched off (the unbanded rows),

@@ -159,9 +159,9 @@ def test_rows_beyond_the_draft():
     assert n_front >= 2 and n_tail >= 2
 
 
-@pytest.mark.parametrize("band", [20, 159, 160, 255])
+@pytest.mark.parametrize("band", [0, 20, 159, 160, 255])
 def test_other_bands(band):
-    """20: static invalid cells from lane 8 on; 159: bw = 319, the widest band with 5 offsets per lane; 160: bw = 321, the first band
+    """0: the smallest band c3_create admits, the diagonal alone (bw = 1: one valid offset, in lane 0); 20: static invalid cells from lane 8 on; 159: bw = 319, the widest band with 5 offsets per lane; 160: bw = 321, the first band
     that takes the wide rows (8 offsets per lane, two rows per direction word); 255: bw = 511, the widest band the lanes hold"""
     recs = list(synth.generate("cfg1", n_reads=8))
     ores, _ = _check([(r[1], r[2]) for r in recs], [r[3] for r in recs], dang_band=band)

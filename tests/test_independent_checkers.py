@@ -375,8 +375,8 @@ class WinGraph:
         return score, prev
 
 
-def _check_windows(subs_quals, min_windows, front=None, tail=None, scoring=POL_DEFAULT):
-    params = O.default_params(pol_match=scoring[0], pol_mismatch=scoring[1], pol_gap=scoring[2])
+def _check_windows(subs_quals, min_windows, front=None, tail=None, scoring=POL_DEFAULT, window=500, shapes=None):
+    params = O.default_params(pol_match=scoring[0], pol_mismatch=scoring[1], pol_gap=scoring[2], pol_window=window)
     O.win_capture(True)
     try:
         for subs, quals in subs_quals:
@@ -401,6 +401,8 @@ def _check_windows(subs_quals, min_windows, front=None, tail=None, scoring=POL_D
         assert ps == opt and last == a["end_node"]
         g.fuse([(int(x), int(y)) for x, y in a["ops"]], q)
         n_full += a["full"]; n_sub += not a["full"]
+        if shapes is not None:
+            shapes.append((a["win"], a["blen"], a["n"], len(q)))
     assert n_full + n_sub >= min_windows
     return n_full, n_sub
 
@@ -451,6 +453,33 @@ def test_window_dp_against_an_unbanded_brute_force_under_other_scorings(scoring)
     fr, tl = _mut(rng, t2[330:]), _mut(rng, t2[:240])
     f2, s2 = _check_windows([(subs, quals)], 6, front=(fr, "5" * len(fr)), tail=(tl, "5" * len(tl)), scoring=scoring)
     assert n_full + f2 >= 6 and n_sub + s2 >= 3, (n_full, n_sub, f2, s2)
+
+
+@pytest.mark.parametrize("window,least", [(7, 700), (128, 40), (2000, 8)])
+def test_window_dp_against_an_unbanded_brute_force_at_other_window_lengths(window, least):
+    """three of the window lengths tests/test_gpu_pol_window.py runs on the GPU, on two reads (four subreads each; the second
+    with dangling pieces and a subread that misses a chunk): windows of 7 backbone bases whose layers are a handful of bases,
+    windows of 128, and one window per read.  The oracle's score is the unbanded optimum of the independently rebuilt graph,
+    its path re-scores to it and spoa's sub-graph rule holds"""
+    rng = np.random.default_rng(79)
+    truth = "".join("ACGT"[i] for i in rng.integers(0, 4, 1080))
+    subs = [_mut(rng, truth) for _ in range(4)]
+    quals = ["".join(chr(33 + int(x)) for x in rng.integers(6, 30, len(s))) for s in subs]
+    shapes = []
+    n_full, n_sub = _check_windows([(subs, quals)], least // 2, window=window, shapes=shapes)
+    t2 = "".join("ACGT"[i] for i in rng.integers(0, 4, 560))
+    subs = [_mut(rng, t2), _mut(rng, t2[:200] + t2[260:]), _mut(rng, t2), _mut(rng, t2)]
+    quals = ["".join(chr(33 + int(x)) for x in rng.integers(6, 30, len(s))) for s in subs]
+    fr, tl = _mut(rng, t2[330:]), _mut(rng, t2[:240])
+    f2, s2 = _check_windows([(subs, quals)], least // 4, front=(fr, "5" * len(fr)), tail=(tl, "5" * len(tl)), window=window, shapes=shapes)
+    assert n_full + n_sub + f2 + s2 >= least, (n_full, n_sub, f2, s2)
+    if window == 7:
+        assert max(b for _, b, _, _ in shapes) == 7 and n_full + f2 == 0
+        assert max(n for _, _, n, _ in shapes) <= 16 and max(q for _, _, _, q in shapes) <= 14
+    elif window == 128:
+        assert max(b for _, b, _, _ in shapes) == 128 and n_full + f2 == 0
+    else:                       # (the capture numbers the windows of each call from 0)
+        assert {w for w, _, _, _ in shapes} == {0} and max(n for _, _, n, _ in shapes) > 1200 and n_full + f2 >= 4
 
 
 def test_window_rules_copy_and_tgs_trim():

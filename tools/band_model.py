@@ -2,7 +2,7 @@
 
 The oracle's capture hook hands over every window alignment of a few synthetic reads (graph, mask, query, path).  For each one
 the script computes the full DP, where the optimal path runs relative to the band centre that k_window derives from the
-backbone position of a row, and whether the exactness certificate (DESIGN.md 4.6b) would accept the banded result for a
+backbone position of a row, and whether the exactness certificate (DESIGN.md 4.6c) would accept the banded result for a
 given band shape.  Usage: python tools/band_model.py cfg2 40 [wl wr]
 """
 import os
