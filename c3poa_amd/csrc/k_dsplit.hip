@@ -3,8 +3,8 @@
 // applies as well; this file sums the lengths and moves the bytes.  The records lie parsed on the device (names / name_off,
 // seqs / quals / off), krec[] lists the kept ones in input order and win[] holds k_demux's winners for them.
 //
-//   k_dsplit_ksum / _kscan / _kfin   krec[] and the kept count for a FASTQ text (k_fasta makes them itself): a one-column
-//       exclusive scan over the records in the k_fa_xsum / xscan / xfin shape.
+//   k_tx_xsum / k_tx_xscan / k_tx_xfin <DsKept>   krec[] and the kept count for a FASTQ text (k_fasta makes them itself): the
+//       one-column exclusive scan of k_text.h over the records.
 //   k_dsplit_key    one lane per kept record: its stream (c3_dsplit_stream) and its output length (c3_demux_rec_len).
 //   k_dsplit_tile   one workgroup per tile of 256 kept records: keys and lengths of the tile in LDS, every lane walks the lanes in
 //       front of it and adds the lengths of those with its own key (LDS broadcast reads) -> rank[]; the last record of each
@@ -13,46 +13,23 @@
 //       stream_off[s + 1]; neighbouring lanes read neighbouring words.  k_dsplit_offs (one workgroup) then turns the totals into
 //       stream_off[0 .. S].  A record's place is stream_off[s] + base[tile][s] + rank, which depends on nothing but the input.
 //   k_dsplit_emit   one wave per kept record in the shape of k_demux_emit: literals and index names by the first lanes, name,
-//       sequence and quality dword-wise (fq_wave_copy), the four waves of a workgroup together on a record above FQ_LONG bytes.
+//       sequence and quality dword-wise (tx_wave_copy), the four waves of a workgroup together on a record above TX_LONG bytes.
 //       A wave writes only inside [place, place + length).
 // Resources (hipcc -O3 gfx950, -Rpass-analysis=kernel-resource-usage): DESIGN.md 5.10.
 #include "k_text.h"
 #include "c3_dsplit.h"
 #include "c3_launch.h"
 
-static_assert(C3_DS_TILE == 64 * FQ_WAVES, "a placement tile is one workgroup of lanes");
+static_assert(C3_DS_TILE == 64 * TX_WAVES, "a placement tile is one workgroup of lanes");
 
-// ---- krec[] of a FASTQ text ----
-__device__ __forceinline__ long long ds_kept_term(const DsArgs& a, long long r) {
-  return (r < a.n_records && c3_dsplit_kept(a.off[r + 1] - a.off[r])) ? 1 : 0;
-}
-__global__ __launch_bounds__(256) void k_dsplit_ksum(DsArgs a) {
-  __shared__ long long lds[FQ_WAVES];
-  long long t;
-  (void)fq_block_excl(ds_kept_term(a, (long long)blockIdx.x * 256 + threadIdx.x), lds, &t);
-  if (threadIdx.x == 0) a.bsum[blockIdx.x] = t;
-}
-__global__ __launch_bounds__(256) void k_dsplit_kscan(DsArgs a, int nb) {
-  __shared__ long long lds[FQ_WAVES];
-  long long run = 0;
-  for (int i0 = 0; i0 < nb; i0 += 256) {
-    const int i = i0 + (int)threadIdx.x;
-    const long long v = i < nb ? a.bsum[i] : 0;
-    long long tot;
-    const long long ex = fq_block_excl(v, lds, &tot);
-    if (i < nb) a.bsum[i] = run + ex;
-    run += tot;
-  }
-  if (threadIdx.x == 0) *a.n_kept_out = run;
-}
-__global__ __launch_bounds__(256) void k_dsplit_kfin(DsArgs a) {
-  __shared__ long long lds[FQ_WAVES];
-  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long v = ds_kept_term(a, r);
-  long long t;
-  const long long ex = a.bsum[blockIdx.x] + fq_block_excl(v, lds, &t);
-  if (v) a.krec[ex] = (int32_t)r;
-}
+// ---- krec[] of a FASTQ text: the functor of the one-column scan (tx_xscan of k_text.h) ----
+struct DsKept {                                          // over the parsed records: which are kept, krec[] in order
+  DsArgs a;
+  __device__ long long n() const { return a.n_records; }
+  __device__ long long term(long long r) const { return c3_dsplit_kept(a.off[r + 1] - a.off[r]) ? 1 : 0; }
+  __device__ void put(long long r, long long ex) const { a.krec[ex] = (int32_t)r; }
+  __device__ void total(long long t) const { *a.n_kept_out = t; }
+};
 
 // ---- placement ----
 __global__ __launch_bounds__(256) void k_dsplit_key(DsArgs a) {
@@ -98,13 +75,13 @@ __global__ __launch_bounds__(256) void k_dsplit_cols(DsArgs a) {
 
 // stream_off[1 .. S] hold the stream totals: -> stream_off[0 .. S], the exclusive sums and the grand total
 __global__ __launch_bounds__(256) void k_dsplit_offs(DsArgs a) {
-  __shared__ long long lds[FQ_WAVES];
+  __shared__ long long lds[TX_WAVES];
   long long run = 0;
   for (int s0 = 0; s0 < a.S; s0 += 256) {
     const int s = s0 + (int)threadIdx.x;
     const long long v = s < a.S ? (long long)a.stream_off[s + 1] : 0;
     long long tot;
-    const long long ex = fq_block_excl(v, lds, &tot);
+    const long long ex = tx_block_excl(v, lds, &tot);
     if (s < a.S) a.stream_off[s + 1] = run + ex + v;      // (a lane rewrites only the word it read)
     run += tot;
   }
@@ -112,12 +89,6 @@ __global__ __launch_bounds__(256) void k_dsplit_offs(DsArgs a) {
 }
 
 // ---- the records ----
-// this wave's piece [b, e) of len bytes shared by `parts` waves, in whole 256-byte rows
-__device__ __forceinline__ void ds_piece(uint32_t len, int part, int parts, uint32_t* b, uint32_t* e) {
-  const uint32_t piece = (((len + parts - 1) / parts) + 255u) & ~255u;
-  *b = min(len, piece * (uint32_t)part); *e = min(len, *b + piece);
-}
-
 // output record of kept record i; part / parts: this wave's share of sequence and quality (part 0 also writes everything else)
 __device__ __forceinline__ void ds_emit_record(const DsArgs& a, long long i, int lane, int part, int parts) {
   const int32_t r = wave_first(a.krec[i]), wa = wave_first(a.win[2 * i]), wb = wave_first(a.win[2 * i + 1]), s = wave_first(a.key[i]);
@@ -128,7 +99,7 @@ __device__ __forceinline__ void ds_emit_record(const DsArgs& a, long long i, int
   uint8_t* body = o + 4u + nlen + al + bl;
   uint8_t* qbody = body + sl + 3u;
   if (part == 0) {
-    fq_wave_copy(o + 1, a.names + no, nlen, lane);
+    tx_wave_copy(o + 1, a.names + no, nlen, lane);
     for (uint32_t j = (uint32_t)lane; j < al; j += 64u) o[2u + nlen + j] = a.a_names[a.a_no[wa] + j];
     for (uint32_t j = (uint32_t)lane; j < bl; j += 64u) o[3u + nlen + al + j] = a.b_names[a.b_no[wb] + j];
     if (lane == 0) {
@@ -137,34 +108,29 @@ __device__ __forceinline__ void ds_emit_record(const DsArgs& a, long long i, int
     }
   }
   uint32_t pb = 0, pe = sl;
-  if (parts > 1) ds_piece(sl, part, parts, &pb, &pe);
-  fq_wave_copy(body + pb, a.seqs + so + pb, pe - pb, lane);
-  if (a.quals) fq_wave_copy(qbody + pb, a.quals + so + pb, pe - pb, lane);
+  if (parts > 1) tx_piece(sl, part, parts, &pb, &pe);
+  tx_wave_copy(body + pb, a.seqs + so + pb, pe - pb, lane);
+  if (a.quals) tx_wave_copy(qbody + pb, a.quals + so + pb, pe - pb, lane);
 }
 
-__global__ __launch_bounds__(64 * FQ_WAVES) void k_dsplit_emit(DsArgs a) {
+__global__ __launch_bounds__(64 * TX_WAVES) void k_dsplit_emit(DsArgs a) {
   const int lane = threadIdx.x & 63;
   const int wv = wave_first((int)(threadIdx.x >> 6));
-  const long long i0 = (long long)blockIdx.x * FQ_WAVES;
+  const long long i0 = (long long)blockIdx.x * TX_WAVES;
   {
     const long long i = i0 + wv;
-    if (i < a.n_kept) { const int32_t r = a.krec[i]; if (a.off[r + 1] - a.off[r] <= FQ_LONG) ds_emit_record(a, i, lane, 0, 1); }
+    if (i < a.n_kept) { const int32_t r = a.krec[i]; if (a.off[r + 1] - a.off[r] <= TX_LONG) ds_emit_record(a, i, lane, 0, 1); }
   }
-  for (int k = 0; k < FQ_WAVES; ++k) {                  // long records of the workgroup: a quarter of sequence and quality each
+  for (int k = 0; k < TX_WAVES; ++k) {                  // long records of the workgroup: a quarter of sequence and quality each
     const long long i = i0 + k;
     if (i >= a.n_kept) break;
     const int32_t r = a.krec[i];
-    if (a.off[r + 1] - a.off[r] > FQ_LONG) ds_emit_record(a, i, lane, wv, FQ_WAVES);
+    if (a.off[r + 1] - a.off[r] > TX_LONG) ds_emit_record(a, i, lane, wv, TX_WAVES);
   }
 }
 
 // bsum holds (n_records + 255) / 256 sums; *n_kept_out the count afterwards
-extern "C" void c3k_launch_dsplit_krec(const DsArgs* a, hipStream_t s) {
-  const int nb = (int)((a->n_records + 255) / 256);
-  if (nb) hipLaunchKernelGGL(k_dsplit_ksum, dim3(nb), dim3(256), 0, s, *a);
-  hipLaunchKernelGGL(k_dsplit_kscan, dim3(1), dim3(256), 0, s, *a, nb);
-  if (nb) hipLaunchKernelGGL(k_dsplit_kfin, dim3(nb), dim3(256), 0, s, *a);
-}
+extern "C" void c3k_launch_dsplit_krec(const DsArgs* a, hipStream_t s) { tx_xscan(DsKept{*a}, a->n_records, a->bsum, s); }
 // n_kept > 0, tiles = (n_kept + C3_DS_TILE - 1) / C3_DS_TILE, base[tiles][S] zeroed by the caller; stream_off[S + 1] afterwards
 extern "C" void c3k_launch_dsplit_place(const DsArgs* a, hipStream_t s) {
   hipLaunchKernelGGL(k_dsplit_key, dim3((unsigned)((a->n_kept + 255) / 256)), dim3(256), 0, s, *a);
@@ -174,5 +140,5 @@ extern "C" void c3k_launch_dsplit_place(const DsArgs* a, hipStream_t s) {
 }
 extern "C" void c3k_launch_dsplit_emit(const DsArgs* a, hipStream_t s) {
   if (a->n_kept <= 0) return;
-  hipLaunchKernelGGL(k_dsplit_emit, dim3((unsigned)((a->n_kept + FQ_WAVES - 1) / FQ_WAVES)), dim3(64 * FQ_WAVES), 0, s, *a);
+  hipLaunchKernelGGL(k_dsplit_emit, dim3((unsigned)((a->n_kept + TX_WAVES - 1) / TX_WAVES)), dim3(64 * TX_WAVES), 0, s, *a);
 }

@@ -12,38 +12,19 @@
 //       every workgroup again with its base, writing the arena offset of each read's bytes of each kind.  No atomics: the
 //       order of the records in a stream is the read order by construction.
 //   k_emit_write   the pass that moves every byte once: one wave per read, the four waves of a workgroup together on the
-//       body segments of a read above EM_LONG bases.  Header literals and decimals are written by the first few lanes; names
+//       body segments of a read above TX_LONG bases.  Header literals and decimals are written by the first few lanes; names
 //       and body segments (a subread's bases or qualities, a consensus, a QV run) go dword-wise from two aligned source
-//       dwords joined by v_alignbyte (k_fastq_gather's scheme).  A wave writes nothing outside its read's own ranges
+//       dwords joined by v_alignbyte (tx_wave_copy of k_text.h).  A wave writes nothing outside its read's own ranges
 //       [roff, roff + len) and reads no dword that does not hold a byte of the segment it copies.
 #include "c3_dev.h"
 #include "c3_args.h"
 #include "c3_emit.h"
 #include "c3_launch.h"
+#include "k_text.h"
 
-#define EM_WAVES 4
-#define EM_LONG 32768                 // read bases above which the workgroup shares the body segments
-
-__device__ __forceinline__ long long em_wave_incl(long long v) {
-  const int lane = threadIdx.x & 63;
-  for (int d = 1; d < 64; d <<= 1) { const long long t = __shfl_up(v, d, 64); if (lane >= d) v += t; }
-  return v;
-}
 __device__ __forceinline__ long long em_wave_sum(long long v) {
   for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
   return v;
-}
-// exclusive scan over the 256 lanes of a workgroup; every lane calls it
-__device__ __forceinline__ long long em_block_excl(long long v, long long* lds, long long* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long long inc = em_wave_incl(v);
-  __syncthreads();                                       // (lds is reused from one call to the next)
-  if (lane == 63) lds[wv] = inc;
-  __syncthreads();
-  long long base = 0, tot = 0;
-  for (int k = 0; k < EM_WAVES; ++k) { const long long x = lds[k]; if (k < wv) base += x; tot += x; }
-  *total = tot;
-  return base + inc - v;
 }
 
 __device__ __forceinline__ int64_t em_clen(const EmitArgs& a, int i) {
@@ -65,9 +46,9 @@ __device__ __forceinline__ long long em_byte_sum(const uint8_t* q, int64_t L, in
   return em_wave_sum(acc);
 }
 
-__global__ __launch_bounds__(64 * EM_WAVES) void k_emit_len(EmitArgs a) {
+__global__ __launch_bounds__(64 * TX_WAVES) void k_emit_len(EmitArgs a) {
   const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * EM_WAVES + (int)(threadIdx.x >> 6);
+  const int i = blockIdx.x * TX_WAVES + (int)(threadIdx.x >> 6);
   if (i >= a.n) return;
   const c3_read_result& r = a.info[i];
   const int64_t so = a.off[i], L = a.off[i + 1] - so, nl = a.name_off[i + 1] - a.name_off[i], clen = em_clen(a, i);
@@ -121,7 +102,7 @@ __device__ __forceinline__ long long em_contrib(const EmRead& r, int c, int K, i
 // most K + 1 of them: 0.07 ms per 100 000 reads at one splint, linear in the splint count (193 passes at 64 splints), and not
 // measured at more than one splint.  A read-major pass over the splints a workgroup actually holds would remove the factor.
 __global__ __launch_bounds__(256) void k_emit_rsum(EmitArgs a) {
-  __shared__ long long lds[EM_WAVES][C3_EMIT_MAX_COLS];
+  __shared__ long long lds[TX_WAVES][C3_EMIT_MAX_COLS];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, SK = a.n_splints * a.K, SC = SK + 1;
   const EmRead r = em_load(a, blockIdx.x * 256 + (int)threadIdx.x);
   for (int c = 0; c < SC; ++c) {
@@ -131,14 +112,14 @@ __global__ __launch_bounds__(256) void k_emit_rsum(EmitArgs a) {
   __syncthreads();
   for (int c = (int)threadIdx.x; c < SC; c += 256) {
     long long t = 0;
-    for (int k = 0; k < EM_WAVES; ++k) t += lds[k][c];
+    for (int k = 0; k < TX_WAVES; ++k) t += lds[k][c];
     a.bsum[(size_t)blockIdx.x * SC + c] = t;
   }
 }
 
 // bsum[nb][S * K + 1] -> exclusive prefix sums per column, in place; stream_off[S * K + 1] and the record count
 __global__ __launch_bounds__(256) void k_emit_rscan(EmitArgs a, int nb) {
-  __shared__ long long lds[EM_WAVES];
+  __shared__ long long lds[TX_WAVES];
   __shared__ long long tot[C3_EMIT_MAX_COLS];
   const int SK = a.n_splints * a.K, SC = SK + 1;
   for (int c = 0; c < SC; ++c) {
@@ -147,7 +128,7 @@ __global__ __launch_bounds__(256) void k_emit_rscan(EmitArgs a, int nb) {
       const int i = i0 + (int)threadIdx.x;
       const long long v = i < nb ? a.bsum[(size_t)i * SC + c] : 0;
       long long t;
-      const long long ex = em_block_excl(v, lds, &t);
+      const long long ex = tx_block_excl(v, lds, &t);
       if (i < nb) a.bsum[(size_t)i * SC + c] = run + ex;
       run += t;
     }
@@ -163,14 +144,14 @@ __global__ __launch_bounds__(256) void k_emit_rscan(EmitArgs a, int nb) {
 }
 
 __global__ __launch_bounds__(256) void k_emit_rfin(EmitArgs a) {
-  __shared__ long long lds[EM_WAVES][C3_EMIT_MAX_COLS];
+  __shared__ long long lds[TX_WAVES][C3_EMIT_MAX_COLS];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, SK = a.n_splints * a.K, SC = SK + 1;
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
   const EmRead r = em_load(a, i);
   long long e0 = 0, e1 = 0, e2 = 0;
   for (int c = 0; c < SK; ++c) {
     const long long v = em_contrib(r, c, a.K, SK);
-    const long long inc = em_wave_incl(v);
+    const long long inc = tx_wave_incl(v);
     if (lane == 63) lds[wv][c] = inc;
     if (r.s >= 0 && c / a.K == r.s) { const int k = c % a.K; const long long ex = inc - v; if (k == 0) e0 = ex; else if (k == 1) e1 = ex; else e2 = ex; }
   }
@@ -189,28 +170,11 @@ __global__ __launch_bounds__(256) void k_emit_rfin(EmitArgs a) {
   }
 }
 
-// dst[0..len) = src[0..len) by the 64 lanes of a wave, any alignment on either side (po_copy_fwd of k_post.hip)
-__device__ __forceinline__ void em_copy(uint8_t* dst, const uint8_t* src, uint32_t len, int lane) {
-  const uint32_t head = min(len, (uint32_t)((4u - ((uintptr_t)dst & 3u)) & 3u));
-  if ((uint32_t)lane < head) dst[lane] = src[lane];
-  const uint32_t nd = (len - head) >> 2;
-  uint32_t* d4 = (uint32_t*)(dst + head);
-  const uint8_t* s = src + head;
-  const uint32_t sh = (uint32_t)((uintptr_t)s & 3u);
-  const uint32_t* sa = (const uint32_t*)(s - sh);
-  if (sh == 0) { for (uint32_t k = (uint32_t)lane; k < nd; k += 64u) d4[k] = sa[k]; }
-  else         { for (uint32_t k = (uint32_t)lane; k < nd; k += 64u) d4[k] = __builtin_amdgcn_alignbyte(sa[k + 1], sa[k], sh); }   // sa[k + 1] holds byte s + 4k + 3 at least
-  const uint32_t done = head + 4u * nd, tail = len - done;
-  if ((uint32_t)lane < tail) dst[done + lane] = src[done + lane];
-}
 // a body segment: the whole of it (parts == 1) or this wave's share in whole 256-byte rows
 __device__ __forceinline__ void em_body(uint8_t* dst, const uint8_t* src, uint32_t len, int lane, int part, int parts) {
   uint32_t b = 0, e = len;
-  if (parts > 1) {
-    const uint32_t piece = (((len + parts - 1) / parts) + 255u) & ~255u;
-    b = min(len, piece * (uint32_t)part); e = min(len, b + piece);
-  }
-  em_copy(dst + b, src + b, e - b, lane);
+  if (parts > 1) tx_piece(len, part, parts, &b, &e);
+  tx_wave_copy(dst + b, src + b, e - b, lane);
 }
 
 // the records of read i by one wave; part / parts: this wave's share of the body segments of a long read (part 0 also
@@ -234,7 +198,7 @@ __device__ __forceinline__ void em_write_read(const EmitArgs& a, int i, int lane
     const int dn = c3_emit_dec_len(idx);
     if (part == 0) {
       if (lane == 0) out[0] = '@';
-      em_copy(out + 1, name, nl, lane);
+      tx_wave_copy(out + 1, name, nl, lane);
       uint8_t* t = out + 1 + nl;                                       // _<idx>\n
       if (lane == 0) t[0] = '_';
       else if (lane <= dn) t[lane] = (uint8_t)c3_emit_dec_char(idx, lane - 1);
@@ -255,7 +219,7 @@ __device__ __forceinline__ void em_write_read(const EmitArgs& a, int i, int lane
     out = a.arena + roff[kind];
     if (part == 0) {
       if (lane == 0) out[0] = kind == C3_EMIT_CONS_FA ? '>' : '@';
-      em_copy(out + 1, name, nl, lane);
+      tx_wave_copy(out + 1, name, nl, lane);
       if (lane < ht) out[1 + nl + lane] = (uint8_t)c3_emit_head_tail_char(lane, a.head[i].aq, h.aql, L, d.ns, clen);
     }
     uint8_t* body = out + 1 + nl + ht;
@@ -268,24 +232,24 @@ __device__ __forceinline__ void em_write_read(const EmitArgs& a, int i, int lane
   }
 }
 
-__global__ __launch_bounds__(64 * EM_WAVES) void k_emit_write(EmitArgs a) {
+__global__ __launch_bounds__(64 * TX_WAVES) void k_emit_write(EmitArgs a) {
   const int lane = threadIdx.x & 63;
   const int wv = wave_first((int)(threadIdx.x >> 6));
-  const int i0 = blockIdx.x * EM_WAVES;
+  const int i0 = blockIdx.x * TX_WAVES;
   {
     const int i = i0 + wv;
-    if (i < a.n && a.off[i + 1] - a.off[i] <= EM_LONG) em_write_read(a, i, lane, 0, 1);
+    if (i < a.n && a.off[i + 1] - a.off[i] <= TX_LONG) em_write_read(a, i, lane, 0, 1);
   }
-  for (int k = 0; k < EM_WAVES; ++k) {                   // long reads of the workgroup: a quarter of every body segment each
+  for (int k = 0; k < TX_WAVES; ++k) {                   // long reads of the workgroup: a quarter of every body segment each
     const int i = i0 + k;
     if (i >= a.n) break;
-    if (a.off[i + 1] - a.off[i] <= EM_LONG) continue;
-    em_write_read(a, i, lane, wv, EM_WAVES);
+    if (a.off[i + 1] - a.off[i] <= TX_LONG) continue;
+    em_write_read(a, i, lane, wv, TX_WAVES);
   }
 }
 
 extern "C" void c3k_launch_emit_len(const EmitArgs* a, hipStream_t s) {
-  if (a->n > 0) hipLaunchKernelGGL(k_emit_len, dim3((a->n + EM_WAVES - 1) / EM_WAVES), dim3(64 * EM_WAVES), 0, s, *a);
+  if (a->n > 0) hipLaunchKernelGGL(k_emit_len, dim3((a->n + TX_WAVES - 1) / TX_WAVES), dim3(64 * TX_WAVES), 0, s, *a);
 }
 // bsum holds (S * K + 1) * ((n + 255) / 256) sums; stream_off S * K + 2 entries (the last = records)
 extern "C" void c3k_launch_emit_scan(const EmitArgs* a, hipStream_t s) {
@@ -295,5 +259,5 @@ extern "C" void c3k_launch_emit_scan(const EmitArgs* a, hipStream_t s) {
   if (nb) hipLaunchKernelGGL(k_emit_rfin, dim3(nb), dim3(256), 0, s, *a);
 }
 extern "C" void c3k_launch_emit_write(const EmitArgs* a, hipStream_t s) {
-  if (a->n > 0) hipLaunchKernelGGL(k_emit_write, dim3((a->n + EM_WAVES - 1) / EM_WAVES), dim3(64 * EM_WAVES), 0, s, *a);
+  if (a->n > 0) hipLaunchKernelGGL(k_emit_write, dim3((a->n + TX_WAVES - 1) / TX_WAVES), dim3(64 * TX_WAVES), 0, s, *a);
 }

@@ -13,10 +13,11 @@
 //       sequence bytes of a sequence line are its place in the sequence arena; the values at a header line are the record's
 //       number, name_off[] and off[].  The header lane also hashes the name.  k_fasta_settle (one lane) then states which records
 //       the text delivers (c3_fasta_verdict), consumed and the byte totals.
-//   k_fa_xsum / k_fa_xscan / k_fa_xfin   a one-column exclusive scan in the same shape, used twice by c3_demux_emit: over the
-//       records (kept = more than 300 sequence bytes -> krec[]) and over the kept records (output length -> roff[]).
+//   k_tx_xsum / k_tx_xscan / k_tx_xfin <FaKept>, <FaLen>   the one-column exclusive scan of k_text.h, used twice by
+//       c3_demux_emit: over the records (kept = more than 300 sequence bytes -> krec[]) and over the kept records (output
+//       length -> roff[]).
 //   k_fasta_gather   moves every name and sequence byte once: one wave per record, the four waves of a workgroup together on a
-//       record above FA_LONG bytes (a line above FA_LONG in quarters, shorter lines dealt round).  Dword path of k_fastq_gather.
+//       record above TX_LONG bytes (a line above TX_LONG in quarters, shorter lines dealt round).  Dword path of tx_wave_copy.
 //       A wave writes only inside its record's range of names / seqs.
 //   k_demux_heads   the first 300 bytes of every kept record into k_demux's slots, one wave per record.
 //   k_demux_emit    one wave per kept record as k_post_emit: literals and index names by the first lanes, name and sequence
@@ -24,12 +25,11 @@
 #include "c3_dev.h"
 #include "c3_fasta.h"
 #include "c3_launch.h"
+#include "k_text.h"
 
 #define FA_TILE 65536u
-#define FA_WAVES 4
-#define FA_SUB (FA_TILE / FA_WAVES)
+#define FA_SUB (FA_TILE / TX_WAVES)
 #define FA_STEP 1024u                 // 64 lanes x 16 bytes
-#define FA_LONG 32768                 // sequence bytes above which the workgroup shares a record
 
 // 0x80 in every byte of w that equals the byte repeated in c4 (exact: no borrow runs into the neighbouring byte)
 __device__ __forceinline__ uint32_t fa_eqmask(uint32_t w, uint32_t c4) {
@@ -63,7 +63,7 @@ __device__ __forceinline__ uint32_t fa_lane_mask(const uint8_t* buf, uint32_t p,
   return out;
 }
 
-__global__ __launch_bounds__(64 * FA_WAVES) void k_fasta_count(const uint8_t* buf, uint32_t hi, int32_t* cnt, C3FaHdr* hdr) {
+__global__ __launch_bounds__(64 * TX_WAVES) void k_fasta_count(const uint8_t* buf, uint32_t hi, int32_t* cnt, C3FaHdr* hdr) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t base = blockIdx.x * FA_TILE + (uint32_t)wv * FA_SUB;
   int c = 0;
@@ -76,44 +76,30 @@ __global__ __launch_bounds__(64 * FA_WAVES) void k_fasta_count(const uint8_t* bu
       if (high && first == UINT32_MAX) first = p + (uint32_t)__ffs((int)high) - 1u;
     }
   c = wave_scan_add(c);
-  if (lane == 63) cnt[blockIdx.x * FA_WAVES + wv] = c;
+  if (lane == 63) cnt[blockIdx.x * TX_WAVES + wv] = c;
   if (first != UINT32_MAX) atomicMin(&hdr->first_high, first);
-}
-
-// exclusive scan over the 256 lanes of a workgroup; every lane calls it
-template <class T> __device__ __forceinline__ T fa_block_excl(T v, T* lds, T* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  T inc = v;
-  for (int d = 1; d < 64; d <<= 1) { const T t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
-  __syncthreads();                                       // (lds is reused from one call to the next)
-  if (lane == 63) lds[wv] = inc;
-  __syncthreads();
-  T base = 0, tot = 0;
-  for (int k = 0; k < FA_WAVES; ++k) { const T x = lds[k]; if (k < wv) base += x; tot += x; }
-  *total = tot;
-  return base + inc - v;
 }
 
 // cnt[0..m) -> exclusive prefix sums, in place; the header gets the terminator count
 __global__ __launch_bounds__(256) void k_fasta_scan(int32_t* cnt, int m, C3FaHdr* hdr) {
-  __shared__ int lds[FA_WAVES];
+  __shared__ int lds[TX_WAVES];
   int run = 0;
   for (int i0 = 0; i0 < m; i0 += 256) {
     const int i = i0 + (int)threadIdx.x;
     const int v = i < m ? cnt[i] : 0;
     int tot;
-    const int ex = fa_block_excl(v, lds, &tot);
+    const int ex = tx_block_excl(v, lds, &tot);
     if (i < m) cnt[i] = run + ex;
     run += tot;
   }
   if (threadIdx.x == 0) hdr->n_term = run;
 }
 
-__global__ __launch_bounds__(64 * FA_WAVES) void k_fasta_lines(const uint8_t* buf, uint32_t hi, const int32_t* cnt, int32_t* nl) {
+__global__ __launch_bounds__(64 * TX_WAVES) void k_fasta_lines(const uint8_t* buf, uint32_t hi, const int32_t* cnt, int32_t* nl) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t base = blockIdx.x * FA_TILE + (uint32_t)wv * FA_SUB;
   if (base >= hi) return;
-  int at = cnt[blockIdx.x * FA_WAVES + wv];
+  int at = cnt[blockIdx.x * TX_WAVES + wv];
   for (uint32_t s = 0; s < FA_SUB; s += FA_STEP) {
     const uint32_t p = base + s + 16u * lane;
     uint32_t high;
@@ -142,26 +128,26 @@ __device__ __forceinline__ FaLine fa_line_terms(const FaArgs& a, int32_t k, int3
 }
 
 __global__ __launch_bounds__(256) void k_fasta_lsum(FaArgs a) {
-  __shared__ long long lds[FA_WAVES];
+  __shared__ long long lds[TX_WAVES];
   const int32_t k = blockIdx.x * 256 + (int)threadIdx.x;
   int32_t b = 0, se = 0;
   if (k <= a.T) { b = fa_begin(a, k); se = c3_fasta_strip_end(a.buf, b, fa_end(a, k)); a.lse[k] = se; }
   const FaLine t = fa_line_terms(a, k, b, se);
   long long th, tn, ts;
-  (void)fa_block_excl(t.h, lds, &th); (void)fa_block_excl(t.nb, lds, &tn); (void)fa_block_excl(t.sb, lds, &ts);
+  (void)tx_block_excl(t.h, lds, &th); (void)tx_block_excl(t.nb, lds, &tn); (void)tx_block_excl(t.sb, lds, &ts);
   if (threadIdx.x == 0) { a.bsum[3 * blockIdx.x] = th; a.bsum[3 * blockIdx.x + 1] = tn; a.bsum[3 * blockIdx.x + 2] = ts; }
 }
 
 // bsum[0 .. 3 * nb) -> exclusive prefix sums per stream, in place; the header count and the closing entries of the record arrays
 __global__ __launch_bounds__(256) void k_fasta_lscan(FaArgs a, int nb) {
-  __shared__ long long lds[FA_WAVES];
+  __shared__ long long lds[TX_WAVES];
   long long run[3] = {0, 0, 0};
   for (int i0 = 0; i0 < nb; i0 += 256) {
     const int i = i0 + (int)threadIdx.x;
     for (int c = 0; c < 3; ++c) {
       const long long v = i < nb ? a.bsum[3 * i + c] : 0;
       long long tot;
-      const long long ex = fa_block_excl(v, lds, &tot);
+      const long long ex = tx_block_excl(v, lds, &tot);
       if (i < nb) a.bsum[3 * i + c] = run[c] + ex;
       run[c] += tot;
     }
@@ -173,15 +159,15 @@ __global__ __launch_bounds__(256) void k_fasta_lscan(FaArgs a, int nb) {
 }
 
 __global__ __launch_bounds__(256) void k_fasta_lfin(FaArgs a) {
-  __shared__ long long lds[FA_WAVES];
+  __shared__ long long lds[TX_WAVES];
   const int32_t k = blockIdx.x * 256 + (int)threadIdx.x;
   int32_t b = 0, se = 0;
   if (k <= a.T) { b = fa_begin(a, k); se = a.lse[k]; }
   const FaLine ln = fa_line_terms(a, k, b, se);
   long long t;
-  const long long eh = a.bsum[3 * blockIdx.x] + fa_block_excl(ln.h, lds, &t);
-  const long long en = a.bsum[3 * blockIdx.x + 1] + fa_block_excl(ln.nb, lds, &t);
-  const long long es = a.bsum[3 * blockIdx.x + 2] + fa_block_excl(ln.sb, lds, &t);
+  const long long eh = a.bsum[3 * blockIdx.x] + tx_block_excl(ln.h, lds, &t);
+  const long long en = a.bsum[3 * blockIdx.x + 1] + tx_block_excl(ln.nb, lds, &t);
+  const long long es = a.bsum[3 * blockIdx.x + 2] + tx_block_excl(ln.sb, lds, &t);
   if (k > a.T) return;
   if (ln.kind == C3_FA_HEADER) {
     a.rec_line[eh] = k; a.name_off[eh] = en; a.off[eh] = es;
@@ -207,7 +193,7 @@ __global__ void k_fasta_settle(FaArgs a) {
   hd->n_kept = 0; hd->out_bytes = 0;
 }
 
-// ---- a one-column exclusive scan over items 0 .. F::n(): term(i), put(i, exclusive sum) for every item with a term, total(sum)
+// ---- the functors of the one-column scan (tx_xscan of k_text.h)
 struct FaKept {                                          // over the delivered records: which are kept, krec[] in order
   FaArgs a;
   __device__ long long n() const { return a.hdr->n_records; }
@@ -227,56 +213,6 @@ struct FaLen {                                           // over the kept record
   __device__ void total(long long t) const { a.hdr->out_bytes = t; }
 };
 
-template <class F> __global__ __launch_bounds__(256) void k_fa_xsum(F f, long long* bsum) {
-  __shared__ long long lds[FA_WAVES];
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  long long t;
-  (void)fa_block_excl(i < f.n() ? f.term(i) : 0ll, lds, &t);
-  if (threadIdx.x == 0) bsum[blockIdx.x] = t;
-}
-template <class F> __global__ __launch_bounds__(256) void k_fa_xscan(F f, long long* bsum, int nb) {
-  __shared__ long long lds[FA_WAVES];
-  long long run = 0;
-  for (int i0 = 0; i0 < nb; i0 += 256) {
-    const int i = i0 + (int)threadIdx.x;
-    const long long v = i < nb ? bsum[i] : 0;
-    long long tot;
-    const long long ex = fa_block_excl(v, lds, &tot);
-    if (i < nb) bsum[i] = run + ex;
-    run += tot;
-  }
-  if (threadIdx.x == 0) f.total(run);
-}
-template <class F> __global__ __launch_bounds__(256) void k_fa_xfin(F f, const long long* bsum) {
-  __shared__ long long lds[FA_WAVES];
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long v = i < f.n() ? f.term(i) : 0ll;
-  long long t;
-  const long long ex = bsum[blockIdx.x] + fa_block_excl(v, lds, &t);
-  if (v) f.put(i, ex);
-}
-
-// dst[0..len) = src[0..len) by the 64 lanes of a wave, any alignment on either side (fq_wave_copy of k_fastq.hip)
-__device__ __forceinline__ void fa_wave_copy(uint8_t* dst, const uint8_t* src, uint32_t len, int lane) {
-  const uint32_t head = min(len, (uint32_t)((4u - ((uintptr_t)dst & 3u)) & 3u));
-  if ((uint32_t)lane < head) dst[lane] = src[lane];
-  const uint32_t nd = (len - head) >> 2;
-  uint32_t* d4 = (uint32_t*)(dst + head);
-  const uint8_t* s = src + head;
-  const uint32_t sh = (uint32_t)((uintptr_t)s & 3u);
-  const uint32_t* sa = (const uint32_t*)(s - sh);
-  if (sh == 0) { for (uint32_t k = (uint32_t)lane; k < nd; k += 64u) d4[k] = sa[k]; }
-  else         { for (uint32_t k = (uint32_t)lane; k < nd; k += 64u) d4[k] = __builtin_amdgcn_alignbyte(sa[k + 1], sa[k], sh); }   // sa[k + 1] holds byte s + 4k + 3 at least
-  const uint32_t done = head + 4u * nd, tail = len - done;
-  if ((uint32_t)lane < tail) dst[done + lane] = src[done + lane];
-}
-
-// this wave's piece [b, e) of len bytes shared by `parts` waves, in whole 256-byte rows
-__device__ __forceinline__ void fa_piece(uint32_t len, int part, int parts, uint32_t* b, uint32_t* e) {
-  const uint32_t piece = (((len + parts - 1) / parts) + 255u) & ~255u;
-  *b = min(len, piece * (uint32_t)part); *e = min(len, *b + piece);
-}
-
 // the sequence lines of record r; part / parts: this wave's share (0 / 1: the wave has the record to itself)
 __device__ __forceinline__ void fa_gather_seq(const FaArgs& a, long long r, int lane, int part, int parts) {
   const int32_t k0 = wave_first(a.rec_line[r]) + 1, k1 = wave_first(a.rec_line[r + 1]);
@@ -286,40 +222,40 @@ __device__ __forceinline__ void fa_gather_seq(const FaArgs& a, long long r, int 
     if (se <= b) continue;
     const uint32_t len = (uint32_t)(se - b);
     uint8_t* dst = a.seqs + wave_first((int)a.ldst[k]);
-    if (parts > 1 && len > FA_LONG) {
+    if (parts > 1 && len > TX_LONG) {
       uint32_t pb, pe;
-      fa_piece(len, part, parts, &pb, &pe);
-      fa_wave_copy(dst + pb, a.buf + b + pb, pe - pb, lane);
+      tx_piece(len, part, parts, &pb, &pe);
+      tx_wave_copy(dst + pb, a.buf + b + pb, pe - pb, lane);
     } else if (parts == 1 || (turn++ % parts) == part) {
-      fa_wave_copy(dst, a.buf + b, len, lane);
+      tx_wave_copy(dst, a.buf + b, len, lane);
     }
   }
 }
 
-__global__ __launch_bounds__(64 * FA_WAVES) void k_fasta_gather(FaArgs a) {
+__global__ __launch_bounds__(64 * TX_WAVES) void k_fasta_gather(FaArgs a) {
   const int lane = threadIdx.x & 63;
   const int wv = wave_first((int)(threadIdx.x >> 6));
-  const long long i0 = (long long)blockIdx.x * FA_WAVES;
+  const long long i0 = (long long)blockIdx.x * TX_WAVES;
   {
     const long long r = i0 + wv;
     if (r < a.n_records) {
       const int64_t no = a.name_off[r];
-      fa_wave_copy(a.names + no, a.buf + fa_begin(a, a.rec_line[r]) + 1, (uint32_t)(a.name_off[r + 1] - no), lane);
-      if (a.off[r + 1] - a.off[r] <= FA_LONG) fa_gather_seq(a, r, lane, 0, 1);
+      tx_wave_copy(a.names + no, a.buf + fa_begin(a, a.rec_line[r]) + 1, (uint32_t)(a.name_off[r + 1] - no), lane);
+      if (a.off[r + 1] - a.off[r] <= TX_LONG) fa_gather_seq(a, r, lane, 0, 1);
     }
   }
-  for (int k = 0; k < FA_WAVES; ++k) {                  // long records of the workgroup
+  for (int k = 0; k < TX_WAVES; ++k) {                  // long records of the workgroup
     const long long r = i0 + k;
     if (r >= a.n_records) break;
-    if (a.off[r + 1] - a.off[r] > FA_LONG) fa_gather_seq(a, r, lane, wv, FA_WAVES);
+    if (a.off[r + 1] - a.off[r] > TX_LONG) fa_gather_seq(a, r, lane, wv, TX_WAVES);
   }
 }
 
-__global__ __launch_bounds__(64 * FA_WAVES) void k_demux_heads(FaArgs a) {
+__global__ __launch_bounds__(64 * TX_WAVES) void k_demux_heads(FaArgs a) {
   const int lane = threadIdx.x & 63;
-  const long long i = (long long)blockIdx.x * FA_WAVES + (threadIdx.x >> 6);
+  const long long i = (long long)blockIdx.x * TX_WAVES + (threadIdx.x >> 6);
   if (i >= a.n_kept) return;
-  fa_wave_copy(a.heads + (size_t)i * C3_DEMUX_HEAD, a.seqs + a.off[a.krec[i]], C3_DEMUX_HEAD, lane);     // kept: more than 300 bytes
+  tx_wave_copy(a.heads + (size_t)i * C3_DEMUX_HEAD, a.seqs + a.off[a.krec[i]], C3_DEMUX_HEAD, lane);     // kept: more than 300 bytes
 }
 
 // output record of kept record i; part / parts as in fa_gather_seq (part 0 also writes everything but the sequence)
@@ -331,67 +267,61 @@ __device__ __forceinline__ void fa_emit_record(const FaArgs& a, long long i, int
   uint8_t* o = a.out + a.roff[i];
   uint8_t* body = o + 4u + nlen + al + bl;
   if (part == 0) {
-    fa_wave_copy(o + 1, a.names + no, nlen, lane);
+    tx_wave_copy(o + 1, a.names + no, nlen, lane);
     for (uint32_t j = (uint32_t)lane; j < al; j += 64u) o[2u + nlen + j] = a.a_names[a.a_no[wa] + j];
     for (uint32_t j = (uint32_t)lane; j < bl; j += 64u) o[3u + nlen + al + j] = a.b_names[a.b_no[wb] + j];
     if (lane == 0) { o[0] = '>'; o[1u + nlen] = '|'; o[2u + nlen + al] = '_'; o[3u + nlen + al + bl] = '\n'; body[sl] = '\n'; }
   }
   uint32_t pb = 0, pe = sl;
-  if (parts > 1) fa_piece(sl, part, parts, &pb, &pe);
-  fa_wave_copy(body + pb, a.seqs + so + pb, pe - pb, lane);
+  if (parts > 1) tx_piece(sl, part, parts, &pb, &pe);
+  tx_wave_copy(body + pb, a.seqs + so + pb, pe - pb, lane);
 }
 
-__global__ __launch_bounds__(64 * FA_WAVES) void k_demux_emit(FaArgs a) {
+__global__ __launch_bounds__(64 * TX_WAVES) void k_demux_emit(FaArgs a) {
   const int lane = threadIdx.x & 63;
   const int wv = wave_first((int)(threadIdx.x >> 6));
-  const long long i0 = (long long)blockIdx.x * FA_WAVES;
+  const long long i0 = (long long)blockIdx.x * TX_WAVES;
   {
     const long long i = i0 + wv;
-    if (i < a.n_kept) { const int32_t r = a.krec[i]; if (a.off[r + 1] - a.off[r] <= FA_LONG) fa_emit_record(a, i, lane, 0, 1); }
+    if (i < a.n_kept) { const int32_t r = a.krec[i]; if (a.off[r + 1] - a.off[r] <= TX_LONG) fa_emit_record(a, i, lane, 0, 1); }
   }
-  for (int k = 0; k < FA_WAVES; ++k) {                  // long records of the workgroup: a quarter of the sequence each
+  for (int k = 0; k < TX_WAVES; ++k) {                  // long records of the workgroup: a quarter of the sequence each
     const long long i = i0 + k;
     if (i >= a.n_kept) break;
     const int32_t r = a.krec[i];
-    if (a.off[r + 1] - a.off[r] > FA_LONG) fa_emit_record(a, i, lane, wv, FA_WAVES);
+    if (a.off[r + 1] - a.off[r] > TX_LONG) fa_emit_record(a, i, lane, wv, TX_WAVES);
   }
 }
 
 static inline int fa_tiles(uint32_t hi) { return (int)(((uint64_t)hi + FA_TILE - 1) / FA_TILE); }
-template <class F> static void fa_xscan(const F& f, long long n_bound, long long* bsum, hipStream_t s) {
-  const int nb = (int)((n_bound + 255) / 256);
-  if (nb) hipLaunchKernelGGL(k_fa_xsum<F>, dim3(nb), dim3(256), 0, s, f, bsum);
-  hipLaunchKernelGGL(k_fa_xscan<F>, dim3(1), dim3(256), 0, s, f, bsum, nb);
-  if (nb) hipLaunchKernelGGL(k_fa_xfin<F>, dim3(nb), dim3(256), 0, s, f, (const long long*)bsum);
-}
 
 // hdr's first three words are preset to all ones by the caller; hi > 0
 extern "C" void c3k_launch_fasta_count(const FaArgs* a, hipStream_t s) {
   const int tiles = fa_tiles(a->hi);
-  hipLaunchKernelGGL(k_fasta_count, dim3(tiles), dim3(64 * FA_WAVES), 0, s, a->buf, a->hi, a->cnt, a->hdr);
-  hipLaunchKernelGGL(k_fasta_scan, dim3(1), dim3(256), 0, s, a->cnt, tiles * FA_WAVES, a->hdr);
+  hipLaunchKernelGGL(k_fasta_count, dim3(tiles), dim3(64 * TX_WAVES), 0, s, a->buf, a->hi, a->cnt, a->hdr);
+  hipLaunchKernelGGL(k_fasta_scan, dim3(1), dim3(256), 0, s, a->cnt, tiles * TX_WAVES, a->hdr);
 }
 // a->T terminators: lines 0 .. T; bsum holds 3 * ((T + 1 + 255) / 256) sums; with `kept`, krec[] and hdr->n_kept as well
 extern "C" void c3k_launch_fasta_records(const FaArgs* a, int kept, hipStream_t s) {
   const int nb = (a->T + 1 + 255) / 256;
-  hipLaunchKernelGGL(k_fasta_lines, dim3(fa_tiles(a->hi)), dim3(64 * FA_WAVES), 0, s, a->buf, a->hi, (const int32_t*)a->cnt, a->nl);
+  hipLaunchKernelGGL(k_fasta_lines, dim3(fa_tiles(a->hi)), dim3(64 * TX_WAVES), 0, s, a->buf, a->hi, (const int32_t*)a->cnt, a->nl);
   hipLaunchKernelGGL(k_fasta_lsum, dim3(nb), dim3(256), 0, s, *a);
   hipLaunchKernelGGL(k_fasta_lscan, dim3(1), dim3(256), 0, s, *a, nb);
   hipLaunchKernelGGL(k_fasta_lfin, dim3(nb), dim3(256), 0, s, *a);
   hipLaunchKernelGGL(k_fasta_settle, dim3(1), dim3(1), 0, s, *a);
-  if (kept) fa_xscan(FaKept{*a}, (long long)a->T + 1, a->bsum, s);      // at most one record per line
+  if (kept) tx_xscan(FaKept{*a}, (long long)a->T + 1, a->bsum, s);      // at most one record per line
 }
 extern "C" void c3k_launch_fasta_gather(const FaArgs* a, hipStream_t s) {
   if (a->n_records <= 0) return;
-  hipLaunchKernelGGL(k_fasta_gather, dim3((unsigned)((a->n_records + FA_WAVES - 1) / FA_WAVES)), dim3(64 * FA_WAVES), 0, s, *a);
+  hipLaunchKernelGGL(k_fasta_gather, dim3((unsigned)((a->n_records + TX_WAVES - 1) / TX_WAVES)), dim3(64 * TX_WAVES), 0, s, *a);
 }
 extern "C" void c3k_launch_demux_heads(const FaArgs* a, hipStream_t s) {
   if (a->n_kept <= 0) return;
-  hipLaunchKernelGGL(k_demux_heads, dim3((unsigned)((a->n_kept + FA_WAVES - 1) / FA_WAVES)), dim3(64 * FA_WAVES), 0, s, *a);
+  hipLaunchKernelGGL(k_demux_heads, dim3((unsigned)((a->n_kept + TX_WAVES - 1) / TX_WAVES)), dim3(64 * TX_WAVES), 0, s, *a);
 }
 // bsum holds (n_kept + 255) / 256 sums
-extern "C" void c3k_launch_demux_len(const FaArgs* a, hipStream_t s) { fa_xscan(FaLen{*a}, a->n_kept, a->bsum, s); }
+extern "C" void c3k_launch_demux_len(const FaArgs* a, hipStream_t s) { tx_xscan(FaLen{*a}, a->n_kept, a->bsum, s); }
 extern "C" void c3k_launch_demux_emit(const FaArgs* a, hipStream_t s) {
   if (a->n_kept <= 0) return;
-  hipLaunchKernelGGL(k_demux_emit, dim3((unsigned)((a->n_kept + FA_WAVES - 1) / FA_WAVES)), dim3(64 * FA_WAVES), 0, s, *a);
+  hipLaunchKernelGGL(k_demux_emit, dim3((unsigned)((a->n_kept + TX_WAVES - 1) / TX_WAVES)), dim3(64 * TX_WAVES), 0, s, *a);
 }

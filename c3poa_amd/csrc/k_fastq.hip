@@ -18,17 +18,17 @@
 //       front of the first bad one: per-workgroup sums, one small workgroup over those, then every workgroup again with its
 //       base, writing off[], name_off[] and the source positions of the kept records.
 //   k_fastq_gather   the pass that moves every byte once: one wave per kept record, the four waves of a workgroup together
-//       on a record above FQ_LONG bytes.  Source and destination sit at any byte: the destination is brought to a dword with
-//       byte stores, the interior is whole dwords from two aligned source dwords joined by v_alignbyte (as k_bgzf and
-//       k_inflate read their input), the end is byte stores.  Nothing outside a record's own destination range is written
-//       (other waves write its neighbours), nothing outside the dwords that hold text bytes is read.
+//       on a record above TX_LONG bytes.  Source and destination sit at any byte (tx_wave_copy of k_text.h): the destination
+//       is brought to a dword with byte stores, the interior is whole dwords from two aligned source dwords joined by
+//       v_alignbyte (as k_bgzf and k_inflate read their input), the end is byte stores.  Nothing outside a record's own
+//       destination range is written (other waves write its neighbours), nothing outside the dwords that hold text bytes is read.
 #include "c3_dev.h"
 #include "c3_fastq.h"
 #include "c3_launch.h"
 #include "k_text.h"
 
 #define FQ_TILE 65536u
-#define FQ_SUB (FQ_TILE / FQ_WAVES)
+#define FQ_SUB (FQ_TILE / TX_WAVES)
 #define FQ_STEP 1024u                 // 64 lanes x 16 bytes
 
 // 0x80 in every byte of w that is '\n' (exact: no borrow runs into the neighbouring byte)
@@ -57,25 +57,25 @@ __device__ __forceinline__ uint32_t fq_lane_mask(const uint8_t* buf, uint32_t p,
   return out;
 }
 
-__global__ __launch_bounds__(64 * FQ_WAVES) void k_fastq_count(const uint8_t* buf, uint32_t lo, uint32_t hi, int32_t* cnt) {
+__global__ __launch_bounds__(64 * TX_WAVES) void k_fastq_count(const uint8_t* buf, uint32_t lo, uint32_t hi, int32_t* cnt) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t base = blockIdx.x * FQ_TILE + (uint32_t)wv * FQ_SUB;
   int c = 0;
   if (base < hi)
     for (uint32_t s = 0; s < FQ_SUB; s += FQ_STEP) c += __popc(fq_lane_mask(buf, base + s + 16u * lane, lo, hi));
   c = wave_scan_add(c);
-  if (lane == 63) cnt[blockIdx.x * FQ_WAVES + wv] = c;
+  if (lane == 63) cnt[blockIdx.x * TX_WAVES + wv] = c;
 }
 
 // cnt[0..m) -> exclusive prefix sums, in place; the header gets the line counts and is made ready for k_fastq_records
 __global__ __launch_bounds__(256) void k_fastq_scan(int32_t* cnt, int m, const uint8_t* buf, uint32_t lo, uint32_t hi, int at_eof, C3FqHdr* hdr) {
-  __shared__ int lds[FQ_WAVES];
+  __shared__ int lds[TX_WAVES];
   int run = 0;
   for (int i0 = 0; i0 < m; i0 += 256) {
     const int i = i0 + (int)threadIdx.x;
     const int v = i < m ? cnt[i] : 0;
     int tot;
-    const int ex = fq_block_excl(v, lds, &tot);
+    const int ex = tx_block_excl(v, lds, &tot);
     if (i < m) cnt[i] = run + ex;
     run += tot;
   }
@@ -86,11 +86,11 @@ __global__ __launch_bounds__(256) void k_fastq_scan(int32_t* cnt, int m, const u
   }
 }
 
-__global__ __launch_bounds__(64 * FQ_WAVES) void k_fastq_lines(const uint8_t* buf, uint32_t lo, uint32_t hi, const int32_t* cnt, int32_t* nl) {
+__global__ __launch_bounds__(64 * TX_WAVES) void k_fastq_lines(const uint8_t* buf, uint32_t lo, uint32_t hi, const int32_t* cnt, int32_t* nl) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t base = blockIdx.x * FQ_TILE + (uint32_t)wv * FQ_SUB;
   if (base >= hi) return;
-  int at = cnt[blockIdx.x * FQ_WAVES + wv];
+  int at = cnt[blockIdx.x * TX_WAVES + wv];
   for (uint32_t s = 0; s < FQ_SUB; s += FQ_STEP) {
     const uint32_t p = base + s + 16u * lane;
     uint32_t m = fq_lane_mask(buf, p, lo, hi);
@@ -134,25 +134,25 @@ __device__ __forceinline__ void fq_rec_terms(int r, int n_rec, const int32_t* sl
 }
 
 __global__ __launch_bounds__(256) void k_fastq_rsum(const int32_t* slen, const int32_t* nlen, int n_full, int min_len, const C3FqHdr* hdr, long long* bsum) {
-  __shared__ long long lds[FQ_WAVES];
+  __shared__ long long lds[TX_WAVES];
   const int n_rec = min(hdr->first_bad, n_full);
   long long k, s, n, tk, ts, tn;
   fq_rec_terms(blockIdx.x * 256 + (int)threadIdx.x, n_rec, slen, nlen, min_len, &k, &s, &n);
-  (void)fq_block_excl(k, lds, &tk); (void)fq_block_excl(s, lds, &ts); (void)fq_block_excl(n, lds, &tn);
+  (void)tx_block_excl(k, lds, &tk); (void)tx_block_excl(s, lds, &ts); (void)tx_block_excl(n, lds, &tn);
   if (threadIdx.x == 0) { bsum[3 * blockIdx.x] = tk; bsum[3 * blockIdx.x + 1] = ts; bsum[3 * blockIdx.x + 2] = tn; }
 }
 
 // bsum[0..3 * nb) -> exclusive prefix sums per stream, in place; the header and the closing entries of off / name_off
 __global__ __launch_bounds__(256) void k_fastq_rscan(long long* bsum, int nb, const int32_t* nl, uint32_t lo, uint32_t hi, int L, int n_full,
                                                      C3FqHdr* hdr, int64_t* off, int64_t* name_off) {
-  __shared__ long long lds[FQ_WAVES];
+  __shared__ long long lds[TX_WAVES];
   long long run[3] = {0, 0, 0};
   for (int i0 = 0; i0 < nb; i0 += 256) {
     const int i = i0 + (int)threadIdx.x;
     for (int c = 0; c < 3; ++c) {
       const long long v = i < nb ? bsum[3 * i + c] : 0;
       long long tot;
-      const long long ex = fq_block_excl(v, lds, &tot);
+      const long long ex = tx_block_excl(v, lds, &tot);
       if (i < nb) bsum[3 * i + c] = run[c] + ex;
       run[c] += tot;
     }
@@ -171,12 +171,12 @@ __global__ __launch_bounds__(256) void k_fastq_rscan(long long* bsum, int nb, co
 
 __global__ __launch_bounds__(256) void k_fastq_rfin(const int32_t* slen, const int32_t* nlen, const int32_t* nl, uint32_t lo, int n_full, int min_len,
                                                     const C3FqHdr* hdr, const long long* bsum, int64_t* off, int64_t* name_off, int4* src) {
-  __shared__ long long lds[FQ_WAVES];
+  __shared__ long long lds[TX_WAVES];
   const int n_rec = min(hdr->first_bad, n_full);
   const int r = blockIdx.x * 256 + (int)threadIdx.x;
   long long k, s, n, t;
   fq_rec_terms(r, n_rec, slen, nlen, min_len, &k, &s, &n);
-  const long long ek = fq_block_excl(k, lds, &t), es = fq_block_excl(s, lds, &t), en = fq_block_excl(n, lds, &t);
+  const long long ek = tx_block_excl(k, lds, &t), es = tx_block_excl(s, lds, &t), en = tx_block_excl(n, lds, &t);
   if (!k) return;
   const long long i = bsum[3 * blockIdx.x] + ek;
   off[i] = bsum[3 * blockIdx.x + 1] + es;
@@ -185,47 +185,47 @@ __global__ __launch_bounds__(256) void k_fastq_rfin(const int32_t* slen, const i
   src[i] = make_int4(nl[4 * r] + 1, nl[4 * r + 2] + 1, b0 + 1, 0);        // sequence, quality, name
 }
 
-__global__ __launch_bounds__(64 * FQ_WAVES) void k_fastq_gather(const uint8_t* buf, const int4* src, const int64_t* off, const int64_t* name_off,
+__global__ __launch_bounds__(64 * TX_WAVES) void k_fastq_gather(const uint8_t* buf, const int4* src, const int64_t* off, const int64_t* name_off,
                                                                 long long n_kept, uint8_t* names, uint8_t* seqs, uint8_t* quals) {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const long long i0 = (long long)blockIdx.x * FQ_WAVES;
+  const long long i0 = (long long)blockIdx.x * TX_WAVES;
   {
     const long long i = i0 + wv;
     if (i < n_kept) {
       const int4 p = src[i];
       const int64_t no = name_off[i], so = off[i];
       const uint32_t nlen = (uint32_t)(name_off[i + 1] - no), sl = (uint32_t)(off[i + 1] - so);
-      fq_wave_copy(names + no, buf + p.z, nlen, lane);
-      if (seqs && sl <= FQ_LONG) {
-        fq_wave_copy(seqs + so, buf + p.x, sl, lane);
-        fq_wave_copy(quals + so, buf + p.y, sl, lane);
+      tx_wave_copy(names + no, buf + p.z, nlen, lane);
+      if (seqs && sl <= TX_LONG) {
+        tx_wave_copy(seqs + so, buf + p.x, sl, lane);
+        tx_wave_copy(quals + so, buf + p.y, sl, lane);
       }
     }
   }
   if (!seqs) return;
-  for (int k = 0; k < FQ_WAVES; ++k) {                  // long records of the workgroup: a quarter (in whole 256-byte rows) each
+  for (int k = 0; k < TX_WAVES; ++k) {                  // long records of the workgroup: a quarter (in whole 256-byte rows) each
     const long long i = i0 + k;
     if (i >= n_kept) break;
     const int64_t so = off[i];
     const uint32_t sl = (uint32_t)(off[i + 1] - so);
-    if (sl <= FQ_LONG) continue;
+    if (sl <= TX_LONG) continue;
     const int4 p = src[i];
-    const uint32_t piece = (((sl + FQ_WAVES - 1) / FQ_WAVES) + 255u) & ~255u;
-    const uint32_t b = min(sl, piece * (uint32_t)wv), e = min(sl, b + piece);
-    fq_wave_copy(seqs + so + b, buf + p.x + b, e - b, lane);
-    fq_wave_copy(quals + so + b, buf + p.y + b, e - b, lane);
+    uint32_t b, e;
+    tx_piece(sl, wv, TX_WAVES, &b, &e);
+    tx_wave_copy(seqs + so + b, buf + p.x + b, e - b, lane);
+    tx_wave_copy(quals + so + b, buf + p.y + b, e - b, lane);
   }
 }
 
 extern "C" void c3k_launch_fastq_count(const uint8_t* buf, uint32_t lo, uint32_t hi, int32_t* cnt, int at_eof, C3FqHdr* hdr, hipStream_t s) {
   const int tiles = (int)(((uint64_t)hi + FQ_TILE - 1) / FQ_TILE);
-  hipLaunchKernelGGL(k_fastq_count, dim3(tiles), dim3(64 * FQ_WAVES), 0, s, buf, lo, hi, cnt);
-  hipLaunchKernelGGL(k_fastq_scan, dim3(1), dim3(256), 0, s, cnt, tiles * FQ_WAVES, buf, lo, hi, at_eof, hdr);
+  hipLaunchKernelGGL(k_fastq_count, dim3(tiles), dim3(64 * TX_WAVES), 0, s, buf, lo, hi, cnt);
+  hipLaunchKernelGGL(k_fastq_scan, dim3(1), dim3(256), 0, s, cnt, tiles * TX_WAVES, buf, lo, hi, at_eof, hdr);
 }
 extern "C" void c3k_launch_fastq_lines(const uint8_t* buf, uint32_t lo, uint32_t hi, const int32_t* cnt, int32_t* nl, hipStream_t s) {
   const int tiles = (int)(((uint64_t)hi + FQ_TILE - 1) / FQ_TILE);
-  hipLaunchKernelGGL(k_fastq_lines, dim3(tiles), dim3(64 * FQ_WAVES), 0, s, buf, lo, hi, cnt, nl);
+  hipLaunchKernelGGL(k_fastq_lines, dim3(tiles), dim3(64 * TX_WAVES), 0, s, buf, lo, hi, cnt, nl);
 }
 // n_full whole candidate records (partial: one more, incomplete, at the end of the file); bsum holds 3 * ((n_full + 256) / 256) sums
 extern "C" void c3k_launch_fastq_records(const uint8_t* buf, uint32_t lo, uint32_t hi, const int32_t* nl, int L, int n_full, int partial, int min_len,
@@ -240,5 +240,5 @@ extern "C" void c3k_launch_fastq_records(const uint8_t* buf, uint32_t lo, uint32
 extern "C" void c3k_launch_fastq_gather(const uint8_t* buf, const int4* src, const int64_t* off, const int64_t* name_off, long long n_kept,
                                         uint8_t* names, uint8_t* seqs, uint8_t* quals, hipStream_t s) {
   if (n_kept <= 0) return;
-  hipLaunchKernelGGL(k_fastq_gather, dim3((unsigned)((n_kept + FQ_WAVES - 1) / FQ_WAVES)), dim3(64 * FQ_WAVES), 0, s, buf, src, off, name_off, n_kept, names, seqs, quals);
+  hipLaunchKernelGGL(k_fastq_gather, dim3((unsigned)((n_kept + TX_WAVES - 1) / TX_WAVES)), dim3(64 * TX_WAVES), 0, s, buf, src, off, name_off, n_kept, names, seqs, quals);
 }

@@ -13,7 +13,7 @@
 //       every workgroup again with its base, writing off[], name_off[], woff[] and the source positions.  woff and the longest
 //       sequence are what the 2-bit pack and k_adapter need, so no offset has to visit the host first.
 //   k_fastx_gather    the pass that moves every byte once, as k_fastq_gather does (one wave per record, four on a record above
-//       FQ_LONG bytes), qualities only when asked for; lane 0 of the record's wave writes the name hash.
+//       TX_LONG bytes), qualities only when asked for; lane 0 of the record's wave writes the name hash.
 // No atomics where a scan gives the place, no scratch, no load outside the dwords that hold text bytes or their 16 bytes of slack.
 #include "c3_dev.h"
 #include "c3_fastx.h"
@@ -68,12 +68,12 @@ __device__ __forceinline__ void fx_terms(const FxArgs& a, int r, int n_rec, long
 }
 
 __global__ __launch_bounds__(256) void k_fastx_rsum(FxArgs a) {
-  __shared__ long long lds[FQ_WAVES];
+  __shared__ long long lds[TX_WAVES];
   long long s, n, w, ts, tn, tw, tm;
   fx_terms(a, blockIdx.x * 256 + (int)threadIdx.x, fx_n_rec(a), &s, &n, &w);
   long long mx = s;
   for (int d = 32; d > 0; d >>= 1) mx = max(mx, (long long)__shfl_xor(mx, d, 64));
-  (void)fq_block_excl(s, lds, &ts); (void)fq_block_excl(n, lds, &tn); (void)fq_block_excl(w, lds, &tw);
+  (void)tx_block_excl(s, lds, &ts); (void)tx_block_excl(n, lds, &tn); (void)tx_block_excl(w, lds, &tw);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = mx;
   __syncthreads();
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void k_fastx_rsum(FxArgs a) {
 
 // bsum[0..4 * nb) -> exclusive prefix sums per column (column 3: the maximum), in place; the header and the closing entries
 __global__ __launch_bounds__(256) void k_fastx_rscan(FxArgs a, int nb) {
-  __shared__ long long lds[FQ_WAVES];
+  __shared__ long long lds[TX_WAVES];
   long long run[3] = {0, 0, 0}, mx = 0;
   for (int i0 = 0; i0 < nb; i0 += 256) {
     const int i = i0 + (int)threadIdx.x;
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void k_fastx_rscan(FxArgs a, int nb) {
     for (int c = 0; c < 3; ++c) {
       const long long v = i < nb ? a.bsum[4 * i + c] : 0;
       long long tot;
-      const long long ex = fq_block_excl(v, lds, &tot);
+      const long long ex = tx_block_excl(v, lds, &tot);
       if (i < nb) a.bsum[4 * i + c] = run[c] + ex;
       run[c] += tot;
     }
@@ -114,12 +114,12 @@ __global__ __launch_bounds__(256) void k_fastx_rscan(FxArgs a, int nb) {
 }
 
 __global__ __launch_bounds__(256) void k_fastx_rfin(FxArgs a) {
-  __shared__ long long lds[FQ_WAVES];
+  __shared__ long long lds[TX_WAVES];
   const int n_rec = fx_n_rec(a);
   const int r = blockIdx.x * 256 + (int)threadIdx.x;
   long long s, n, w, t;
   fx_terms(a, r, n_rec, &s, &n, &w);
-  const long long es = fq_block_excl(s, lds, &t), en = fq_block_excl(n, lds, &t), ew = fq_block_excl(w, lds, &t);
+  const long long es = tx_block_excl(s, lds, &t), en = tx_block_excl(n, lds, &t), ew = tx_block_excl(w, lds, &t);
   if (r >= n_rec) return;
   const long long* base = a.bsum + 4 * blockIdx.x;
   a.off[r] = base[0] + es; a.name_off[r] = base[1] + en; a.woff[r] = base[2] + ew;
@@ -128,35 +128,35 @@ __global__ __launch_bounds__(256) void k_fastx_rfin(FxArgs a) {
   a.src[r] = make_int4(a.nl[l0] + 1, a.kind == 4 ? a.nl[l0 + 2] + 1 : 0, b0 + 1, 0);           // sequence, quality, name
 }
 
-__global__ __launch_bounds__(64 * FQ_WAVES) void k_fastx_gather(FxArgs a) {
+__global__ __launch_bounds__(64 * TX_WAVES) void k_fastx_gather(FxArgs a) {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const long long i0 = (long long)blockIdx.x * FQ_WAVES;
+  const long long i0 = (long long)blockIdx.x * TX_WAVES;
   {
     const long long i = i0 + wv;
     if (i < a.n_records) {
       const int4 p = a.src[i];
       const int64_t no = a.name_off[i], so = a.off[i];
       const uint32_t nlen = (uint32_t)(a.name_off[i + 1] - no), sl = (uint32_t)(a.off[i + 1] - so);
-      fq_wave_copy(a.names + no, a.buf + p.z, nlen, lane);
+      tx_wave_copy(a.names + no, a.buf + p.z, nlen, lane);
       if (lane == 0) a.hash[i] = c3_fasta_hash(a.buf + p.z, (int64_t)nlen);
-      if (sl <= FQ_LONG) {
-        fq_wave_copy(a.seqs + so, a.buf + p.x, sl, lane);
-        if (a.quals) fq_wave_copy(a.quals + so, a.buf + p.y, sl, lane);
+      if (sl <= TX_LONG) {
+        tx_wave_copy(a.seqs + so, a.buf + p.x, sl, lane);
+        if (a.quals) tx_wave_copy(a.quals + so, a.buf + p.y, sl, lane);
       }
     }
   }
-  for (int k = 0; k < FQ_WAVES; ++k) {                  // long records of the workgroup: a quarter (in whole 256-byte rows) each
+  for (int k = 0; k < TX_WAVES; ++k) {                  // long records of the workgroup: a quarter (in whole 256-byte rows) each
     const long long i = i0 + k;
     if (i >= a.n_records) break;
     const int64_t so = a.off[i];
     const uint32_t sl = (uint32_t)(a.off[i + 1] - so);
-    if (sl <= FQ_LONG) continue;
+    if (sl <= TX_LONG) continue;
     const int4 p = a.src[i];
-    const uint32_t piece = (((sl + FQ_WAVES - 1) / FQ_WAVES) + 255u) & ~255u;
-    const uint32_t b = min(sl, piece * (uint32_t)wv), e = min(sl, b + piece);
-    fq_wave_copy(a.seqs + so + b, a.buf + p.x + b, e - b, lane);
-    if (a.quals) fq_wave_copy(a.quals + so + b, a.buf + p.y + b, e - b, lane);
+    uint32_t b, e;
+    tx_piece(sl, wv, TX_WAVES, &b, &e);
+    tx_wave_copy(a.seqs + so + b, a.buf + p.x + b, e - b, lane);
+    if (a.quals) tx_wave_copy(a.quals + so + b, a.buf + p.y + b, e - b, lane);
   }
 }
 
@@ -177,5 +177,5 @@ extern "C" void c3k_launch_fastx_records(const FxArgs* a, hipStream_t s) {
 }
 extern "C" void c3k_launch_fastx_gather(const FxArgs* a, hipStream_t s) {
   if (a->n_records <= 0) return;
-  hipLaunchKernelGGL(k_fastx_gather, dim3((unsigned)((a->n_records + FQ_WAVES - 1) / FQ_WAVES)), dim3(64 * FQ_WAVES), 0, s, *a);
+  hipLaunchKernelGGL(k_fastx_gather, dim3((unsigned)((a->n_records + TX_WAVES - 1) / TX_WAVES)), dim3(64 * TX_WAVES), 0, s, *a);
 }

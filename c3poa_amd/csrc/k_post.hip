@@ -11,8 +11,8 @@
 //       one small workgroup over those, then every workgroup again with its base, writing the arena offset of each record.
 //       No atomics anywhere: the order of the records in a stream is the input order by construction.
 //   k_post_emit   the pass that moves every byte once: one wave per read, the four waves of a workgroup together on the
-//       body segments of a read above PO_LONG bytes.  Literals and decimals are written by the first few lanes; forward
-//       segments go dword-wise from two aligned source dwords joined by v_alignbyte (k_fastq_gather's scheme); reverse
+//       body segments of a read above TX_LONG bytes.  Literals and decimals are written by the first few lanes; forward
+//       segments go dword-wise from two aligned source dwords joined by v_alignbyte (tx_wave_copy of k_text.h); reverse
 //       segments walk the source dwords from the end, swap the bytes of each and complement them through a 256-byte table in
 //       LDS (qualities skip the table).  A wave writes nothing outside its record's own range [roff, roff + length) and reads
 //       nothing outside the dwords that hold the batch's bytes (the host keeps 16 bytes of slack behind every buffer).
@@ -20,29 +20,9 @@
 #include "c3_args.h"
 #include "c3_post.h"
 #include "c3_launch.h"
+#include "k_text.h"
 
-#define PO_WAVES 4
-#define PO_LONG 32768                 // read bytes above which the workgroup shares the body segments
 #define PO_COLS (C3_POST_MAX_STREAMS + 1)
-
-__device__ __forceinline__ long long po_wave_incl(long long v) {
-  const int lane = threadIdx.x & 63;
-  for (int d = 1; d < 64; d <<= 1) { const long long t = __shfl_up(v, d, 64); if (lane >= d) v += t; }
-  return v;
-}
-
-// exclusive scan over the 256 lanes of a workgroup; every lane calls it
-__device__ __forceinline__ long long po_block_excl(long long v, long long* lds, long long* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long long inc = po_wave_incl(v);
-  __syncthreads();                                       // (lds is reused from one call to the next)
-  if (lane == 63) lds[wv] = inc;
-  __syncthreads();
-  long long base = 0, tot = 0;
-  for (int k = 0; k < PO_WAVES; ++k) { const long long x = lds[k]; if (k < wv) base += x; tot += x; }
-  *total = tot;
-  return base + inc - v;
-}
 
 __global__ __launch_bounds__(256) void k_post_classify(PostArgs a) {
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
@@ -89,25 +69,25 @@ __device__ __forceinline__ long long po_contrib(const PoRead& r, int c, int S, i
 }
 
 __global__ __launch_bounds__(256) void k_post_rsum(PostArgs a) {
-  __shared__ long long lds[PO_WAVES][PO_COLS];
+  __shared__ long long lds[TX_WAVES][PO_COLS];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, SC = a.S + 1;
   const PoRead r = po_load(a, blockIdx.x * 256 + (int)threadIdx.x);
   for (int c = 0; c < SC; ++c) {
     int rec;
-    const long long inc = po_wave_incl(po_contrib(r, c, a.S, &rec));
+    const long long inc = tx_wave_incl(po_contrib(r, c, a.S, &rec));
     if (lane == 63) lds[wv][c] = inc;
   }
   __syncthreads();
   if ((int)threadIdx.x < SC) {
     long long t = 0;
-    for (int k = 0; k < PO_WAVES; ++k) t += lds[k][threadIdx.x];
+    for (int k = 0; k < TX_WAVES; ++k) t += lds[k][threadIdx.x];
     a.bsum[(size_t)blockIdx.x * SC + threadIdx.x] = t;
   }
 }
 
 // bsum[nb][S + 1] -> exclusive prefix sums per column, in place; stream_off[S + 1] and the kept count
 __global__ __launch_bounds__(256) void k_post_rscan(PostArgs a, int nb) {
-  __shared__ long long lds[PO_WAVES];
+  __shared__ long long lds[TX_WAVES];
   __shared__ long long tot[PO_COLS];
   const int SC = a.S + 1;
   for (int c = 0; c < SC; ++c) {
@@ -116,7 +96,7 @@ __global__ __launch_bounds__(256) void k_post_rscan(PostArgs a, int nb) {
       const int i = i0 + (int)threadIdx.x;
       const long long v = i < nb ? a.bsum[(size_t)i * SC + c] : 0;
       long long t;
-      const long long ex = po_block_excl(v, lds, &t);
+      const long long ex = tx_block_excl(v, lds, &t);
       if (i < nb) a.bsum[(size_t)i * SC + c] = run + ex;
       run += t;
     }
@@ -132,7 +112,7 @@ __global__ __launch_bounds__(256) void k_post_rscan(PostArgs a, int nb) {
 }
 
 __global__ __launch_bounds__(256) void k_post_rfin(PostArgs a) {
-  __shared__ long long lds[PO_WAVES][PO_COLS];
+  __shared__ long long lds[TX_WAVES][PO_COLS];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, SC = a.S + 1;
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
   const PoRead r = po_load(a, i);
@@ -140,7 +120,7 @@ __global__ __launch_bounds__(256) void k_post_rfin(PostArgs a) {
   for (int c = 0; c < a.S; ++c) {
     int rec;
     const long long v = po_contrib(r, c, a.S, &rec);
-    const long long inc = po_wave_incl(v);
+    const long long inc = tx_wave_incl(v);
     if (lane == 63) lds[wv][c] = inc;
     const long long ex = inc - v;
     if (rec == 0) e0 = ex; else if (rec == 1) e1 = ex; else if (rec == 2) e2 = ex; else if (rec == 3) e3 = ex; else if (rec == 4) e4 = ex; else if (rec == 5) e5 = ex;
@@ -157,22 +137,7 @@ __global__ __launch_bounds__(256) void k_post_rfin(PostArgs a) {
   }
 }
 
-// dst[0..len) = src[0..len) by the 64 lanes of a wave, any alignment on either side (fq_wave_copy of k_fastq.hip)
-__device__ __forceinline__ void po_copy_fwd(uint8_t* dst, const uint8_t* src, uint32_t len, int lane) {
-  const uint32_t head = min(len, (uint32_t)((4u - ((uintptr_t)dst & 3u)) & 3u));
-  if ((uint32_t)lane < head) dst[lane] = src[lane];
-  const uint32_t nd = (len - head) >> 2;
-  uint32_t* d4 = (uint32_t*)(dst + head);
-  const uint8_t* s = src + head;
-  const uint32_t sh = (uint32_t)((uintptr_t)s & 3u);
-  const uint32_t* sa = (const uint32_t*)(s - sh);
-  if (sh == 0) { for (uint32_t k = (uint32_t)lane; k < nd; k += 64u) d4[k] = sa[k]; }
-  else         { for (uint32_t k = (uint32_t)lane; k < nd; k += 64u) d4[k] = __builtin_amdgcn_alignbyte(sa[k + 1], sa[k], sh); }   // sa[k + 1] holds byte s + 4k + 3 at least
-  const uint32_t done = head + 4u * nd, tail = len - done;
-  if ((uint32_t)lane < tail) dst[done + lane] = src[done + lane];
-}
-
-// dst[j] = T(src[len - 1 - j]), T = the complement table (COMP) or the identity: destination dwords in ascending order, the
+// the reverse of tx_wave_copy: dst[j] = T(src[len - 1 - j]), T = the complement table (COMP) or the identity: destination dwords in ascending order, the
 // source dword of each (any alignment: two aligned dwords joined by v_alignbyte) taken from the end and byte-swapped
 template <bool COMP> __device__ __forceinline__ uint8_t po_tr(const uint8_t* tab, uint8_t c) { return COMP ? tab[c] : c; }
 template <bool COMP> __device__ __forceinline__ void po_copy_rev(uint8_t* dst, const uint8_t* src, uint32_t len, int lane, const uint8_t* tab) {
@@ -217,15 +182,12 @@ __device__ __forceinline__ void po_emit_records(const PostArgs& a, int i, int la
       } else if (kind == C3_SEG_DEC) {
         if (part == 0 && lane < sl) out[lane] = (uint8_t)c3_post_digit((uint32_t)sa, sl, lane);
       } else if (kind == C3_SEG_NAME) {
-        if (part == 0) po_copy_fwd(out, a.names + no, (uint32_t)sl, lane);
+        if (part == 0) tx_wave_copy(out, a.names + no, (uint32_t)sl, lane);
       } else {
-        uint32_t b = 0, e = (uint32_t)sl;                             // this wave's piece of the destination, in whole 256-byte rows
-        if (parts > 1) {
-          const uint32_t piece = ((((uint32_t)sl + parts - 1) / parts) + 255u) & ~255u;
-          b = min((uint32_t)sl, piece * (uint32_t)part); e = min((uint32_t)sl, b + piece);
-        }
+        uint32_t b = 0, e = (uint32_t)sl;                             // this wave's piece of the destination
+        if (parts > 1) tx_piece((uint32_t)sl, part, parts, &b, &e);
         const uint8_t* src = (kind == C3_SEG_SEQ_F || kind == C3_SEG_SEQ_R) ? seq + sa : qual + sa;
-        if (kind == C3_SEG_SEQ_F || kind == C3_SEG_QUAL_F) po_copy_fwd(out + b, src + b, e - b, lane);
+        if (kind == C3_SEG_SEQ_F || kind == C3_SEG_QUAL_F) tx_wave_copy(out + b, src + b, e - b, lane);
         else if (kind == C3_SEG_SEQ_R) po_copy_rev<true>(out + b, src + ((uint32_t)sl - e), e - b, lane, comp);
         else po_copy_rev<false>(out + b, src + ((uint32_t)sl - e), e - b, lane, comp);
       }
@@ -255,25 +217,25 @@ __device__ __forceinline__ void po_emit_psl(const PostArgs& a, int i, int lane) 
   }
 }
 
-__global__ __launch_bounds__(64 * PO_WAVES) void k_post_emit(PostArgs a) {
+__global__ __launch_bounds__(64 * TX_WAVES) void k_post_emit(PostArgs a) {
   __shared__ uint8_t comp[256];
   comp[threadIdx.x] = c3_post_comp((uint8_t)threadIdx.x);
   __syncthreads();
   const int lane = threadIdx.x & 63;
   const int wv = wave_first((int)(threadIdx.x >> 6));
-  const int i0 = blockIdx.x * PO_WAVES;
+  const int i0 = blockIdx.x * TX_WAVES;
   {
     const int i = i0 + wv;
     if (i < a.n) {
       if (a.o.n_ad > 0) po_emit_psl(a, i, lane);
-      if (a.off[i + 1] - a.off[i] <= PO_LONG) po_emit_records(a, i, lane, 0, 1, comp);
+      if (a.off[i + 1] - a.off[i] <= TX_LONG) po_emit_records(a, i, lane, 0, 1, comp);
     }
   }
-  for (int k = 0; k < PO_WAVES; ++k) {                   // long reads of the workgroup: a quarter of every body segment each
+  for (int k = 0; k < TX_WAVES; ++k) {                   // long reads of the workgroup: a quarter of every body segment each
     const int i = i0 + k;
     if (i >= a.n) break;
-    if (a.off[i + 1] - a.off[i] <= PO_LONG) continue;
-    po_emit_records(a, i, lane, wv, PO_WAVES, comp);
+    if (a.off[i + 1] - a.off[i] <= TX_LONG) continue;
+    po_emit_records(a, i, lane, wv, TX_WAVES, comp);
   }
 }
 
@@ -288,5 +250,5 @@ extern "C" void c3k_launch_post_scan(const PostArgs* a, hipStream_t s) {
   if (nb) hipLaunchKernelGGL(k_post_rfin, dim3(nb), dim3(256), 0, s, *a);
 }
 extern "C" void c3k_launch_post_emit(const PostArgs* a, hipStream_t s) {
-  if (a->n > 0) hipLaunchKernelGGL(k_post_emit, dim3((a->n + PO_WAVES - 1) / PO_WAVES), dim3(64 * PO_WAVES), 0, s, *a);
+  if (a->n > 0) hipLaunchKernelGGL(k_post_emit, dim3((a->n + TX_WAVES - 1) / TX_WAVES), dim3(64 * TX_WAVES), 0, s, *a);
 }
