@@ -238,14 +238,15 @@ extern "C" int c3_set_splints(c3_handle* h, int n, const char* cat, const int64_
   if (!h || n <= 0 || !cat || !off) return C3_E_ARG;
   HIPCHK(hipSetDevice(h->cfg.device));
   std::vector<uint8_t> codes((size_t)n * 2 * C3_SPLINT_MAX, 0);
-  h->sp_len.assign(n, 0); h->max_spl = 0;
+  // a refused table changes nothing: sp_len / max_spl size the scratch of the scans that run against the table on the device
+  std::vector<int> sp_len((size_t)n, 0); int max_spl = 0;
   for (int i = 0; i < n; ++i) {
     int S = (int)(off[i + 1] - off[i]);
     if (S <= 0 || S > C3_SPLINT_MAX) return c3_fail(h, C3_E_LIMIT, "splint length must be 1..512");
     // a cell grows by the larger of the two substitution scores per splint row, whichever of them it is
     if ((long long)std::max({h->cfg.conk_match, h->cfg.conk_mismatch, 0}) * S > 32000 || h->cfg.conk_penalty < 0 || h->cfg.conk_penalty > 32000)
       return c3_fail(h, C3_E_LIMIT, "max(conk_match, conk_mismatch) * splint length and conk_penalty must stay within 32000 (16-bit score cells in k_conk)");
-    h->sp_len[i] = S; h->max_spl = std::max(h->max_spl, S);
+    sp_len[(size_t)i] = S; max_spl = std::max(max_spl, S);
     for (int k = 0; k < S; ++k) {
       int c = code_of(cat[off[i] + k]);
       codes[((size_t)i * 2 + 0) * C3_SPLINT_MAX + k] = (uint8_t)c;
@@ -253,9 +254,9 @@ extern "C" int c3_set_splints(c3_handle* h, int n, const char* cat, const int64_
     }
   }
   HIPCHK(h->d_sp_codes.put(codes.data(), codes.size(), h->stream));
-  HIPCHK(h->d_sp_len.put(h->sp_len.data(), sizeof(int) * n, h->stream));
+  HIPCHK(h->d_sp_len.put(sp_len.data(), sizeof(int) * n, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->n_spl = n;
+  h->sp_len.swap(sp_len); h->max_spl = max_spl; h->n_spl = n;
   return C3_E_OK;
 }
 

@@ -143,7 +143,8 @@ const char* c3_last_error(const c3_handle* h);
 /* splint table (C3POa.py:231-234: splint_dict[name] = [seq, revcomp(seq)]); the library makes the
  * reverse complements itself.  cat = concatenated ASCII, off[n+1]. */
 /* k_conk keeps its score cells in 16 bits: max(conk_match, conk_mismatch, 0) * splint length must not exceed 32000 and
- * conk_penalty must lie in 0..32000, for every splint; otherwise C3_E_LIMIT with a c3_last_error text. */
+ * conk_penalty must lie in 0..32000, for every splint; otherwise C3_E_LIMIT with a c3_last_error text.  A splint of 0 or of more
+ * than 512 bases is C3_E_LIMIT as well.  A refused call leaves the table of the last successful call in force. */
 int c3_set_splints(c3_handle* h, int n, const char* cat, const int64_t* off);
 
 /* batch = the `reads` argument of analyze_reads (C3POa.py:110) in SoA form.
