@@ -2,7 +2,7 @@
 """C3POa.py -- drop-in CLI of the MI355X-native R2C2 consensus caller.
 
 Same flags, inputs and output tree as rvolden/C3POa v2.2.3 (/root/reference/C3POa.py:26-63, 175-272):
-    python3 C3POa.py -r reads.fastq -s splint.fasta -o out -c config -l 1000 -d 500 -n N -g 1000 [-z] [-b] [-co]
+    python3 C3POa.py -r reads.fastq|reads.bam -s splint.fasta -o out -c config -l 1000 -d 500 -n N -g 1000 [-z] [-b] [-co]
 writes <out>/c3poa.log, <out>/tmp/splint_to_read_alignments.psl (reused when present),
 <out>/<splint>/R2C2_Consensus.fasta[.gz] and <out>/<splint>/R2C2_Subreads.fastq[.gz].
 
@@ -24,7 +24,8 @@ from c3poa_amd.seqio import fastx_read, revcomp  # noqa: E402
 
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="Makes consensus sequences from R2C2 reads.", add_help=True, prefix_chars="-")
-    parser.add_argument("--reads", "-r", type=str, action="store", help="FASTQ file that contains the long R2C2 reads.")
+    parser.add_argument("--reads", "-r", type=str, action="store", help="File that contains the long R2C2 reads: FASTQ (plain, gzip or BGZF) or an unaligned BAM "
+                             "(.bam, as basecallers write it; an aligned BAM is refused: convert it with samtools fastq).")
     parser.add_argument("--splint_file", "-s", type=str, action="store", help="Path to the splint FASTA file.")
     parser.add_argument("--out_path", "-o", type=str, action="store", default=os.getcwd(),
                         help="Directory where all the files will end up. Defaults to your current directory.")
@@ -45,7 +46,7 @@ def parse_args(argv=None):
                         help="Number of reads processed by each worker in each iteration. Defaults to 1000.")
     parser.add_argument("--splint-finder", dest="splint_finder", choices=["gpu", "blat"], default="gpu",
                         help="How reads are assigned to splints when the PSL does not exist yet: the GPU finder "
-                             "(default) or the blat binary of the config file, as upstream.")
+                             "(default) or the blat binary of the config file, as upstream (FASTQ input only: a .bam is refused).")
     parser.add_argument("--blatThreads", "-b", action="store_true", default=False, help="Accepted for compatibility.")
     parser.add_argument("--compress_output", "-co", action="store_true", default=False,
                         help="Use to compress (gzip) both the consensus fasta and subread fastq output files.")
@@ -53,13 +54,14 @@ def parse_args(argv=None):
                         help="Compress the outputs to BGZF on the GPU while the run goes (implies -co: the same .gz file "
                              "names, readable by gzip, without an uncompressed file or a pass after the run). Off by default.")
     parser.add_argument("--inflate", choices=["host", "gpu"], default="host",
-                        help="Where a BGZF .gz input is inflated: zlib threads on the host (default), or the GPU (the "
+                        help="Where a BGZF .gz or a .bam input is inflated: zlib threads on the host (default), or the GPU (the "
                              "inflater threads' cores go back to the parser and the writers). Any other gzip file is read "
                              "as before.")
     parser.add_argument("--parse", choices=["host", "gpu"], default="host",
-                        help="Where the records of a BGZF .gz input are found: the reader's parser thread on the host "
+                        help="Where the records of a BGZF .gz or a .bam input are found: the reader's parser thread on the host "
                              "(default), or the GPU, where --inflate gpu has left the text (needs --inflate gpu; strict "
-                             "four-line FASTQ is parsed there, anything else by the host parser as before).")
+                             "four-line FASTQ is parsed there, anything else by the host parser as before; the records of "
+                             "an unaligned BAM are decoded there, and a record it cannot take is an error on either path).")
     parser.add_argument("--consensus-fastq", dest="consensus_fastq", action="store_true", default=False,
                         help="Also write <splint>/R2C2_Consensus.fastq: every consensus with per-base support QVs computed on "
                              "the GPU (not calibrated error probabilities; see DESIGN.md). Off by default.")

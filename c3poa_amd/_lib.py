@@ -30,7 +30,7 @@ EXPORTS = ["c3_default_config", "c3_version", "c3_device_count", "c3_warm_device
            "c3_bgzf_create", "c3_bgzf_destroy", "c3_bgzf_bound", "c3_bgzf_compress", "c3_bgzf_compress_host",
            "c3_write_group_bgzf", "c3_write_consensus_fastq_bgzf",
            "c3_bgzf_scan", "c3_bgzf_decompress", "c3_bgzf_decompress_host", "c3_reader_open_inflate", "c3_reader_inflate_wait",
-           "c3_fastq_parse", "c3_fastq_parse_host", "c3_reader_parse_on_device", "c3_reader_parse_stats",
+           "c3_fastq_parse", "c3_fastq_parse_host", "c3_reader_parse_on_device", "c3_reader_parse_stats", "c3_bam_parse", "c3_bam_parse_host",
            "c3_post_emit", "c3_post_emit_host", "c3_post_emit_timing",
            "c3_fasta_parse", "c3_fasta_parse_host", "c3_demux_emit", "c3_demux_emit_host", "c3_demux_emit_timing",
            "c3_emit_group", "c3_emit_group_host", "c3_batch_emit_snapshot", "c3_batch_emit_fetch", "c3_emit_timing_get", "c3_append_streams",
@@ -120,6 +120,11 @@ class DemuxTextTiming(C.Structure):
 
 class FastqInfo(_Info):
     _fields_ = [(k, C.c_int64) for k in ("n_records", "n_kept", "n_short", "consumed", "name_bytes", "base_bytes")] + [("departed", C.c_int32)]
+
+
+class BamInfo(_Info):
+    _fields_ = [(k, C.c_int64) for k in ("n_records", "n_kept", "n_short", "consumed", "name_bytes", "base_bytes", "header_bytes", "bad_at")] + \
+               [("departed", C.c_int32), ("reason", C.c_int32)]
 
 
 class FastxInfo(_Info):
@@ -259,6 +264,9 @@ def load():
     fq = [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(FastqInfo)]
     lib.c3_fastq_parse.argtypes = [vp] + fq
     lib.c3_fastq_parse_host.argtypes = fq
+    bam = [vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(BamInfo)]
+    lib.c3_bam_parse.argtypes = [vp] + bam
+    lib.c3_bam_parse_host.argtypes = bam
     lib.c3_reader_parse_on_device.argtypes = [vp, C.c_int]
     lib.c3_reader_parse_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.c3_post_emit.argtypes = [vp, C.POINTER(PostArgs), vp, C.c_int64, vp, vp]
@@ -1138,12 +1146,14 @@ class HostBatch:
 
 
 class Reader:
-    """native streaming FASTA/FASTQ(.gz) reader (c3_reader_*): mm.fastx_read replacement that yields SoA groups"""
+    """native streaming FASTA/FASTQ(.gz) reader (c3_reader_*): mm.fastx_read replacement that yields SoA groups; a path
+    ending in .bam is read as unaligned BAM (BGZF; the groups of the FASTQ of the same records; a record it cannot take is
+    a ValueError of next naming the record, its inflated byte offset and the reason)"""
 
     def __init__(self, path, n_sets=3, names_only=False, byte_range=None, inflate_device=None, parse_device=False, stage_device=False):
         """byte_range = (beg, end): only the records that START inside [beg, end) (plain files; c3_reader_open_range)
         inflate_device = d: a BGZF file is inflated by k_inflate on device d (c3_reader_open_inflate; whole-file readers)
-        parse_device: ... and its records are parsed there too (k_fastq; c3_reader_parse_on_device).  C3Error with code
+        parse_device: ... and its records are parsed there too (k_fastq, k_bam for a .bam; c3_reader_parse_on_device).  C3Error with code
         E_STATE when the reader is not one of a BGZF file with inflate_device
         stage_device: ... and the bases and qualities of its groups stay there (c3_reader_stage_on_device): a device group has
         hb.dev (c3_device_batch) and no seqs / quals; after a departure the groups are host groups (hb.dev is None)"""
@@ -1491,14 +1501,16 @@ class FastqParse:
         return [(self.names[no[i]:no[i + 1]], self.seqs[o[i]:o[i + 1]], self.quals[o[i]:o[i + 1]]) for i in range(len(o) - 1)]
 
 
-def _fastq_call(fn, first, text, at_eof, min_len, text_offset=0, caps=None):
+def _fastq_call(fn, first, text, at_eof, min_len, text_offset=0, caps=None, bam_at_start=None):
+    """bam_at_start is None: a FASTQ call; else a BAM call (at_start in front of at_eof, a BamInfo, room for 2 bases per byte)"""
     src = _bytes(text)
     n = len(src)
     # the text at byte `text_offset` (0..3) of a dword
     raw = np.zeros(n + 16, dtype=np.uint8)
     at = (-raw.ctypes.data) % 4 + int(text_offset)
     raw[at:at + n] = np.frombuffer(src, dtype=np.uint8)
-    names_cap, bases_cap, max_records = caps if caps is not None else (n, n // 2 + 1, n // 7 + 1)
+    fit = (n, n // 2 + 1, n // 7 + 1) if bam_at_start is None else (n, n, n // 38 + 1)
+    names_cap, bases_cap, max_records = caps if caps is not None else fit
     g = FASTQ_GUARD
 
     def arr(nbytes):
@@ -1508,8 +1520,9 @@ def _fastq_call(fn, first, text, at_eof, min_len, text_offset=0, caps=None):
     bufs = {"names": arr(names_cap), "seqs": arr(bases_cap), "quals": arr(bases_cap),
             "name_off": arr(8 * (max_records + 1)), "off": arr(8 * (max_records + 1))}
     ptr = {k: v.ctypes.data + g for k, v in bufs.items()}
-    info = FastqInfo()
-    rc = fn(*(first + (raw.ctypes.data + at if n else None, n, int(bool(at_eof)), int(min_len), ptr["names"], names_cap, ptr["name_off"],
+    info = FastqInfo() if bam_at_start is None else BamInfo()
+    kind = () if bam_at_start is None else (int(bool(bam_at_start)),)
+    rc = fn(*(first + (raw.ctypes.data + at if n else None, n) + kind + (int(bool(at_eof)), int(min_len), ptr["names"], names_cap, ptr["name_off"],
                        ptr["seqs"], ptr["quals"], bases_cap, ptr["off"], max_records, C.byref(info))))
     out = FastqParse()
     out.info = info.as_dict()
@@ -1536,6 +1549,19 @@ def fastq_parse_host(text, at_eof=False, min_len=0, text_offset=0, caps=None):
     """c3_fastq_parse_host: the longest prefix of whole strict records of `text`; the host statement of Bgzf.fastq_parse.
     caps = (names_cap, bases_cap, max_records) instead of sizes that always fit; C3Error (code E_LIMIT, .info) when too small"""
     return _fastq_call(load().c3_fastq_parse_host, (), text, at_eof, min_len, text_offset, caps)
+
+
+# ---- Unaligned BAM records on the GPU (-r reads.bam; include/c3poa.h "Unaligned BAM records on the GPU", DESIGN.md 5.12) ----
+BAM_TILE = 65536                # C3_BAM_TILE: bytes of data per chain tile of k_bam
+BAM_MAX_RECORD = 1 << 28        # C3_BAM_MAX_RECORD
+BAM_REASONS = ("OK", "BLOCK", "NAME", "FIELDS", "FLAG", "EMPTY", "NOQUAL", "TRUNCATED", "HEADER")      # c3_bam_info.reason
+
+
+def bam_parse_host(data, at_start=True, at_eof=False, min_len=0, text_offset=0, caps=None):
+    """c3_bam_parse_host: the file header (at_start) and the longest prefix of whole strict records of the inflated BAM bytes
+    `data`; the host statement of Bgzf.bam_parse.  The result object, text_offset and caps of fastq_parse_host; info also has
+    header_bytes, reason (an index of BAM_REASONS) and bad_at"""
+    return _fastq_call(load().c3_bam_parse_host, (), data, at_eof, min_len, text_offset, caps, bam_at_start=bool(at_start))
 
 
 # ---- Sample demultiplexer, text in / file bytes out (C3POa_demux.py --emit gpu; DESIGN.md 5.7) ----
@@ -1791,6 +1817,11 @@ class Bgzf:
         """c3_fastq_parse: the strict FASTQ records of `text` found and gathered by k_fastq (a FastqParse); text_offset
         0..3 = where the text starts inside a dword, which the device copy keeps"""
         return _fastq_call(self.lib.c3_fastq_parse, (self.z,), text, at_eof, min_len, text_offset, caps)
+
+    def bam_parse(self, data, at_start=True, at_eof=False, min_len=0, text_offset=0, caps=None):
+        """c3_bam_parse: the strict records of the inflated BAM bytes `data` found and gathered by k_bam (a FastqParse whose
+        info is that of bam_parse_host); text_offset places the data at that byte (0..3) of a dword"""
+        return _fastq_call(self.lib.c3_bam_parse, (self.z,), data, at_eof, min_len, text_offset, caps, bam_at_start=bool(at_start))
 
     def close(self):
         if self.z:

@@ -14,6 +14,10 @@ int c3_qv_check(const char* cons, int n, int n_pieces, const char* seq_cat, cons
 int c3_fastq_check_args(const char* who, const char* text, int64_t n, const char* names, int64_t names_cap, const int64_t* name_off,
                         const char* seqs, const char* quals, int64_t bases_cap, const int64_t* off, int64_t max_records,
                         c3_fastq_info* info);                                                                         // c3_fastq.cpp
+int c3_bam_check_args(const char* who, const char* data, int64_t n, const char* names, int64_t names_cap, const int64_t* name_off,
+                      const char* seqs, const char* quals, int64_t bases_cap, const int64_t* off, int64_t max_records,
+                      c3_bam_info* info);                                                                             // c3_bam.cpp
+const char* c3_bam_reason_text(int reason);                                                                           // c3_bam.cpp
 int c3_fasta_check_args(const char* who, const char* text, int64_t n, const char* names, int64_t names_cap, const int64_t* name_off,
                         const char* seqs, int64_t bases_cap, const int64_t* off, const uint64_t* name_hash, int64_t max_records,
                         c3_fasta_info* info);                                                                         // c3_fasta.cpp
@@ -26,9 +30,14 @@ int c3_demux_text_check_args(const char* who, const char* src, int64_t n, int fl
 int c3_bgzf_data_error(const char* who, int64_t member, int st);                                                      // c3_inflate.cpp
 
 // the reader's device stretches (c3_stream.hip, called by c3_io.cpp; not part of the public interface)
-struct c3_fq_stretch { c3_fastq_info info; const int64_t* off; const int64_t* name_off; int64_t text_bytes; };
+// (a BAM stretch fills the same table: info as for FASTQ, plus the reason and place of a departure and the file header's bytes)
+struct c3_fq_stretch { c3_fastq_info info; const int64_t* off; const int64_t* name_off; int64_t text_bytes;
+                       int32_t reason; int64_t bad_at, header_bytes; };
 extern "C" int c3_bgzf_stretch_parse(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, int64_t carry_from, int64_t carry_len,
                                      int at_eof, c3_fq_stretch* out);
+// the same for the inflated bytes of a BAM file (k_bam): at_start != 0 while the file header has not been consumed
+extern "C" int c3_bgzf_stretch_parse_bam(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, int64_t carry_from, int64_t carry_len,
+                                         int at_start, int at_eof, c3_fq_stretch* out);
 extern "C" int c3_bgzf_stretch_fetch(c3_bgzf* z, int slot, int64_t r0, int64_t r1, char* names, char* seqs, char* quals);
 extern "C" int c3_bgzf_stretch_text(c3_bgzf* z, int slot, int64_t from, int64_t len, char* dst);
 // the reader's device buffer sets (c3_reader_stage_on_device): n_sets pairs of grow-only device buffers; _reserve grows set

@@ -276,6 +276,9 @@ struct c3_bgzf {
   } fq[2];
   DBuf d_cnt, d_nl, d_slen, d_nlen, d_bsum, d_hdr;
   C3FqHdr* h_hdr = nullptr;
+  // k_bam (first use): the chain tiles, the record starts and what the rule says of each; the slots and sums are k_fastq's
+  DBuf d_tiles, d_rpos, d_reason, d_rsrc, d_bhdr;
+  C3BamHdr* h_bhdr = nullptr;
   hipStream_t copy_stream = nullptr;
   // the reader's device buffer sets (c3_reader_stage_on_device): the home of a device group, filled from the slots on copy_stream
   struct DevSet { DBuf seqs, quals; };

@@ -29,6 +29,7 @@
 
 #include "../../include/c3poa.h"
 #include "c3_checks.h"
+#include "c3_bam.h"
 #include "c3_emit.h"
 
 namespace {
@@ -86,6 +87,7 @@ struct BgzfStretch {
   bool on_dev = false;                      // parsed on the device: fq describes its records, next_rec is the first not yet in a group
   c3_fq_stretch fq{};
   int64_t next_rec = 0;
+  int64_t base_off = 0;                     // BAM: inflated file offset of the stretch's first byte (error texts)
 };
 struct Bgzf {
   FILE* fp = nullptr;
@@ -107,6 +109,10 @@ struct Bgzf {
   // c3_reader_stage_on_device: while dev_active, groups stay on the device (one device set per host set, held by dev)
   bool stage_on = false;
   int64_t grp_dev = 0, grp_host = 0, host_bytes = 0;
+  // a .bam file: the device stretches go through k_bam; at_start until a stretch has consumed the file header; dev_base =
+  // inflated bytes consumed by the stretches in front of the current one
+  bool bam = false, bam_at_start = true;
+  int64_t dev_base = 0;
 };
 
 struct c3_reader {
@@ -122,6 +128,8 @@ struct c3_reader {
   size_t file_bytes = 0, hint_bases = 0;
   int64_t buf_off = 0;          // file offset of buf[0] (plain files)
   int64_t range_end = -1;       // byte range readers stop at the first record that starts at or after this offset
+  bool bam = false;             // a .bam path: the inflated bytes are BAM records (c3_bam.h), not text
+  bool bam_hdr = false;         // ... whose file header has been consumed
 };
 
 namespace {
@@ -198,8 +206,10 @@ bool bgzf_next_stretch(Bgzf* bz, BgzfStretch* b, size_t max_members = 512) {
   if (b->coff.empty()) return false;
   b->on_dev = false;
   if (bz->dev && bz->parse_on) {                                // inflated and parsed on the device; only the record tables come back
-    const int rc = c3_bgzf_stretch_parse(bz->dev, (int)(b - bz->st), (const char*)b->comp.data(), (int64_t)b->comp.size(),
-                                         bz->carry_from, bz->carry_len, bz->eof ? 1 : 0, &b->fq);
+    const int rc = bz->bam ? c3_bgzf_stretch_parse_bam(bz->dev, (int)(b - bz->st), (const char*)b->comp.data(), (int64_t)b->comp.size(),
+                                                       bz->carry_from, bz->carry_len, bz->bam_at_start ? 1 : 0, bz->eof ? 1 : 0, &b->fq)
+                           : c3_bgzf_stretch_parse(bz->dev, (int)(b - bz->st), (const char*)b->comp.data(), (int64_t)b->comp.size(),
+                                                   bz->carry_from, bz->carry_len, bz->eof ? 1 : 0, &b->fq);
     if (rc != C3_E_OK) { bz->why = c3_last_error(nullptr); bz->bad = true; return false; }
     b->on_dev = true; b->next_rec = 0; b->dend = 0;
     ++bz->n_dev;
@@ -321,17 +331,20 @@ extern "C" int c3_reader_open(const char* path, int n_sets, c3_reader** out) {
   if (!path || !out) return C3_E_ARG;
   c3_reader* r = new c3_reader();
   size_t n = strlen(path);
-  if (n > 3 && strcmp(path + n - 3, ".gz") == 0) {
-    // BGZF (bgzip): members located by their headers and inflated in parallel; any other gzip file: one zlib stream
+  r->bam = n > 4 && strcmp(path + n - 4, ".bam") == 0;
+  if (r->bam || (n > 3 && strcmp(path + n - 3, ".gz") == 0)) {
+    // BGZF (bgzip): members located by their headers and inflated in parallel; any other gzip file: one zlib stream.
+    // A .bam is BGZF by definition (no C3_NO_BGZF escape); one that is not stays open so that the first next can say so
     unsigned char hd[18]; size_t got = 0;
     FILE* f = fopen(path, "rb");
     if (f) { got = fread(hd, 1, 18, f); }
-    if (f && got == 18 && bgzf_member_size(hd, 18) && !getenv("C3_NO_BGZF")) {
+    if (f && got == 18 && bgzf_member_size(hd, 18) && (r->bam || !getenv("C3_NO_BGZF"))) {
       rewind(f);
-      r->bz = new Bgzf(); r->bz->fp = f;
+      r->bz = new Bgzf(); r->bz->fp = f; r->bz->bam = r->bam;
       const char* e = getenv("C3_GZ_THREADS");
       r->bz->threads = e ? std::max(1, atoi(e)) : (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
-    } else {
+    } else if (r->bam) r->fp = f;
+    else {
       if (f) fclose(f);
       r->gz = gzopen(path, "rb"); if (r->gz) gzbuffer(r->gz, 1 << 20);
     }
@@ -396,6 +409,7 @@ extern "C" int c3_reader_open_range(const char* path, int n_sets, int64_t beg, i
   if (!path || !out || beg < 0) return C3_E_ARG;
   size_t n = strlen(path);
   if (n > 3 && strcmp(path + n - 3, ".gz") == 0) return C3_E_ARG;              // a gzip stream cannot be entered in the middle
+  if (n > 4 && strcmp(path + n - 4, ".bam") == 0) return C3_E_ARG;             // ... nor a BAM file (BGZF, and records that are a linked list)
   int rc = c3_reader_open(path, n_sets, out);
   if (rc != C3_E_OK) return rc;
   c3_reader* r = *out;
@@ -518,6 +532,14 @@ extern "C" int c3_reader_range_lost(const c3_reader* r) { return r && r->range_l
 
 namespace {
 
+// the error of a BAM reader at the record it cannot take: its index, its inflated byte offset, the reason (both paths)
+int bam_fail(c3_reader* r, int reason, int64_t at) {
+  char buf[320];
+  snprintf(buf, sizeof buf, "BAM input: record %lld at inflated byte %lld: %s", (long long)r->n_records, (long long)at, c3_bam_reason_text(reason));
+  r->err = buf;
+  return C3_E_ARG;
+}
+
 // the next stretch becomes the current one (what bgzf_read does between two stretches), and the one after it starts loading.
 // false: nothing more was loaded (end of file, or b->bad)
 bool dev_advance(Bgzf* b) {
@@ -530,8 +552,39 @@ bool dev_advance(Bgzf* b) {
   BgzfStretch& c = b->st[b->cur];
   if (c.fq.info.departed) b->parse_on = false;                  // from here on the host parser (the load below already goes its way)
   b->carry_from = c.fq.info.consumed; b->carry_len = c.fq.text_bytes - c.fq.info.consumed;
+  if (b->bam) {
+    c.base_off = b->dev_base; b->dev_base += c.fq.info.consumed;
+    if (c.fq.header_bytes > 0) b->bam_at_start = false;
+    if (c.fq.info.departed) return true;                        // a departure is the reader's error: nothing more is loaded
+  }
   if (!b->eof) { BgzfStretch* nx = &b->st[b->cur ^ 1]; b->pre_on = true; b->pre = std::thread([b, nx]() { b->pre_ok = bgzf_next_stretch(b, nx); }); }
   return true;
+}
+
+// First kept record (sl bases) of a reader's very first group: the bytes of max_reads records of this length, for ONE page-locked
+// allocation instead of a dozen grow-and-copy steps (page-locking is slow and serialised by the driver).  The three group
+// loops (device records, BAM records, text) size their first group with it; what the reader can still deliver, which caps
+// it, differs between them and stays with each.
+size_t first_group_estimate(int max_reads, int64_t max_bases, size_t sl) {
+  size_t want = (size_t)max_reads * (sl + sl / 4) + 4096;
+  if (max_bases > 0) want = std::min(want, (size_t)max_bases + sl + 4096);
+  return std::min(want, (size_t)2 << 30);
+}
+
+// ... and the other buffer sets of the reader right away, `want` bytes each: a page-lock issued later, while the GPU is busy,
+// stalls the running kernels for its whole duration (some 50 ms per 400 MiB).  Only as many sets as the `deliver` bytes the
+// reader can still yield could fill are reserved now (a 100-read input used to pin ten buffers of max_reads reads each); the
+// rest grow lazily if ever needed.  stage: the sets are the device sets of c3_reader_stage_on_device.
+int reserve_other_sets(c3_reader* r, BatchSet& s, size_t want, size_t deliver, bool stage) {
+  size_t left = deliver > want ? deliver - want : 0;
+  for (BatchSet& o : r->sets) if (&o != &s) {
+    if (left == 0) break;
+    const size_t w2 = std::min(want, left + 4096);
+    if (stage) { if (c3_bgzf_set_reserve(r->bz->dev, (int)(&o - r->sets.data()), (int64_t)w2, 0) != C3_E_OK) { r->err = c3_last_error(nullptr); return C3_E_NOMEM; } }
+    else if (!o.seqs.reserve(w2, 0) || !o.quals.reserve(w2, 0)) return C3_E_NOMEM;
+    left -= std::min(left, w2);
+  }
+  return C3_E_OK;
 }
 
 // the device parser's side of c3_reader_next_set: records of the device stretches enter the group under the group rule of the
@@ -549,6 +602,17 @@ int device_fill(c3_reader* r, BatchSet& s, int max_reads, int64_t max_bases, int
       const bool departed = c->on_dev && c->fq.info.departed;
       if (!departed && dev_advance(b)) continue;
       if (b->bad) { b->dev_active = false; break; }             // (the caller reports it)
+      if (b->bam) {
+        // BAM has no second parser: a departure, a record the end of the file cut and a file without a whole header are errors
+        c = &b->st[b->cur];
+        b->dev_active = false;
+        if (departed) return bam_fail(r, c->fq.reason, c->base_off + c->fq.bad_at);
+        if (b->bam_at_start) return bam_fail(r, C3_BAM_TRUNCATED, 0);
+        if (c->on_dev && c->fq.text_bytes > c->fq.info.consumed) return bam_fail(r, C3_BAM_TRUNCATED, c->base_off + c->fq.info.consumed);
+        c->on_dev = false; c->dend = 0; b->dpos = 0;
+        r->eof = true; r->bam_hdr = true;
+        break;
+      }
       // a departure, or the end of the file with a record the last stretch's end cut: the text from there on goes to the
       // host parser, through the buffer bgzf_read serves
       c = &b->st[b->cur];
@@ -579,21 +643,10 @@ int device_fill(c3_reader* r, BatchSet& s, int max_reads, int64_t max_bases, int
     if (!r->names_only) {
       size_t want = nb + 16;
       if (n0 == 0 && !r->hint_bases) {
-        // first kept record of the very first group: one page-locked allocation for max_reads records of this length, never
-        // more than the file can deliver, and the other sets right away (the sizing of the host loop below, for the same reasons)
-        size_t est = (size_t)max_reads * (size_t)(sl0 + sl0 / 4) + 4096;
-        if (max_bases > 0) est = std::min(est, (size_t)max_bases + (size_t)sl0 + 4096);
-        est = std::min(est, (size_t)2 << 30);
+        // first kept record of the very first group: never more than the file can deliver (compressed size: a generous bound)
         const size_t deliver = r->file_bytes ? r->file_bytes * 16 + (size_t)sl0 + 4096 : (size_t)-1;
-        want = std::max(want, std::min(est, deliver));
-        size_t left = deliver > want ? deliver - want : 0;
-        for (BatchSet& o : r->sets) if (&o != &s) {
-          if (left == 0) break;
-          const size_t w2 = std::min(want, left + 4096);
-          if (stage) { if (c3_bgzf_set_reserve(b->dev, (int)(&o - r->sets.data()), (int64_t)w2, 0) != C3_E_OK) { r->err = c3_last_error(nullptr); return C3_E_NOMEM; } }
-          else if (!o.seqs.reserve(w2, 0) || !o.quals.reserve(w2, 0)) return C3_E_NOMEM;
-          left -= std::min(left, w2);
-        }
+        want = std::max(want, std::min(first_group_estimate(max_reads, max_bases, (size_t)sl0), deliver));
+        if (reserve_other_sets(r, s, want, deliver, stage) != C3_E_OK) return C3_E_NOMEM;
       }
       if (stage) { if (c3_bgzf_set_reserve(b->dev, set, (int64_t)want, (int64_t)nb0) != C3_E_OK) { r->err = c3_last_error(nullptr); return C3_E_NOMEM; } }
       else if (!s.seqs.reserve(want, nb0) || !s.quals.reserve(want, nb0)) return C3_E_NOMEM;
@@ -645,7 +698,45 @@ extern "C" int c3_reader_next_set(c3_reader* r, int set, int max_reads, int64_t 
   // holds a record; when it holds none the call goes on as an ordinary host group, in the page-locked set
   const bool dev_group = try_dev && n > 0;
   bool size_host_set = stage_rd && !dev_group && r->hint_bases;   // ... sized like a later set, but only once the text does hold a record
-  while (!dev_group && n < max_reads && (max_bases <= 0 || (int64_t)nb < max_bases)) {
+  // a .bam file: records by the rule of c3_bam.h (what c3_bam_parse_host applies) over the bytes bgzf_read yields
+  while (r->bam && !dev_group && n < max_reads && (max_bases <= 0 || (int64_t)nb < max_bases)) {
+    if (!r->bz) return fail(r, "BAM input: not a BGZF file");
+    const uint8_t* d = (const uint8_t*)r->buf.data();
+    const int64_t at = r->buf_off + (int64_t)r->beg;                 // inflated file offset of the record
+    C3BamRec rec;
+    int st;
+    if (!r->bam_hdr) {
+      int64_t nx = 0;
+      st = c3_bam_header(d, (int64_t)r->beg, (int64_t)r->end, &nx);
+      if (st == C3_BAM_OK) { r->beg = (size_t)nx; r->bam_hdr = true; continue; }
+    } else st = r->beg == r->end ? (int)C3_BAM_INCOMPLETE : c3_bam_record(d, (int64_t)r->beg, (int64_t)r->end, &rec);
+    if (st == C3_BAM_INCOMPLETE) {
+      if (refill(r)) continue;
+      if (r->bz->bad || (r->bam_hdr && r->beg == r->end)) break;     // a damaged member (reported below), or the end of the file
+      return bam_fail(r, C3_BAM_TRUNCATED, r->bam_hdr ? at : 0);
+    }
+    if (st != C3_BAM_OK) return bam_fail(r, st, r->bam_hdr ? at : 0);
+    r->beg = (size_t)rec.next;
+    ++r->n_records;
+    const size_t sl = rec.l_seq;
+    if ((int64_t)sl < (int64_t)min_len) { ++n_short; continue; }
+    if (!s.names.reserve(nn + rec.name_len + 16, nn)) return C3_E_NOMEM;
+    memcpy(s.names.p + nn, d + rec.name, rec.name_len);
+    if (!r->names_only) {
+      size_t want = nb + sl + 16;
+      if (n == 0 && !r->hint_bases) {                                // (the sizing of the text loop below: a compressed file)
+        const size_t deliver = r->file_bytes ? r->file_bytes * 16 + sl + 4096 : (size_t)-1;
+        want = std::max(want, std::min(first_group_estimate(max_reads, max_bases, sl), deliver));
+        if (reserve_other_sets(r, s, want, deliver, false) != C3_E_OK) return C3_E_NOMEM;
+      }
+      if (!s.seqs.reserve(want, nb) || !s.quals.reserve(want, nb)) return C3_E_NOMEM;
+      char* sq = s.seqs.p + nb; char* ql = s.quals.p + nb;
+      for (size_t i = 0; i < sl; ++i) { sq[i] = (char)c3_bam_base_at(d + rec.seq, (int64_t)i); ql[i] = (char)c3_bam_qual(d[rec.qual + i]); }
+    }
+    nn += rec.name_len; nb += sl; ++n;
+    s.name_off.push_back((int64_t)nn); s.off.push_back((int64_t)nb);
+  }
+  while (!r->bam && !dev_group && n < max_reads && (max_bases <= 0 || (int64_t)nb < max_bases)) {
     if (!next_line(r, &p, &l)) break;
     if (l == 0) continue;
     if (p[0] != '>' && p[0] != '@') return fail(r, "not FASTA/FASTQ: record does not start with '>' or '@'");
@@ -687,14 +778,10 @@ extern "C" int c3_reader_next_set(c3_reader* r, int set, int max_reads, int64_t 
     ++r->n_records;
     if ((int64_t)sl < (int64_t)min_len) { ++n_short; continue; }     // dropped: buffers are simply overwritten
     if (n == 0 && !r->names_only && !r->hint_bases && sl > 0) {
-      // first kept record of the very first group: size the buffers for max_reads records of this length in ONE page-locked
-      // allocation instead of a dozen grow-and-copy steps (page-locking is slow and serialised by the driver)
-      size_t want = (size_t)max_reads * (sl + sl / 4) + 4096;
-      if (max_bases > 0) want = std::min(want, (size_t)max_bases + sl + 4096);
-      want = std::min(want, (size_t)2 << 30);
+      // first kept record of the very first group (first_group_estimate) ...
+      size_t want = first_group_estimate(max_reads, max_bases, sl);
       // ... but never more than this reader can still deliver: sequence bytes are at most half of the bytes left in its
-      // file / byte range (the other half are qualities), and only as many buffer sets as those bytes can fill are page-locked
-      // now (a 100-read input used to pin ten buffers of max_reads reads each)
+      // file / byte range (the other half are qualities)
       size_t deliver = (size_t)-1;
       if (!r->gz && !r->bz && r->file_bytes) {
         const int64_t stop = r->range_end >= 0 ? std::min<int64_t>(r->range_end + (int64_t)(4 * sl + 4096), (int64_t)r->file_bytes) : (int64_t)r->file_bytes;
@@ -703,15 +790,7 @@ extern "C" int c3_reader_next_set(c3_reader* r, int set, int max_reads, int64_t 
       } else if ((r->gz || r->bz) && r->file_bytes) deliver = r->file_bytes * 16 + sb + sl + 4096;        // (compressed size: a generous bound)
       want = std::min(want, std::max(deliver, sb + sl + 4096));
       if (!s.seqs.reserve(want, sb + sl) || !s.quals.reserve(want, sb + sl)) return C3_E_NOMEM;
-      // ... and the other buffer sets of this reader right away: a page-lock issued later, while the GPU is busy, stalls the
-      // running kernels for its whole duration (some 50 ms per 400 MiB)
-      size_t left = deliver > want ? deliver - want : 0;
-      for (BatchSet& o : r->sets) if (&o != &s) {
-        if (left == 0) break;                                              // nothing left to fill it with: grows lazily if ever needed
-        const size_t w2 = std::min(want, left + 4096);
-        if (!o.seqs.reserve(w2, 0) || !o.quals.reserve(w2, 0)) return C3_E_NOMEM;
-        left -= std::min(left, w2);
-      }
+      if (reserve_other_sets(r, s, want, deliver, false) != C3_E_OK) return C3_E_NOMEM;
     }
     nn += name_len; nb += sl; ++n;
     s.name_off.push_back((int64_t)nn); s.off.push_back((int64_t)nb);

@@ -1,13 +1,13 @@
 // c3_launch.h -- the one declaration of every kernel launcher and kernel query.  The host units call through it, and every k_*.hip
 // that defines a launcher includes it too, so a prototype that drifts from its definition fails to compile in the kernel's own
-// translation unit.  Declarations only: the argument blocks are named, not defined (c3_args.h, c3_post.h, c3_inflate.h, c3_fastq.h, c3_fasta.h, c3_emit.h, c3_fastx.h, c3_dsplit.h).
+// translation unit.  Declarations only: the argument blocks are named, not defined (c3_args.h, c3_post.h, c3_inflate.h, c3_fastq.h, c3_bam.h, c3_fasta.h, c3_emit.h, c3_fastx.h, c3_dsplit.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 struct ConkArgs; struct AdapterArgs; struct PostArgs; struct PeaksArgs; struct PoaArgs; struct PrepArgs; struct WinArgs; struct StitchArgs;
-struct ZeroArgs; struct QvArgs; struct C3BgzfMember; struct C3FqHdr; struct FaArgs; struct EmitArgs; struct FxArgs; struct DsArgs;
+struct ZeroArgs; struct QvArgs; struct C3BgzfMember; struct C3FqHdr; struct C3BamHdr; struct C3BamTile; struct FaArgs; struct EmitArgs; struct FxArgs; struct DsArgs;
 
 extern "C" {
 void c3k_launch_conk(const ConkArgs*, int, int, int, hipStream_t);                                                          // k_conk.hip
@@ -37,6 +37,10 @@ void c3k_launch_fastq_lines(const uint8_t*, uint32_t, uint32_t, const int32_t*, 
 void c3k_launch_fastq_records(const uint8_t*, uint32_t, uint32_t, const int32_t*, int, int, int, int, int32_t*, int32_t*, long long*,
                               C3FqHdr*, int64_t*, int64_t*, int4*, hipStream_t);
 void c3k_launch_fastq_gather(const uint8_t*, const int4*, const int64_t*, const int64_t*, long long, uint8_t*, uint8_t*, uint8_t*, hipStream_t);
+void c3k_launch_bam_chain(const uint8_t*, uint32_t, uint32_t, int, C3BamTile*, C3BamHdr*, hipStream_t);                          // k_bam.hip
+void c3k_launch_bam_records(const uint8_t*, uint32_t, uint32_t, const C3BamTile*, int, int, int, uint32_t*, int32_t*, int32_t*, int32_t*,
+                            int4*, long long*, C3BamHdr*, int64_t*, int64_t*, int4*, hipStream_t);
+void c3k_launch_bam_gather(const uint8_t*, const int4*, const int64_t*, const int64_t*, long long, uint8_t*, uint8_t*, uint8_t*, hipStream_t);
 void c3k_launch_fasta_count(const FaArgs*, hipStream_t);                                                                   // k_fasta.hip
 void c3k_launch_fasta_records(const FaArgs*, int, hipStream_t);
 void c3k_launch_fasta_gather(const FaArgs*, hipStream_t);

@@ -3,6 +3,7 @@
 #include "c3_host.h"
 #include "c3_bgzf.h"
 #include "c3_fastq.h"
+#include "c3_bam.h"
 #include "c3_inflate.h"
 
 // ---- BGZF output (k_bgzf.hip; host statement c3_bgzf.cpp) ---------------------------------
@@ -64,6 +65,7 @@ extern "C" void c3_bgzf_destroy(c3_bgzf* z) {
   if (z->h_res) (void)hipHostFree(z->h_res);
   if (z->copy_stream) { (void)hipStreamSynchronize(z->copy_stream); (void)hipStreamDestroy(z->copy_stream); }
   if (z->h_hdr) (void)hipHostFree(z->h_hdr);
+  if (z->h_bhdr) (void)hipHostFree(z->h_bhdr);
   for (auto& f : z->fq) { if (f.h_off) (void)hipHostFree(f.h_off); if (f.h_name_off) (void)hipHostFree(f.h_name_off); }
   delete z;
 }
@@ -224,14 +226,14 @@ static int fq_parse_device(c3_bgzf* z, c3_bgzf::FqSlot& sl, uint32_t lo, int64_t
 }
 
 // the kept records of the parse that fq_parse_device just made, gathered into sl.names / sl.seqs / sl.quals (queued, not waited for)
-static int fq_gather_device(c3_bgzf* z, c3_bgzf::FqSlot& sl, const c3_fastq_info& info) {
+static int fq_gather_device(c3_bgzf* z, c3_bgzf::FqSlot& sl, const c3_fastq_info& info, bool bam = false) {
   if (info.n_kept == 0) return C3_E_OK;
   ZCHK(sl.names.ensure((size_t)info.name_bytes + 256), "k_fastq names");
   ZCHK(sl.seqs.ensure((size_t)info.base_bytes + 256), "k_fastq bases");
   ZCHK(sl.quals.ensure((size_t)info.base_bytes + 256), "k_fastq qualities");
-  c3k_launch_fastq_gather(sl.text.as<uint8_t>(), sl.src.as<int4>(), sl.off.as<int64_t>(), sl.name_off.as<int64_t>(), (long long)info.n_kept,
-                          sl.names.as<uint8_t>(), sl.seqs.as<uint8_t>(), sl.quals.as<uint8_t>(), z->stream);
-  ZCHK(hipGetLastError(), "k_fastq_gather launch");
+  (bam ? c3k_launch_bam_gather : c3k_launch_fastq_gather)(sl.text.as<uint8_t>(), sl.src.as<int4>(), sl.off.as<int64_t>(), sl.name_off.as<int64_t>(), (long long)info.n_kept,
+                                                          sl.names.as<uint8_t>(), sl.seqs.as<uint8_t>(), sl.quals.as<uint8_t>(), z->stream);
+  ZCHK(hipGetLastError(), bam ? "k_bam_gather launch" : "k_fastq_gather launch");
   return C3_E_OK;
 }
 
@@ -263,13 +265,104 @@ extern "C" int c3_fastq_parse(c3_bgzf* z, const char* text, int64_t n, int at_eo
   return C3_E_OK;
 }
 
+// ---- Unaligned BAM records on the GPU (k_bam.hip; host statement c3_bam.cpp) ---------------
+// One parse = three waits, as for FASTQ: the chain (header status, number of record starts: sizes rec_pos[] and the record
+// tables), the header after the scans (sizes the outputs, answers the capacity question), the finished arrays.
+static int bam_prepare(c3_bgzf* z) {
+  ZCHK(hipSetDevice(z->device), "hipSetDevice");
+  if (!z->h_bhdr) ZCHK(hipHostMalloc((void**)&z->h_bhdr, sizeof(C3BamHdr), hipHostMallocDefault), "k_bam buffers");
+  if (!z->copy_stream) ZCHK(hipStreamCreateWithFlags(&z->copy_stream, hipStreamNonBlocking), "k_bam buffers");
+  ZCHK(z->d_bhdr.ensure(sizeof(C3BamHdr)), "k_bam buffers");
+  return C3_E_OK;
+}
+
+// the data [lo, lo + n) of sl.text parsed: tables and header on the device, *info filled; no byte gathered yet
+static int bam_parse_device(c3_bgzf* z, c3_bgzf::FqSlot& sl, uint32_t lo, int64_t n, int at_start, int at_eof, int min_len, c3_bam_info* info) {
+  memset(info, 0, sizeof *info);
+  sl.n_rec = 0;
+  if (n == 0) return C3_E_OK;
+  const uint32_t hi = lo + (uint32_t)n;
+  const size_t tiles = ((size_t)hi + C3_BAM_TILE - 1) / C3_BAM_TILE;
+  const uint8_t* buf = sl.text.as<uint8_t>();
+  C3BamHdr* hdr = z->d_bhdr.as<C3BamHdr>();
+  ZCHK(z->d_tiles.ensure(tiles * sizeof(C3BamTile)), "k_bam tiles");
+  c3k_launch_bam_chain(buf, lo, hi, at_start, z->d_tiles.as<C3BamTile>(), hdr, z->stream);
+  ZCHK(hipGetLastError(), "k_bam chain launch");
+  ZCHK(hipMemcpyAsync(z->h_bhdr, hdr, sizeof(C3BamHdr), hipMemcpyDeviceToHost, z->stream), "k_bam chain");
+  ZCHK(hipStreamSynchronize(z->stream), "k_bam chain");
+  {
+    const C3BamHdr& h = *z->h_bhdr;
+    if (h.hstat == C3_BAM_HEADER) { info->departed = 1; info->reason = C3_BAM_HEADER; return C3_E_OK; }
+    if (h.hstat == C3_BAM_INCOMPLETE) { if (at_eof) { info->departed = 1; info->reason = C3_BAM_TRUNCATED; } return C3_E_OK; }      // consumed = 0
+    if (h.hstat != C3_BAM_OK || h.start < (int64_t)lo || h.start > (int64_t)hi || h.n_starts < 0 || h.n_starts > n / (4 + C3_BAM_MIN_BLOCK) + 1 ||
+        (h.n_starts == 0 && h.start != (int64_t)hi)) return host_fail(C3_E_HIP, "k_bam: chain out of range");
+    info->header_bytes = at_start ? h.start - (int64_t)lo : 0;
+    if (h.n_starts == 0) { info->consumed = h.start - (int64_t)lo; return C3_E_OK; }        // the header alone
+  }
+  const int ns = (int)z->h_bhdr->n_starts;
+  const size_t nr = (size_t)ns + 1, nb = ((size_t)ns + 255) / 256;
+  ZCHK(z->d_rpos.ensure(nr * sizeof(uint32_t)), "k_bam records");
+  ZCHK(z->d_slen.ensure(nr * sizeof(int32_t)), "k_bam records");
+  ZCHK(z->d_nlen.ensure(nr * sizeof(int32_t)), "k_bam records");
+  ZCHK(z->d_reason.ensure(nr * sizeof(int32_t)), "k_bam records");
+  ZCHK(z->d_rsrc.ensure(nr * sizeof(int4)), "k_bam records");
+  ZCHK(z->d_bsum.ensure((nb + 1) * 3 * sizeof(long long)), "k_bam sums");
+  ZCHK(sl.off.ensure(nr * sizeof(int64_t)), "k_bam offsets");
+  ZCHK(sl.name_off.ensure(nr * sizeof(int64_t)), "k_bam offsets");
+  ZCHK(sl.src.ensure(nr * sizeof(int4)), "k_bam sources");
+  c3k_launch_bam_records(buf, lo, hi, z->d_tiles.as<C3BamTile>(), ns, at_eof, min_len, z->d_rpos.as<uint32_t>(), z->d_slen.as<int32_t>(),
+                         z->d_nlen.as<int32_t>(), z->d_reason.as<int32_t>(), z->d_rsrc.as<int4>(), z->d_bsum.as<long long>(), hdr,
+                         sl.off.as<int64_t>(), sl.name_off.as<int64_t>(), sl.src.as<int4>(), z->stream);
+  ZCHK(hipGetLastError(), "k_bam_records launch");
+  ZCHK(hipMemcpyAsync(z->h_bhdr, hdr, sizeof(C3BamHdr), hipMemcpyDeviceToHost, z->stream), "k_bam_records");
+  ZCHK(hipStreamSynchronize(z->stream), "k_bam_records");
+  const C3BamHdr& h = *z->h_bhdr;
+  if (h.n_records < 0 || h.n_records > ns || h.n_kept < 0 || h.n_kept > h.n_records || h.consumed < 0 || h.consumed > n ||
+      h.base_bytes < 0 || h.base_bytes > n || h.name_bytes < 0 || h.name_bytes > n || h.bad_at < 0 || h.bad_at > n ||
+      h.reason < 0 || h.reason > C3_BAM_TRUNCATED) return host_fail(C3_E_HIP, "k_bam: header out of range");
+  info->n_records = h.n_records; info->n_kept = h.n_kept; info->n_short = h.n_short; info->consumed = h.consumed;
+  info->name_bytes = h.name_bytes; info->base_bytes = h.base_bytes; info->departed = h.departed; info->reason = h.reason; info->bad_at = h.bad_at;
+  sl.n_rec = h.n_kept;
+  return C3_E_OK;
+}
+
+extern "C" int c3_bam_parse(c3_bgzf* z, const char* data, int64_t n, int at_start, int at_eof, int min_len, char* names, int64_t names_cap,
+                            int64_t* name_off, char* seqs, char* quals, int64_t bases_cap, int64_t* off, int64_t max_records,
+                            c3_bam_info* info) {
+  int rc = c3_bam_check_args("c3_bam_parse", data, n, names, names_cap, name_off, seqs, quals, bases_cap, off, max_records, info);
+  if (rc) return rc;
+  if (!z) return host_fail(C3_E_ARG, "c3_bam_parse: null handle");
+  if (n == 0) { name_off[0] = 0; off[0] = 0; return C3_E_OK; }
+  if ((rc = bam_prepare(z)) != C3_E_OK) return rc;
+  c3_bgzf::FqSlot& sl = z->fq[0];
+  const uint32_t lo = (uint32_t)((uintptr_t)data & 3u);               // the data keeps its place inside a dword: the kernels see the caller's misalignment
+  ZCHK(sl.text.ensure((size_t)lo + (size_t)n + 256), "k_bam data");
+  ZCHK(hipMemcpyAsync(sl.text.as<char>() + lo, data, (size_t)n, hipMemcpyHostToDevice, z->stream), "copy in");
+  if ((rc = bam_parse_device(z, sl, lo, n, at_start, at_eof, min_len, info)) != C3_E_OK) return rc;
+  if (info->n_kept > max_records || info->name_bytes > names_cap || info->base_bytes > bases_cap) {
+    return host_fail(C3_E_LIMIT, "c3_bam_parse: capacity too small (needed sizes in info)");
+  }
+  if (info->n_kept == 0) { name_off[0] = 0; off[0] = 0; return C3_E_OK; }
+  c3_fastq_info fi; memset(&fi, 0, sizeof fi);
+  fi.n_kept = info->n_kept; fi.name_bytes = info->name_bytes; fi.base_bytes = info->base_bytes;
+  if ((rc = fq_gather_device(z, sl, fi, true)) != C3_E_OK) return rc;
+  const size_t nt = ((size_t)info->n_kept + 1) * sizeof(int64_t);
+  ZCHK(hipMemcpyAsync(off, sl.off.p, nt, hipMemcpyDeviceToHost, z->stream), "k_bam_gather");
+  ZCHK(hipMemcpyAsync(name_off, sl.name_off.p, nt, hipMemcpyDeviceToHost, z->stream), "k_bam_gather");
+  if (info->name_bytes) ZCHK(hipMemcpyAsync(names, sl.names.p, (size_t)info->name_bytes, hipMemcpyDeviceToHost, z->stream), "k_bam_gather");
+  ZCHK(hipMemcpyAsync(seqs, sl.seqs.p, (size_t)info->base_bytes, hipMemcpyDeviceToHost, z->stream), "k_bam_gather");
+  ZCHK(hipMemcpyAsync(quals, sl.quals.p, (size_t)info->base_bytes, hipMemcpyDeviceToHost, z->stream), "k_bam_gather");
+  ZCHK(hipStreamSynchronize(z->stream), "k_bam_gather");
+  return C3_E_OK;
+}
+
 // ---- the reader's device stretches (c3_io.cpp; not part of the public interface) ----------
 // Stretch = `carry_len` bytes of the other slot's text from `carry_from` on (the record its end cut), then the inflated
 // members of comp; it stays on the device, is parsed there with min_len 0 (the group rule, min_len included, is the
 // reader's), and the record tables come back (c3_fq_stretch, c3_checks.h).  On return the slot holds the finished records
 // until it is loaded again.
-extern "C" int c3_bgzf_stretch_parse(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, int64_t carry_from, int64_t carry_len,
-                                     int at_eof, c3_fq_stretch* out) {
+static int stretch_parse(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, int64_t carry_from, int64_t carry_len,
+                         bool bam, int at_start, int at_eof, c3_fq_stretch* out) {
   if (!z || !out || slot < 0 || slot > 1 || ncomp < 0 || (ncomp > 0 && !comp) || carry_len < 0) return host_fail(C3_E_ARG, "c3_bgzf_stretch_parse: bad arguments");
   memset(out, 0, sizeof *out);
   int64_t nm = 0, ob = 0;
@@ -277,7 +370,7 @@ extern "C" int c3_bgzf_stretch_parse(c3_bgzf* z, int slot, const char* comp, int
   if (rc) return rc;
   const int64_t total = carry_len + ob;
   if (total > C3_FASTQ_MAX_TEXT) return host_fail(C3_E_LIMIT, "c3_bgzf_stretch_parse: stretch longer than C3_FASTQ_MAX_TEXT");
-  if ((rc = fq_prepare(z)) != C3_E_OK) return rc;
+  if ((rc = bam ? bam_prepare(z) : fq_prepare(z)) != C3_E_OK) return rc;
   c3_bgzf::FqSlot& sl = z->fq[slot];
   const c3_bgzf::FqSlot& other = z->fq[slot ^ 1];
   if (carry_len > 0 && (carry_from < 0 || carry_from + carry_len > other.text_n)) return host_fail(C3_E_ARG, "c3_bgzf_stretch_parse: carry outside the other stretch");
@@ -292,10 +385,16 @@ extern "C" int c3_bgzf_stretch_parse(c3_bgzf* z, int slot, const char* comp, int
   }
   sl.text_n = total;
   out->text_bytes = total;
-  if ((rc = fq_parse_device(z, sl, 0, total, at_eof, 0, &out->info)) != C3_E_OK) return rc;
+  if (bam) {
+    c3_bam_info bi;
+    if ((rc = bam_parse_device(z, sl, 0, total, at_start, at_eof, 0, &bi)) != C3_E_OK) return rc;
+    out->info.n_records = bi.n_records; out->info.n_kept = bi.n_kept; out->info.n_short = bi.n_short; out->info.consumed = bi.consumed;
+    out->info.name_bytes = bi.name_bytes; out->info.base_bytes = bi.base_bytes; out->info.departed = bi.departed;
+    out->reason = bi.reason; out->bad_at = bi.bad_at; out->header_bytes = bi.header_bytes;
+  } else if ((rc = fq_parse_device(z, sl, 0, total, at_eof, 0, &out->info)) != C3_E_OK) return rc;
   const int64_t nk = out->info.n_kept;
   if (nk > 0) {
-    if ((rc = fq_gather_device(z, sl, out->info)) != C3_E_OK) return rc;
+    if ((rc = fq_gather_device(z, sl, out->info, bam)) != C3_E_OK) return rc;
     if (sl.h_cap < (size_t)nk + 1) {
       if (sl.h_off) (void)hipHostFree(sl.h_off);
       if (sl.h_name_off) (void)hipHostFree(sl.h_name_off);
@@ -313,6 +412,17 @@ extern "C" int c3_bgzf_stretch_parse(c3_bgzf* z, int slot, const char* comp, int
     out->off = sl.h_off; out->name_off = sl.h_name_off;
   }
   return C3_E_OK;
+}
+
+extern "C" int c3_bgzf_stretch_parse(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, int64_t carry_from, int64_t carry_len,
+                                     int at_eof, c3_fq_stretch* out) {
+  return stretch_parse(z, slot, comp, ncomp, carry_from, carry_len, false, 0, at_eof, out);
+}
+// the inflated bytes of a BAM file: the same carry rule (a file header that is not whole yet is carried like a cut record:
+// consumed = 0), the same slot arrays and tables, k_bam in place of k_fastq
+extern "C" int c3_bgzf_stretch_parse_bam(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, int64_t carry_from, int64_t carry_len,
+                                         int at_start, int at_eof, c3_fq_stretch* out) {
+  return stretch_parse(z, slot, comp, ncomp, carry_from, carry_len, true, at_start, at_eof, out);
 }
 
 // records [r0, r1) of the slot's stretch copied to the host (names / seqs / quals point at the place of record r0; seqs and

@@ -89,6 +89,10 @@ def ensure_psl(blat, args, tmp_dir):
         print("Assigning splints to reads on the GPU", file=sys.stderr)
         gpu_find_splints(args, align_psl)
     elif not os.path.exists(align_psl) or os.stat(align_psl).st_size == 0:
+        if str(args.reads).endswith(".bam"):
+            # blat takes FASTA, written here from the reads by the text reader, which does not read BAM
+            raise RuntimeError("--splint-finder blat reads FASTQ only, not %r: use --splint-finder gpu, or convert the file with "
+                               "samtools fastq" % str(args.reads))
         if shutil.which(blat) is None:
             raise RuntimeError("no %s and no blat binary (%r); use --splint-finder gpu" % (align_psl, blat))
         print("Aligning splints to reads with blat", file=sys.stderr)

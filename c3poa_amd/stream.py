@@ -131,7 +131,7 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
     # <splint>/tmp<k>/ directories in glob order -- the reference's record order is arbitrary as well; here it is the
     # round-robin order of the ranges, and the file order itself with a single range).
     size = os.path.getsize(args.reads)
-    splittable = not str(args.reads).endswith(".gz") and size > 0
+    splittable = not str(args.reads).endswith((".gz", ".bam")) and size > 0      # (BGZF, BAM included, cannot be entered in the middle)
     per_gpu = max(1, int(os.environ.get("C3_READERS_PER_GPU", READERS_PER_GPU)))
     min_range = int(os.environ.get("C3_MIN_RANGE_BYTES", MIN_RANGE_BYTES))
     n_ranges = max(1, min(n_work * per_gpu, size // max(min_range, 1))) if splittable else 1
@@ -151,13 +151,13 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
             dev = dmap[dev % len(dmap)]
         return dev
 
-    # --inflate gpu: the (single, whole-file) reader of a .gz input inflates its BGZF stretches with k_inflate on worker 0's
-    # device instead of zlib threads; any other gzip file has no member sizes to split on and is read as before
+    # --inflate gpu: the (single, whole-file) reader of a .gz or .bam input inflates its BGZF stretches with k_inflate on worker
+    # 0's device instead of zlib threads; any other gzip file has no member sizes to split on and is read as before
     inflate_dev, parse_dev = None, False
-    if getattr(args, "inflate", "host") == "gpu" and str(args.reads).endswith(".gz"):
+    if getattr(args, "inflate", "host") == "gpu" and str(args.reads).endswith((".gz", ".bam")):
         if _is_bgzf(args.reads):
             inflate_dev = worker_device(0)
-            # --parse gpu: ... and its records are found there too (k_fastq); only the finished arrays come to the host
+            # --parse gpu: ... and its records are found there too (k_fastq; k_bam for a .bam); only the finished arrays come to the host
             parse_dev = getattr(args, "parse", "host") == "gpu"
         else:
             print("C3POa: --inflate gpu: %s is gzip but not BGZF (no member size in front); only BGZF can be inflated on the GPU, the file is read as before" % args.reads, file=sys.stderr)

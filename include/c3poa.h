@@ -499,6 +499,58 @@ int c3_reader_parse_on_device(c3_reader* r, int on);
  * were counted short) from the device: proof that the device path ran and nothing fell back silently */
 int c3_reader_parse_stats(const c3_reader* r, int64_t* stretches_device, int64_t* stretches_host, int64_t* records_device);
 
+/* ---- Unaligned BAM records on the GPU (-r reads.bam) ----
+ * The inflated bytes of a BAM file: the file header (magic "BAM\1", l_text, the text, n_ref, per reference l_name, name, l_ref;
+ * skipped, not interpreted; a wrong magic, a negative length or n_ref > C3_BAM_MAX_REFS is a departure, reason HEADER; a
+ * header whose n_ref exceeds an eighth of the bytes behind it cannot end inside the data and is incomplete), then records.  All fields are
+ * little-endian.  The record at byte p: block_size (u32) at +0, l_read_name (u8) at +12, n_cigar_op (u16) at +16, flag (u16)
+ * at +18, l_seq (u32) at +20, read_name at +36, then 4 * n_cigar_op cigar bytes, (l_seq + 1) / 2 packed bases, l_seq
+ * qualities, and tags up to p + 4 + block_size, where the next record begins (the rule is c3poa_amd/csrc/c3_bam.h).
+ * A record is STRICT when none of these holds; they are tested in this order and the first that holds is the reason (the
+ * values of c3_bam_info.reason, 0 = none):
+ *   1 BLOCK   block_size outside [34, C3_BAM_MAX_RECORD]
+ *   2 NAME    l_read_name == 0, or read_name[l_read_name - 1] != 0 (looked at where that byte lies inside the record)
+ *   3 FIELDS  32 + l_read_name + 4 * n_cigar_op + (l_seq + 1) / 2 + l_seq > block_size (in 64 bits)
+ *   4 FLAG    flag & (0x10 | 0x100 | 0x800): a reverse-strand, secondary or supplementary record; such a file is aligned
+ *             (convert it with samtools fastq)
+ *   5 EMPTY   l_seq == 0
+ *   6 NOQUAL  qual[0] == 0xFF
+ * n_cigar_op > 0 and every other flag bit are accepted and ignored; tags are skipped.  Delivered: the name = read_name up to
+ * the first NUL, blank or tab (the cut of the FASTQ rule); the bases "=ACMGRSVTWYHKDBN"[code], high nibble first; the
+ * qualities min(q, 93) + 33.
+ * The call parses the longest prefix of whole strict records: info->consumed is its byte length.  With at_start != 0 the
+ * data begins with the file header, which is consumed first and reported in header_bytes; a header that is merely incomplete
+ * gives consumed = 0 and is no error.  A record that does not end inside the data is left unconsumed; that is no error
+ * unless at_eof != 0, which makes it (and an incomplete header) a departure with reason 7, TRUNCATED.  The first record that
+ * is not strict is a DEPARTURE: parsing stops in front of it, consumed ends there, departed = 1, reason and bad_at (its byte
+ * offset in data) are set, and the records before it are delivered as usual (reason 8, HEADER: bad_at = 0, nothing
+ * delivered).  Records with fewer than min_len bases are counted in n_short and not stored; n_records = n_kept + n_short.
+ * names / name_off[n_kept + 1], seqs / quals / off[n_kept + 1] of the kept records mean what they mean in c3_host_batch.
+ * c3_bam_parse runs k_bam on the device of a c3_bgzf; c3_bam_parse_host is its host statement.  n_kept > max_records,
+ * name_bytes > names_cap or base_bytes > bases_cap return C3_E_LIMIT with the needed sizes in info and nothing written to
+ * the arrays; n > C3_FASTQ_MAX_TEXT returns C3_E_LIMIT (positions are 32-bit on the device); null arguments and a null handle
+ * return C3_E_ARG before anything is launched (data may be null when n == 0); n == 0 is success with all counts zero.
+ * Errors through c3_last_error(NULL).
+ * The reader: c3_reader_open / c3_reader_open_inflate on a path ending in ".bam" read it as BGZF (C3_NO_BGZF is not looked at;
+ * a .bam that is not BGZF fails at the first c3_reader_next with a text) and form the groups of the group rule from these
+ * records; c3_reader_parse_on_device and c3_reader_stage_on_device are valid on such a reader (k_bam in place of k_fastq).
+ * A departure is an error of c3_reader_next on either path, BAM has no second parser: the c3_reader_error text names the
+ * record's index, its inflated byte offset and the reason.  The call that meets it returns the error at once: the groups of
+ * the earlier calls were delivered, the records that this call had collected in front of the departure are not (unlike
+ * c3_bam_parse, which delivers the records before it).  c3_reader_noqual stays 0; c3_reader_open_range refuses ".bam"
+ * with C3_E_ARG. */
+#define C3_BAM_TILE 65536            /* bytes of data per chain tile on the device (the tests place records against it) */
+#define C3_BAM_MAX_RECORD (1 << 28)
+#define C3_BAM_MAX_REFS (1 << 20)    /* references in the file header (an unaligned BAM has none) */
+typedef struct { int64_t n_records, n_kept, n_short, consumed, name_bytes, base_bytes, header_bytes, bad_at;
+                 int32_t departed, reason; } c3_bam_info;
+int c3_bam_parse(c3_bgzf* z, const char* data, int64_t n, int at_start, int at_eof, int min_len,
+                 char* names, int64_t names_cap, int64_t* name_off, char* seqs, char* quals, int64_t bases_cap,
+                 int64_t* off, int64_t max_records, c3_bam_info* info);
+int c3_bam_parse_host(const char* data, int64_t n, int at_start, int at_eof, int min_len,
+                      char* names, int64_t names_cap, int64_t* name_off, char* seqs, char* quals, int64_t bases_cap,
+                      int64_t* off, int64_t max_records, c3_bam_info* info);
+
 /* ---- Post-processing on the GPU (C3POa_postprocessing.py --emit gpu) ----
  * One batch of consensus reads and its adapter table in, finished file bytes out: classification (parse_blat), trimming,
  * orientation, oligo-dT demultiplexing and record formatting of write_fasta_file (C3POa_postprocessing.py:238-398), and the

@@ -30,7 +30,13 @@ struct c3_fq_stretch;
 int c3_bgzf_stretch_parse(c3_bgzf*, int, const char*, int64_t, int64_t, int64_t, int, c3_fq_stretch*) { return C3_E_NO_DEVICE; }
 int c3_bgzf_stretch_fetch(c3_bgzf*, int, int64_t, int64_t, char*, char*, char*) { return C3_E_NO_DEVICE; }
 int c3_bgzf_stretch_text(c3_bgzf*, int, int64_t, int64_t, char*) { return C3_E_NO_DEVICE; }
+int c3_bgzf_stretch_parse_bam(c3_bgzf*, int, const char*, int64_t, int64_t, int64_t, int, int, c3_fq_stretch*) { return C3_E_NO_DEVICE; }
+int c3_bgzf_sets_create(c3_bgzf*, int) { return C3_E_NO_DEVICE; }
+int c3_bgzf_set_reserve(c3_bgzf*, int, int64_t, int64_t) { return C3_E_NO_DEVICE; }
+int c3_bgzf_stretch_stage(c3_bgzf*, int, int64_t, int64_t, char*, int, int64_t) { return C3_E_NO_DEVICE; }
+int c3_bgzf_set_get(const c3_bgzf*, int, const char**, const char**, int*) { return C3_E_NO_DEVICE; }
 }
+const char* c3_bam_reason_text(int) { return ""; }                // (c3_bam.cpp in the real build)
 
 template <class T> static T* exact(const std::vector<T>& v) {  // a heap block of exactly v.size() elements (never null)
   T* p = (T*)malloc(v.size() * sizeof(T) + (v.empty() ? 1 : 0));
