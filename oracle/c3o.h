@@ -138,6 +138,9 @@ int c3o_determine_consensus(const char* const* subs, const char* const* quals,
  * returns the stitched length (0 = no rescue). */
 int c3o_zero_repeats(const char* d0, const char* q0, int n0, const char* d1, const char* q1, int n1,
                      const c3o_params* P, char* out, int cap, int64_t* cells);
+/* the overlap alignment of the rescue alone: out[5] = score, r_st, r_en, q_st, q_en; returns the score.
+ * Neither zr_max_cells nor zr_min_score is applied. */
+int c3o_zero_local(const char* d0, int n0, const char* d1, int n1, const c3o_params* P, int32_t* out);
 
 /* adapter finder of the post-processing step (C3POa_postprocessing.py:229-264): out[12] = score, qStart, qEnd, tStart,
  * tEnd, matches, misMatches, qBaseInsert, tBaseInsert, qNumInsert, tNumInsert, read length.  rc = 1: strand '-'. */

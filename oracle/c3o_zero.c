@@ -118,3 +118,20 @@ int c3o_zero_repeats(const char* d0, const char* q0, int n0, const char* d1, con
   c3o_leave();
   return r;
 }
+
+/* the alignment alone, for tests: out[5] = score, r_st, r_en, q_st, q_en (all 0 but the score when nothing scores);
+ * no cell cap and no acceptance threshold: the caller applies zr_min_score */
+int c3o_zero_local(const char* d0, int n0, const char* d1, int n1, const c3o_params* P, int32_t* out) {
+  for (int k = 0; k < 5; ++k) out[k] = 0;
+  if (n0 <= 0 || n1 <= 0) return 0;
+  c3o_enter();
+  uint8_t* c0 = (uint8_t*)malloc((size_t)n0 + 1); uint8_t* c1 = (uint8_t*)malloc((size_t)n1 + 1);
+  for (int i = 0; i < n0; ++i) c0[i] = (uint8_t)c3o_code(d0[i]);
+  for (int i = 0; i < n1; ++i) c1[i] = (uint8_t)c3o_code(d1[i]);
+  int r_st = 0, r_en = 0, q_st = 0, q_en = 0; int64_t cells = 0;
+  out[0] = zr_local(c0, n0, c1, n1, P, &r_st, &r_en, &q_st, &q_en, &cells);
+  out[1] = r_st; out[2] = r_en; out[3] = q_st; out[4] = q_en;
+  free(c0); free(c1);
+  c3o_leave();
+  return out[0];
+}

@@ -232,6 +232,16 @@ def pairwise_consensus(msa_rows, subreads, quals):
     return out.raw[:n].decode()
 
 
+def zero_local(d0, d1, params=None):
+    """the overlap alignment of the zero-repeat rescue alone: (score, r_st, r_en, q_st, q_en), d0 = columns, d1 = rows;
+    zr_min_score and zr_max_cells are not applied"""
+    P = params or default_params()
+    b0, b1 = _b(d0), _b(d1)
+    out = np.zeros(5, dtype=np.int32)
+    lib().c3o_zero_local(b0, len(b0), b1, len(b1), C.byref(P), out.ctypes.data_as(C.c_void_p))
+    return tuple(int(v) for v in out)
+
+
 def determine_consensus(subs, quals, front=None, tail=None, params=None, return_draft=False):
     """front/tail: (seq, qual) or None"""
     P = params or default_params()
