@@ -14,6 +14,8 @@ struct C3Counters {
   unsigned long long zero_cells;        // k_zero / k_zero_long: overlap cells of the zero-repeat rescue
   int poa_ovf;                          // k_poa: reads whose scratch overflowed (list PoaArgs::overflow)
   int poa_ovf16;                        // k_poa: reads with a score beyond the 16-bit cells (list PoaArgs::overflow16)
+  int pair_queue;                       // k_poa_pair: work queue
+  int n_pair, n_pair_declined;          // k_poa_pair: reads it aligned and flagged / reads with >= 2 subreads it declined (k_poa aligns those)
   int n_windows;                        // k_prep: windows reserved (may exceed PrepArgs::wcap)
   int win_ovf;                          // first k_window launch: windows queued for the second one (WinArgs::ovf_list)
   int win_queue2;                       // second k_window launch: work queue
@@ -47,6 +49,17 @@ struct PoaArgs {
   int* pbase;               // [slots][Pcap] node of every fused base
   int* overflow;            // reads whose scratch overflowed (count in cnt->poa_ovf): redone with worst-case scratch; nullptr in the passes that have it
   int* overflow16;          // reads with a score beyond the 16-bit cells (count in cnt->poa_ovf16): redone by the 32-bit instance; nullptr in that pass
+  // what k_poa_pair left (PoaPairArgs); nullptr in every pass but the first DEF, NARROW, 16-bit one: those recompute
+  const uint8_t* pair_done; const uint16_t* pair_vq; const int* pair_cells;
+};
+// k_poa_pair (k_poa_pair.hip): subread 1 against the chain of subread 0, ahead of the first k_poa pass, in that pass's slots
+struct PoaPairArgs {
+  C3Batch b; const C3Info* info; C3Params p; C3Counters* cnt; const int* work; int n_work;
+  int* ibase; char* cellsb;             // k_poa's per-slot int block (row records go to its rowm) and cell arena (direction bytes, 128 per row)
+  size_t dstride; int dbytes;           // bytes between the arenas of two slots / usable bytes of one
+  int Ncap, cells_cap, rb_span;         // as in PoaArgs: a read k_poa's slot would be too small for is declined
+  uint16_t* vq;                         // per base of the batch (at off[rid] + sub_beg[1] + q): node aligned to base q of subread 1, 0xffff = insertion
+  int* cells; uint8_t* done;            // per read: counted cells / 1 = vq and cells are valid (zeroed by the host per batch)
 };
 // k_poa scratch of one slot, bytes per region (each region is one buffer strided by slot):
 //   ints  C3_POA_NI * Ncap ints (n_in n_out grp order order2 index gfirst glast rem mpl mpr rowm[3N] anchor col col2t nxt foff)
@@ -55,6 +68,11 @@ struct PoaArgs {
 //         that keep them): cells_cap >> far_shift far cells, a quarter in the 16-bit instance, all of them in the 32-bit one
 //   bases 5 * Ncap bytes (base rows2[4N]); score Ncap long longs; desc 2 * Ncap uint4; jump C3_JUMP_LEVELS * Ncap ints; path Pcap ints
 #define C3_POA_NI 19
+#define C3_POA_I_ROWM 11              // block of rowm in the int region (3 blocks: 11..13); k_poa's Ctx and k_poa_pair's row records use it
+// abPOA's default scoring with match 5: what the DEF instances of k_poa and k_poa_pair are compiled for
+__host__ __device__ inline bool c3_poa_default_scoring(const C3Params& p) {
+  return p.poa_match == 5 && p.poa_mismatch == 4 && p.o1 == 4 && p.e1 == 2 && p.o2 == 24 && p.e2 == 1;
+}
 __host__ __device__ inline int c3_poa_far_shift(bool w32) { return w32 ? 0 : 2; }
 struct PoaLayout { size_t ints, edges, cells, bases, score, desc, jump, path, total; };
 __host__ __device__ inline PoaLayout c3_poa_layout(size_t Ncap, size_t K, int cells_cap, int far_shift, size_t Pcap) {

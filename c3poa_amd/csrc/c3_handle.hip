@@ -221,7 +221,7 @@ extern "C" void c3_destroy(c3_handle* h) {
   (void)hipSetDevice(h->cfg.device);
   for (hipStream_t s : {h->stream, h->stream_up, h->stream_dn}) if (s) (void)hipStreamSynchronize(s);
   for (hipStream_t s : {h->stream, h->stream_up, h->stream_dn}) if (s) (void)hipStreamDestroy(s);
-  for (hipEvent_t ev : {h->ev_dn, h->ev_up[0], h->ev_up[1], h->ev_qv[0], h->ev_qv[1]}) if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : {h->ev_dn, h->ev_up[0], h->ev_up[1], h->ev_qv[0], h->ev_qv[1], h->ev_pair[0], h->ev_pair[1]}) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : h->ev) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : h->ev_post) if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : h->ev_fa) if (ev) (void)hipEventDestroy(ev);

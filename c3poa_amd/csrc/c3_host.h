@@ -178,6 +178,9 @@ struct c3_handle {
   DBuf s_poa_i, s_poa_nk, s_poa_cells, s_poa_b, s_poa_sc, s_poa_desc, s_poa_jump, s_poa_path, d_overflow;      // POA scratch
   int n_poa_redo = 0;        // reads of the last run that needed the full-size second POA pass
   int n_poa_redo16 = 0;      // ... of them: because a score left the 16-bit cells
+  // k_poa_pair: vq of subread 1 (16 bits per base of the batch), counted cells and done flag per read; its event pair and counters.
+  // vq has a buffer of its own: d_tpos is the only per-base array of that size, and its -1 of failed reads is read later
+  DBuf d_pair_vq, d_pair_cells, d_pair_done; hipEvent_t ev_pair[2] = {nullptr, nullptr}; bool pair_ran = false; int n_pair = 0, n_pair_declined = 0;
   DBuf s_eD, s_lw, d_wrec, d_wlay, d_wbase, d_wout;       // prep / windows
   DBuf s_win_i, s_win_nk, s_win_h, s_win_d, s_win_b, s_win_sc, s_win_desc, s_win_h2, s_win_d2, d_wovf;
   DBuf s_zero_d, d_zinfo, d_zflag, d_zwork; std::vector<int> zwork;  // zero-repeat rescue: k_zero direction bytes, per-read records, work list

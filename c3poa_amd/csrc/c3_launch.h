@@ -6,7 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-struct ConkArgs; struct AdapterArgs; struct PostArgs; struct PeaksArgs; struct PoaArgs; struct PrepArgs; struct WinArgs; struct StitchArgs;
+struct ConkArgs; struct AdapterArgs; struct PostArgs; struct PeaksArgs; struct PoaArgs; struct PoaPairArgs; struct PrepArgs; struct WinArgs; struct StitchArgs;
 struct ZeroArgs; struct QvArgs; struct C3BgzfMember; struct C3FqHdr; struct C3BamHdr; struct C3BamTile; struct FaArgs; struct EmitArgs; struct FxArgs; struct DsArgs;
 
 extern "C" {
@@ -15,6 +15,7 @@ void c3k_launch_adapter(const AdapterArgs*, int, hipStream_t);                  
 void c3k_launch_match_index(const char*, const int*, int, int, const char*, const long long*, int*, hipStream_t);
 void c3k_launch_pairwise(const uint8_t*, int, const uint8_t*, int, const uint8_t*, int, uint8_t*, uint8_t*, int*, hipStream_t);   // k_poa.hip
 void c3k_launch_poa(const PoaArgs*, int, int, int, hipStream_t);
+void c3k_launch_poa_pair(const PoaPairArgs*, int, hipStream_t);                                                             // k_poa_pair.hip
 void c3k_launch_post_classify(const PostArgs*, hipStream_t);                                                                // k_post.hip
 void c3k_launch_post_scan(const PostArgs*, hipStream_t);
 void c3k_launch_post_emit(const PostArgs*, hipStream_t);

@@ -202,7 +202,7 @@ static int fetch_summary(c3_handle* h) {
 }
 
 // one launch of k_poa over `nw` reads of `d_work` with the given capacities
-static int launch_poa(c3_handle* h, const int* d_work, int nw, int Ncap, int K, int Pcap, long long cells, int* d_overflow, int* d_overflow16, int waves_per_cu, int wide_ring) {
+static int launch_poa(c3_handle* h, const int* d_work, int nw, int Ncap, int K, int Pcap, long long cells, int* d_overflow, int* d_overflow16, int waves_per_cu, int wide_ring, bool first_pass = false) {
   cells = (cells + 15) & ~15LL;                   // every per-slot arena starts 16-byte aligned
   cells = (cells + 63) & ~63LL;
   // far arena (32-bit cells of rows with a successor beyond the LDS ring, rows wider than a ring slot, rows with > 4 predecessors):
@@ -227,6 +227,28 @@ static int launch_poa(c3_handle* h, const int* d_work, int nw, int Ncap, int K, 
   a.msa_dbg = nullptr; a.msa_off = nullptr; a.msa_len = nullptr;
   if (h->debug_msa) { a.msa_dbg = h->d_msa.as<uint8_t>(); a.msa_off = h->d_msa_off.as<int64_t>(); a.msa_len = h->d_msa_len.as<int>(); }
   DBG("poa: nw=%d Ncap=%d K=%d cells=%lld slots=%d (%.1f MB per slot)%s\n", nw, Ncap, K, cells, slots, L.total / 1048576.0, d_overflow ? "" : (d_overflow16 ? " [full-size pass]" : " [32-bit pass]"));
+  // k_poa_pair ahead of the first pass when that pass is the default-scoring, NARROW, 16-bit instance: it aligns subread 1 to the
+  // chain of subread 0 in this pass's slots and leaves vq, cells and a flag per read (C3_DEBUG_POA_PAIR=0: test hook, not launched);
+  // every other pass gets null pointers and recomputes
+  const bool def = c3_poa_default_scoring(a.p);
+  const char* pe = getenv("C3_DEBUG_POA_PAIR");
+  if (first_pass && def && !w32 && !wide_ring && !(pe && atoi(pe) == 0)) {
+    HIPCHK(h->d_pair_vq.ensure(sizeof(uint16_t) * (size_t)h->total + 64)); HIPCHK(h->d_pair_cells.ensure(sizeof(int) * (size_t)h->n));
+    HIPCHK(h->d_pair_done.ensure((size_t)h->n));
+    for (int i = 0; i < 2; ++i) if (!h->ev_pair[i]) HIPCHK(hipEventCreate(&h->ev_pair[i]));
+    HIPCHK(hipMemsetAsync(h->d_pair_done.p, 0, (size_t)h->n, h->stream));
+    PoaPairArgs q; memset(&q, 0, sizeof(q));
+    q.b = a.b; q.info = a.info; q.p = a.p; q.cnt = a.cnt; q.work = d_work; q.n_work = nw;
+    q.ibase = a.ibase; q.cellsb = a.cellsb; q.dstride = L.cells; q.dbytes = (int)std::min<size_t>(L.cells, (size_t)1 << 30);
+    q.Ncap = Ncap; q.cells_cap = (int)cells; q.rb_span = a.rb_span;
+    q.vq = h->d_pair_vq.as<uint16_t>(); q.cells = h->d_pair_cells.as<int>(); q.done = h->d_pair_done.as<uint8_t>();
+    HIPCHK(hipEventRecord(h->ev_pair[0], h->stream));
+    c3k_launch_poa_pair(&q, slots, h->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev_pair[1], h->stream));
+    a.pair_done = q.done; a.pair_vq = q.vq; a.pair_cells = q.cells;
+    h->pair_ran = true;
+  }
   // the pass with an overflow list runs the 16-bit rows; the final pass (no list) the 32-bit rows only (C3_DEBUG_POA32: test hook, first pass too)
   c3k_launch_poa(&a, slots, w32 ? 1 : 0, wide_ring, h->stream);
   HIPCHK(hipGetLastError());
@@ -268,6 +290,8 @@ static int run_poa(c3_handle* h) {
   C3Counters* dc = dev_cnt(h);        // (zero_cells of run_zero stay: tm.cells_poa counts them)
   HIPCHK(zero_cnt(h, &dc->queue)); HIPCHK(zero_cnt(h, &dc->cells)); HIPCHK(zero_cnt(h, &dc->poa_ovf)); HIPCHK(zero_cnt(h, &dc->poa_ovf16));
   HIPCHK(zero_cnt(h, &dc->phases));
+  HIPCHK(zero_cnt(h, &dc->pair_queue)); HIPCHK(zero_cnt(h, &dc->n_pair)); HIPCHK(zero_cnt(h, &dc->n_pair_declined));
+  h->pair_ran = false; h->n_pair = 0; h->n_pair_declined = 0;
   // ring geometry of the first pass: subreads beyond the LDS query copy (1792 bases) or with bands beyond two 64-column chunks
   // (w = band_b + band_f * Q; a row holds 2w+1 columns + the drift of its predecessors' maxima) take the WIDE instance
   // (4 ring rows of 192 cells, sliding query window); C3_DEBUG_POA_WIDE = 0 / 1 forces one (test hook)
@@ -276,11 +300,12 @@ static int run_poa(c3_handle* h) {
   // pass 1: scratch for the typical alignment.  Its two lists: reads the scratch was too small for -> pass 2 (the same kernel, worst-case
   // scratch); reads with a score beyond the 16-bit cells (from either pass) -> pass 3 (the 32-bit instance, worst-case scratch)
   int* ovA = h->d_overflow.as<int>(); int* ovB = h->d_overflow.as<int>() + nw;
-  int rc = launch_poa(h, h->d_work.as<int>(), nw, Ncap, K, Pcap, cells, ovA, ovB, 24, wide_ring);
+  int rc = launch_poa(h, h->d_work.as<int>(), nw, Ncap, K, Pcap, cells, ovA, ovB, 24, wide_ring, true);
   if (rc) return rc;
   h->n_poa_redo = 0; h->n_poa_redo16 = 0;
   C3Counters c;
   HIPCHK(read_counters(h, &c));
+  h->n_pair = c.n_pair; h->n_pair_declined = c.n_pair_declined;
   if (c.poa_ovf > 0) {
     h->n_poa_redo = c.poa_ovf;
     HIPCHK(zero_cnt(h, &dc->queue));
@@ -506,7 +531,7 @@ extern "C" int c3_batch_run(c3_handle* h, int stages) {
   // per-run figures start from zero: repeated runs of one resident batch (bench.py, tools/) must not accumulate
   if (stages & C3_STAGE_CONK) { h->tm.ms_conk = 0; h->tm.cells_conk = 0; }
   if (stages & C3_STAGE_PEAKS) h->tm.ms_peaks = 0;
-  if (stages & C3_STAGE_POA) { h->tm.ms_poa = 0; h->tm.cells_poa = 0; }
+  if (stages & C3_STAGE_POA) { h->tm.ms_poa = 0; h->tm.cells_poa = 0; h->tm.ms_poa_pair = 0; h->tm.n_pair = h->tm.n_pair_declined = 0; h->pair_ran = false; h->n_pair = h->n_pair_declined = 0; }
   if (stages & C3_STAGE_POLISH) { h->tm.ms_prep = h->tm.ms_window = h->tm.ms_stitch = 0; h->tm.cells_polish = 0; h->tm.cells_polish_computed = 0; h->tm.n_band_layers = h->tm.n_band_fallback = h->tm.n_band_mismatch = 0; h->tm.n_windows = 0; h->tm.n_win_redo = 0; }
   HIPCHK(hipEventRecord(t0, h->stream));
   if (stages & C3_STAGE_CONK) { if ((rc = run_conk(h))) return rc; h->tm.cells_conk = 0; for (int i = 0; i < h->n; ++i) h->tm.cells_conk += (h->off[i + 1] - h->off[i]) * (int64_t)h->max_spl; }
@@ -528,6 +553,8 @@ extern "C" int c3_batch_run(c3_handle* h, int stages) {
       HIPCHK(read_counters(h, &c));
       if (!h->work.empty()) h->tm.cells_poa = (int64_t)(c.zero_cells + c.cells);      // zero-repeat overlaps + POA
       h->tm.n_poa_redo = h->n_poa_redo; h->tm.n_poa_redo16 = h->n_poa_redo16;
+      h->tm.n_pair = h->n_pair; h->tm.n_pair_declined = h->n_pair_declined;
+      if (h->pair_ran) { HIPCHK(hipEventElapsedTime(&ms, h->ev_pair[0], h->ev_pair[1])); h->tm.ms_poa_pair = ms; }
       DBG("run: poa done\n");
       HIPCHK(hipEventElapsedTime(&ms, t3, t4)); h->tm.ms_poa = ms;
     }

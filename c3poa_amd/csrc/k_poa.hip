@@ -39,7 +39,7 @@ struct Ctx {
 #endif
 #define CTX_I(name, k) __device__ __forceinline__ int* name() const { return I + (size_t)(k) * Ncap; }
   CTX_I(n_in, 0) CTX_I(n_out, 1) CTX_I(grp, 2) CTX_I(index, 5) CTX_I(gfirst, 6) CTX_I(glast, 7)
-  CTX_I(rem, 8) CTX_I(mpl, 9) CTX_I(mpr, 10) CTX_I(rowm, 11) /* 3 ints per row: band begin, band end, cell offset (blocks 11..13) */ CTX_I(anchor, 14) CTX_I(col, 15)
+  CTX_I(rem, 8) CTX_I(mpl, 9) CTX_I(mpr, 10) CTX_I(rowm, C3_POA_I_ROWM) /* 3 ints per row: band begin, band end, cell offset (blocks 11..13) */ CTX_I(anchor, 14) CTX_I(col, 15)
   CTX_I(col2t, 16) CTX_I(nxt, 17) CTX_I(foff, 18) /* per row: offset of its cells in the far arena (far / wide / many-predecessor rows only) */
 #undef CTX_I
   __device__ __forceinline__ int* order() const { return I + (size_t)(3 + osel) * Ncap; }
@@ -1158,6 +1158,13 @@ extern "C" void c3k_launch_pairwise(const uint8_t* rows, int ncol, const uint8_t
   hipLaunchKernelGGL(k_pairwise, dim3(1), dim3(64), 0, s, rows, ncol, qa, la, qb, lb, scratch, out, out_len);
 }
 
+// vq of subread 1 as k_poa_pair left it (16 bits per base, 0xffff = insertion) -> the vq of poa_fuse.  A call of its own: inlined, the
+// copy loop cost k_poa spilled registers
+__device__ __attribute__((noinline)) void pair_fetch(int* vq, const uint16_t* pv, int Q) {
+  for (int k = wave_lane(); k < Q; k += 64) { const int v = pv[k]; vq[k] = v == 0xffff ? -1 : v; }
+  WSYNC();
+}
+
 // 6 waves/SIMD (80 VGPRs, 26 spilled outside the row loop) with a 4-row LDS ring (6.7 KB per wave, 24 waves per CU):
 // 59.4 ms per 32768 cfg2 reads against 67.8 ms at 4 waves/SIMD with the 8-row ring -- the row loop is a dependent
 // chain (scan -> next row), so resident waves are what hides its latency.
@@ -1213,7 +1220,12 @@ __global__ __launch_bounds__(64, C3_POA_WAVES) void k_poa(PoaArgs a) {
       int poff = 0;
       for (int s = 0; s < ns && !fail; ++s) {
         const int qb = wave_first(info->sub_beg[s]), Q = wave_first(info->sub_end[s]) - qb;
-        if (s > 0) { const int rc = poa_align<W32, DEF, WIDE>(c, a.p, qb, Q, lane, &cells PHP); if (rc < 0) { fail = (rc == -4 || rc == -5) ? 2 : 1; punted = rc == -5; break; } }
+        // subread 1 of a read k_poa_pair has taken: its vq and cell count are stored, the alignment is not repeated
+        if (!W32 && DEF && !WIDE && s == 1 && a.pair_done != nullptr && wave_first((int)a.pair_done[rid]) != 0) {
+          pair_fetch(c.mpl(), a.pair_vq + a.b.off[rid] + qb, Q);
+          cells += wave_first(a.pair_cells[rid]);
+        }
+        else if (s > 0) { const int rc = poa_align<W32, DEF, WIDE>(c, a.p, qb, Q, lane, &cells PHP); if (rc < 0) { fail = (rc == -4 || rc == -5) ? 2 : 1; punted = rc == -5; break; } }
         if (poa_fuse(c, s == 0, qb, Q, c.path() + poff, lane PHP) < 0) { fail = 2; break; }                 // node capacity
         poff += Q;
       }
@@ -1401,7 +1413,7 @@ __global__ __launch_bounds__(64, C3_POA_WAVES) void k_poa(PoaArgs a) {
 
 extern "C" void c3k_launch_poa(const PoaArgs* a, int slots, int wide32, int wide_ring, hipStream_t stream) {
   const C3Params& p = a->p;
-  const bool def = p.poa_match == 5 && p.poa_mismatch == 4 && p.o1 == 4 && p.e1 == 2 && p.o2 == 24 && p.e2 == 1;
+  const bool def = c3_poa_default_scoring(p);
 #define C3_POA_LAUNCH(W, D, R) hipLaunchKernelGGL((k_poa<W, D, R>), dim3(slots), dim3(64), 0, stream, *a)
   if (wide32) { if (def) C3_POA_LAUNCH(true, true, false); else C3_POA_LAUNCH(true, false, false); }
   else if (wide_ring) { if (def) C3_POA_LAUNCH(false, true, true); else C3_POA_LAUNCH(false, false, true); }

@@ -122,6 +122,8 @@ typedef struct {
   int64_t n_band_mismatch;                  /* C3_DEBUG_BAND=verify only: accepted band layers whose traceback differs from the full matrix's (must be 0) */
   int64_t n_win_redo;                       /* windows with a layer beyond the first launch's DP scratch, redone by the full-size second launch of k_window */
   int64_t n_poa_redo16;                     /* of n_poa_redo: reads redone by the 32-bit POA pass -- a score did not fit the 16-bit cells of the first passes, or the 32-bit cells of its wide / far rows did not fit the arena of the full-size pass (0 on the config shapes) */
+  int64_t n_pair, n_pair_declined;          /* k_poa_pair: reads whose second subread it aligned to the chain of the first ahead of k_poa / reads with >= 2 subreads it left to k_poa (both 0 when it does not run: non-default scoring, WIDE or 32-bit first pass) */
+  float ms_poa_pair;                        /* its kernel time (part of ms_poa) */
 } c3_timing;
 
 typedef struct c3_handle c3_handle;

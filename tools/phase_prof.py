@@ -28,6 +28,8 @@ for which, kn in ((0, "k_poa"), (1, "k_window")):
     h.lib.c3_debug_phases(h.h, which, out)
     tot = float(sum(out[:8]) + out[9] + (out[8] if which else 0)) or 1.0
     print(kn, " ".join("%s=%.1f%%" % (names[which][i], 100 * out[i] / tot) for i in range(10) if out[i]), "| raw[8..11] =", out[8], out[9], out[10], out[11])
+    if which == 0:         # the raw counters (cycle sums over all waves; [12], [13] packed row counts): tools/pair_phase_split.py subtracts two runs
+        print("k_poa raw", " ".join(str(int(x)) for x in out))
     if which == 1 and out[11]:
         rows = out[11] & 0xffffffff; gen = out[10] >> 32; kept = out[10] & 0xffffffff; multi = out[11] >> 32
         print("   rows %d: fast %.1f%%, general %.1f%% = predecessor r-1 but kept for later %.1f%% + several predecessors %.1f%% + one far predecessor %.1f%%" % (
