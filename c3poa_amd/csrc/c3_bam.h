@@ -1,5 +1,5 @@
 // c3_bam.h -- the rule of one unaligned BAM record (include/c3poa.h "Unaligned BAM records on the GPU"), once,
-// for the host statement (c3_bam.cpp), the reader (c3_io.cpp) and k_bam (k_bam.hip): the file header's extent, the strictness
+// for the host statement (c3_bam.cpp), the reader (c3_reader.cpp) and k_bam (k_bam.hip): the file header's extent, the strictness
 // test of the record at a byte, the chain step, the name cut and the two byte maps.  Finding the record starts in parallel,
 // the prefix sums and the byte moves are what the two sides do each in their own way.
 #ifndef C3_BAM_H

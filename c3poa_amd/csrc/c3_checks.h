@@ -8,7 +8,7 @@
 void c3_set_host_error(const char* msg);        // c3_handle.hip: the text of c3_last_error(NULL)
 
 int c3_demux_prepare(int n_a, const char* a_cat, const int64_t* a_off, int n_b, const char* b_cat, const int64_t* b_off,
-                     uint8_t* tab, int* n_codes, const char** msg);                                                  // c3_io.cpp
+                     uint8_t* tab, int* n_codes, const char** msg);                                                  // c3_index.cpp
 int c3_qv_check(const char* cons, int n, int n_pieces, const char* seq_cat, const char* qual_cat, const int64_t* piece_off,
                 const int32_t* modes, const char* qv_out, const char** msg);                                          // c3_qv.cpp
 int c3_fastq_check_args(const char* who, const char* text, int64_t n, const char* names, int64_t names_cap, const int64_t* name_off,
@@ -29,7 +29,7 @@ int c3_demux_text_check_args(const char* who, const char* src, int64_t n, int fl
                              c3_demux_text_info* info, int* S, uint8_t* tab, int* n_codes);                          // c3_dsplit.cpp
 int c3_bgzf_data_error(const char* who, int64_t member, int st);                                                      // c3_inflate.cpp
 
-// the reader's device stretches (c3_stream.hip, called by c3_io.cpp; not part of the public interface)
+// the reader's device stretches (c3_stream.hip, called by c3_reader.cpp and c3_reader_bgzf.cpp; not part of the public interface)
 // (a BAM stretch fills the same table: info as for FASTQ, plus the reason and place of a departure and the file header's bytes)
 struct c3_fq_stretch { c3_fastq_info info; const int64_t* off; const int64_t* name_off; int64_t text_bytes;
                        int32_t reason; int64_t bad_at, header_bytes; };
@@ -47,3 +47,5 @@ extern "C" int c3_bgzf_sets_create(c3_bgzf* z, int n_sets);
 extern "C" int c3_bgzf_set_reserve(c3_bgzf* z, int set, int64_t bytes, int64_t keep);
 extern "C" int c3_bgzf_stretch_stage(c3_bgzf* z, int slot, int64_t r0, int64_t r1, char* names, int set, int64_t at);
 extern "C" int c3_bgzf_set_get(const c3_bgzf* z, int set, const char** d_seqs, const char** d_quals, int* device);
+// the --bgzf writers' private call (c3_stream.hip, called by c3_writer.cpp): pieces p[0..np) compressed as one text
+extern "C" int c3_bgzf_compress_pieces(c3_bgzf* z, const char* const* p, const int64_t* len, int np, char* dst, int64_t cap, int64_t* out_len);

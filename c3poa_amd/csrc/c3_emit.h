@@ -1,5 +1,5 @@
 // c3_emit.h -- the record rule of the main CLI's writer (include/c3poa.h "Records formatted on the GPU"), once,
-// for the host statement (c3_emit.cpp), the host writer (c3_io.cpp: emit_of) and k_emit (k_emit.hip): which records a read
+// for the host statement (c3_emit.cpp), the host writer (c3_writer.cpp: emit_of) and k_emit (k_emit.hip): which records a read
 // produces (C3POa.py:115-132, determine_consensus.py:57-77,108-114), in which order, how long each is, and the text of the
 // average quality in the consensus header (C3POa.py:168).  How the bytes are moved is what the two sides do each in their
 // own way.
@@ -45,7 +45,7 @@ C3_PO_HD inline void c3_emit_piece(const c3_read_result& r, const C3EmitDec& d, 
   *beg = b; *end = e;
 }
 
-// str(round(tot / L, 2)) of Python (C3POa.py:168; avg_qual_text of c3_io.cpp prints "%.2f" and drops one trailing zero): the
+// str(round(tot / L, 2)) of Python (C3POa.py:168; avg_qual_text of c3_writer.cpp prints "%.2f" and drops one trailing zero): the
 // IEEE double d = tot / L, two decimals correctly rounded from d's binary value (ties of that value to even), by integers:
 // |d| < 256, so d = m * 2^-sh with sh >= 45 and 100 * m < 2^60.  A sign whenever tot < 0.  At most 7 bytes; returns the length.
 C3_PO_HD inline int c3_emit_avgq(int64_t tot, int64_t L, char* out) {

@@ -235,7 +235,7 @@ C3_BGZF_HD inline int c3_inflate_member(P& p, C3InfTab* T, uint32_t plen, uint32
   return outn == isize ? C3_INF_OK : C3_INF_SHORT;
 }
 
-// ---- member framing (host): what bgzf_next_stretch of c3_io.cpp checks, as one walk ------------------------------------
+// ---- member framing (host): what bgzf_next_stretch of c3_reader_bgzf.cpp checks, as one walk ------------------------------------
 struct C3BgzfMember { uint32_t poff, plen, ooff, isize, crc; };   // payload offset / bytes, output offset, trailer
 
 // member at src[at..n): fills m (poff counted from the member's first byte, ooff left alone) and returns its size, or 0

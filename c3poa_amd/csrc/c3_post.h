@@ -25,7 +25,7 @@
 // ---- match_index (C3POa_postprocessing.py:266-285) for one piece; k_match_index and c3_post_oligo call it --------------
 // sliding Levenshtein distance against every index, the reference's quirks included (a slice that is too short for index k
 // ends the loop over indexes at that position; stable order; the winner needs distance < 2 and a runner-up more than 1
-// further away).  At most 16 indexes of at most 32 bases.  Same function as the host statement c3_match_index (c3_io.cpp).
+// further away).  At most 16 indexes of at most 32 bases.  Same function as the host statement c3_match_index (c3_index.cpp).
 template <class OFF> C3_PO_HD inline int c3_match_rule(const char* seq, int L, int n_idx, const char* idx_cat, const OFF* idx_off) {
   int best[C3_POST_MAX_IDX];
   for (int k = 0; k < C3_POST_MAX_IDX; ++k) best[k] = INT32_MAX;

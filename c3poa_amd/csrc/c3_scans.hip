@@ -218,7 +218,7 @@ static std::vector<uint32_t> dmx_meta(int n_a, const char* a_cat, const int64_t*
 }
 
 // sample demultiplexer (paper/Demultiplex_R2C2_reads.py, demultiplex): k_demux over n heads of 300 bytes; the host
-// statement is c3_demux_host (c3_io.cpp), which also holds the checks both share (c3_demux_prepare).
+// statement is c3_demux_host (c3_index.cpp), which also holds the checks both share (c3_demux_prepare).
 extern "C" int c3_demux_indexes(c3_handle* h, int n, const char* heads, int n_a, const char* a_cat, const int64_t* a_off,
                                 int n_b, const char* b_cat, const int64_t* b_off, int32_t* win, uint8_t* dist) {
   if (!h) return C3_E_ARG;

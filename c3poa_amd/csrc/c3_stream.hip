@@ -70,7 +70,7 @@ extern "C" void c3_bgzf_destroy(c3_bgzf* z) {
   delete z;
 }
 
-// the concatenation of pieces p[0..np) compressed as one text (the writers' formatter slices, c3_io.cpp)
+// the concatenation of pieces p[0..np) compressed as one text (the writers' formatter slices, c3_writer.cpp)
 extern "C" int c3_bgzf_compress_pieces(c3_bgzf* z, const char* const* p, const int64_t* len, int np, char* dst, int64_t cap, int64_t* out_len) {
   if (!z || !out_len || np < 0 || (np > 0 && (!p || !len))) return host_fail(C3_E_ARG, "c3_bgzf_compress: bad arguments");
   int64_t n = 0;
@@ -356,7 +356,7 @@ extern "C" int c3_bam_parse(c3_bgzf* z, const char* data, int64_t n, int at_star
   return C3_E_OK;
 }
 
-// ---- the reader's device stretches (c3_io.cpp; not part of the public interface) ----------
+// ---- the reader's device stretches (c3_reader.cpp; not part of the public interface) ----------
 // Stretch = `carry_len` bytes of the other slot's text from `carry_from` on (the record its end cut), then the inflated
 // members of comp; it stays on the device, is parsed there with min_len 0 (the group rule, min_len included, is the
 // reader's), and the record tables come back (c3_fq_stretch, c3_checks.h).  On return the slot holds the finished records

@@ -116,7 +116,7 @@ extern "C" void c3k_launch_adapter(const AdapterArgs* a, int grid, hipStream_t s
 // One lane per piece (the 20-mer cut next to an adapter): sliding Levenshtein distance against every index, the
 // reference's quirks included (a slice that is too short for index k ends the loop over indexes at that position;
 // stable order; winner needs distance < 2 and a runner-up more than 1 further away).  Same function as the host
-// statement c3_match_index (c3_io.cpp), which the golden cases of the reference pin.
+// statement c3_match_index (c3_index.cpp), which the golden cases of the reference pin.
 #define PIECE_W 64      // bytes per piece slot (at most C3_POST_MAX_IDX indexes of at most C3_POST_MAX_IDX_LEN bases: c3_post.h)
 __global__ __launch_bounds__(64) void k_match_index(const char* pieces, const int* lens, int n, int n_idx,
                                                      const char* idx_cat, const long long* idx_off, int* out) {

@@ -2,7 +2,7 @@
 // Per read and per index k (length m <= 32): the minimum over the windows head[i : i+m], i in 0 .. 299-m, of the global
 // Levenshtein distance index <-> window; then per set (A = Nextera, B = TSO) the stable-sort decision: the first index
 // of minimum distance wins when that distance is < 4 and the runner-up's is more than 1 further away.  Same function as
-// the host statement c3_demux_host (c3_io.cpp), which the golden cases of the reference pin.
+// the host statement c3_demux_host (c3_index.cpp), which the golden cases of the reference pin.
 //
 // One workgroup of 256 lanes takes DMX_R reads.  Lane work item = (read, index, window chunk): DMX_C chunks of ~37
 // windows per (read, index), chunk fastest, so neighbouring lanes share one index (one m, equal trip counts) and one

@@ -1,8 +1,8 @@
 #!/bin/sh
 # Host sanitizer check of c3_emit_group_host against the writer it states: compiles c3poa_amd/csrc/c3_emit.cpp,
-# c3poa_amd/csrc/c3_io.cpp and tools/emit_fuzz_host.cpp for the CPU with AddressSanitizer and UndefinedBehaviorSanitizer and
+# c3poa_amd/csrc/c3_writer.cpp and tools/emit_fuzz_host.cpp for the CPU with AddressSanitizer and UndefinedBehaviorSanitizer and
 # runs a few thousand random and hostile record tables through both (see the .cpp).  A stand-alone program: nothing is loaded
-# into Python and nothing runs on a GPU (c3_io.cpp includes the HIP headers for its page-locked buffers, hence hipcc).
+# into Python and nothing runs on a GPU (hipcc only because the library is built with it: the writer needs no HIP header).
 #   tools/emit_fuzz_host.sh [groups]
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -10,6 +10,6 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 OUT=$(mktemp -d)
 trap 'rm -rf "$OUT"' EXIT
 $HIPCC -std=c++17 -O1 -g -fno-omit-frame-pointer -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -Wall \
-  "$ROOT/c3poa_amd/csrc/c3_emit.cpp" "$ROOT/c3poa_amd/csrc/c3_io.cpp" "$ROOT/tools/emit_fuzz_host.cpp" -lz -o "$OUT/emit_fuzz_host"
+  "$ROOT/c3poa_amd/csrc/c3_emit.cpp" "$ROOT/c3poa_amd/csrc/c3_writer.cpp" "$ROOT/tools/emit_fuzz_host.cpp" -lz -o "$OUT/emit_fuzz_host"
 # (the writer keeps its pooled arenas until the process ends, on purpose: no leak report)
 ASAN_OPTIONS=detect_leaks=0 "$OUT/emit_fuzz_host" "${1:-4000}" "$OUT"
