@@ -25,6 +25,117 @@ def test_library_exports_every_declared_symbol():
     assert set(_lib.EXPORTS) <= set(names)
 
 
+def _header():
+    """(prototypes {name: (return type, [parameter types])}, structs {name: [(field, type, is_array)]}) of include/c3poa.h.  A
+    statement that is none of a prototype, a struct, an enum or an opaque typedef is an AssertionError naming it."""
+    txt = open(os.path.join(ROOT, "include", "c3poa.h")).read()
+    txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
+    txt = re.sub(r"^\s*#.*$", " ", txt, flags=re.M)
+    txt = re.sub(r'extern\s+"C"\s*\{', " ", txt).rstrip()
+    assert txt.endswith("}"), txt[-40:]
+    txt = txt[:-1]
+    structs = {}
+
+    def struct(m):
+        fields = []
+        for decl in filter(None, (d.strip() for d in m.group(1).split(";"))):
+            first, *more = [p.strip() for p in decl.split(",")]
+            f = re.fullmatch(r"(.*[\s*])(\w+)\s*(\[[^\]]*\])?", first)
+            assert f, "unreadable field %r of %s" % (decl, m.group(2))
+            fields.append((f.group(2), f.group(1).strip(), bool(f.group(3))))
+            for p in more:
+                g = re.fullmatch(r"(\w+)\s*(\[[^\]]*\])?", p)
+                assert g, "unreadable field %r of %s" % (decl, m.group(2))
+                fields.append((g.group(1), f.group(1).strip(), bool(g.group(2))))
+        structs[m.group(2)] = fields
+        return " "
+
+    txt = re.sub(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;", struct, txt, flags=re.S)
+    txt = re.sub(r"typedef\s+enum\s*\{[^}]*\}\s*\w+\s*;", " ", txt)
+    protos = {}
+    for stmt in filter(None, (" ".join(s.split()) for s in txt.split(";"))):
+        if re.fullmatch(r"typedef struct (\w+) \1", stmt):
+            continue
+        m = re.fullmatch(r"([\w\s*]+?[\s*])(c3_\w+) ?\(([^()]*)\)", stmt)
+        assert m, "unreadable declaration: %r" % stmt
+        params = [] if m.group(3).strip() == "void" else [p.strip() for p in m.group(3).split(",")]
+        types = []
+        for p in params:
+            t = re.fullmatch(r"(.*[\s*])(\w+)", p)
+            assert t, "unreadable parameter %r of %s" % (p, m.group(2))
+            types.append(t.group(1).strip())
+        assert m.group(2) not in protos, m.group(2)
+        protos[m.group(2)] = (m.group(1).strip(), types)
+    return protos, structs
+
+
+def _c_class(ctype):
+    """the class of a C type of the header: ptr, i32, i64, f32, f64 or void"""
+    if "*" in ctype:
+        return "ptr"
+    t = ctype.replace("const", "").strip()
+    assert t in ("int", "int32_t", "int64_t", "float", "double", "void"), "a type the test does not know: %r" % ctype
+    return {"int": "i32", "int32_t": "i32", "int64_t": "i64", "float": "f32", "double": "f64", "void": "void"}[t]
+
+
+def _ctypes_class(t):
+    if t is None:
+        return "void"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "ptr"
+    for k, ts in (("i32", (C.c_int, C.c_int32)), ("i64", (C.c_int64,)), ("f32", (C.c_float,)), ("f64", (C.c_double,))):
+        if t in ts:
+            return k
+    raise AssertionError("a ctypes type the test does not know: %r" % (t,))
+
+
+def test_prototype_table_agrees_with_the_header():
+    """every entry of the binding's prototype table against the declaration of include/c3poa.h: the number of parameters, and the
+    class of every parameter and of the return value (int / int32_t: c_int or c_int32; int64_t: c_int64; double: c_double; any
+    pointer: a pointer type; void: None; const char* returned: c_char_p).  load() applies exactly this table, and EXPORTS is
+    its key list."""
+    from c3poa_amd import _lib
+    protos, _structs = _header()
+    assert len(protos) >= 100
+    assert list(_lib._PROTOTYPES) == _lib.EXPORTS and len(set(_lib.EXPORTS)) == len(_lib.EXPORTS)
+    assert set(_lib._PROTOTYPES) == set(protos), sorted(set(_lib._PROTOTYPES) ^ set(protos))
+    lib = _lib.load()
+    for name, (ret, params) in protos.items():
+        restype, argtypes = _lib._PROTOTYPES[name]
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+        assert len(argtypes) == len(params), (name, len(argtypes), params)
+        assert _ctypes_class(restype) == _c_class(ret), (name, ret, restype)
+        if _c_class(ret) == "ptr":
+            assert " ".join(ret.split()) == "const char*" and restype is C.c_char_p, (name, ret, restype)
+        for k, (p, a) in enumerate(zip(params, argtypes)):
+            assert _ctypes_class(a) == _c_class(p), (name, k, p, a)
+
+
+def test_structures_agree_with_the_header():
+    """every struct of include/c3poa.h against its ctypes Structure: the field names in order and the class of every field (the
+    rule of the prototype test, with float: c_float).  c3_read_result has arrays: its names are compared here, its size in
+    test_default_config_matches_reference_call_sites and against RESULT_DTYPE at import."""
+    from c3poa_amd import _lib
+    _protos, structs = _header()
+    binding = {"c3_config": _lib.Config, "c3_read_result": _lib.ReadResult, "c3_timing": _lib.Timing, "c3_host_batch": _lib.HostBatchStruct,
+               "c3_qv_timing": _lib.QvTiming, "c3_fastq_info": _lib.FastqInfo, "c3_bam_info": _lib.BamInfo, "c3_post_args": _lib.PostArgs,
+               "c3_post_timing": _lib.PostTiming, "c3_fasta_info": _lib.FastaInfo, "c3_demux_info": _lib.DemuxInfo,
+               "c3_demux_timing": _lib.DemuxTiming, "c3_emit_timing": _lib.EmitTiming, "c3_fastx_info": _lib.FastxInfo,
+               "c3_post_text_info": _lib.PostTextInfo, "c3_post_text_timing": _lib.PostTextTiming, "c3_demux_sets": _lib.DemuxSetsStruct,
+               "c3_demux_text_info": _lib.DemuxTextInfo, "c3_demux_text_timing": _lib.DemuxTextTiming,
+               "c3_device_batch": _lib.DeviceBatchStruct}
+    assert set(structs) == set(binding), sorted(set(structs) ^ set(binding))
+    for name, fields in structs.items():
+        got = binding[name]._fields_
+        assert [f[0] for f in got] == [f[0] for f in fields], name
+        for (fname, ctype, is_array), (_n, t) in zip(fields, got):
+            if is_array:
+                assert name == "c3_read_result" and issubclass(t, C.Array) and _ctypes_class(t._type_) == _c_class(ctype), (name, fname)
+            else:
+                assert _ctypes_class(t) == _c_class(ctype), (name, fname, ctype, t)
+
+
 def test_default_config_matches_reference_call_sites():
     from c3poa_amd import _lib
     c = _lib.default_config()
