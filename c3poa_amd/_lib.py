@@ -1016,7 +1016,7 @@ class Reader(_Owned):
         hb.dev (c3_device_batch) and no seqs / quals; after a departure the groups are host groups (hb.dev is None)"""
         self.lib = load()
         self.r = C.c_void_p()
-        self.n_sets, self._cur = max(1, int(n_sets)), -1
+        self.n_sets, self._cur, self.parse_device = max(1, int(n_sets)), -1, bool(parse_device)
         if inflate_device is not None:
             if byte_range is not None:
                 raise ValueError("inflate_device goes with a whole-file reader")

@@ -22,7 +22,9 @@ from c3poa_amd.seqio import fastx_read, revcomp  # noqa: E402
 
 
 class FakeHandle:
-    """stand-in for _lib.Handle: same methods the pipeline calls; results from the oracle; random latency"""
+    """stand-in for _lib.Handle: the methods the pipeline calls (the handle protocol in the docstring of stream.Pipeline);
+    results from the oracle; random latency"""
+    QV_BYTE = ord("I")
     delays = random.Random(7)
 
     def __init__(self, **cfg):
@@ -49,7 +51,7 @@ class FakeHandle:
         self.cur, self.staged = self.staged, None
         self.n, self.off = self.cur[2], self.cur[3]
 
-    def run(self):
+    def run(self, qv=False):
         time.sleep(self.delays.random() * 0.05)
 
     def timing(self):
@@ -85,11 +87,18 @@ class FakeHandle:
         self.snap = None
         return res, buf, coff
 
+    def results_fetch_qv(self, into, shape):
+        """the oracle's consensus with a constant quality byte"""
+        res, buf, coff = self.results_fetch(into, shape)
+        qv = into.fit_qv(shape[1])
+        qv[:int(coff[-1])] = self.QV_BYTE
+        return res, buf, coff, qv
+
     def close(self):
         pass
 
 
-def _run(tmp_path, tag, recs, n_dev, batch, monkeypatch, readers_per_gpu=1, raw=False):
+def _run(tmp_path, tag, recs, n_dev, batch, monkeypatch, readers_per_gpu=1, raw=False, qv=False):
     out = str(tmp_path / tag) + "/"
     os.makedirs(out)
     fq = str(tmp_path / "reads.fastq")
@@ -102,12 +111,14 @@ def _run(tmp_path, tag, recs, n_dev, batch, monkeypatch, readers_per_gpu=1, raw=
     monkeypatch.setenv("C3_READERS_PER_GPU", str(readers_per_gpu))
     monkeypatch.setenv("C3_MIN_RANGE_BYTES", "1")
     args = types.SimpleNamespace(out_path=out, reads=fq, groupSize=1000, lencutoff=1000, mdistcutoff=500, zero=True,
-                                 compress_output=False)
+                                 compress_output=False, consensus_fastq=qv)
     sd = {"Splint1": [synth.SPLINT1, revcomp(synth.SPLINT1)]}
     adapter = {r[0]: ["Splint1", r[3]] for r in recs}
     n = stream.run(args, sd, adapter, {"Splint1"}, n_dev)
     assert n == len(recs)
-    assert sorted(os.listdir(out + "Splint1")) == ["R2C2_Consensus.fasta", "R2C2_Subreads.fastq"]       # no part file left
+    assert sorted(os.listdir(out + "Splint1")) == ["R2C2_Consensus.fasta"] + ["R2C2_Consensus.fastq"] * qv + ["R2C2_Subreads.fastq"]       # no part file left
+    if qv:
+        return tuple(sorted(fastx_read(out + "Splint1/" + f)) for f in ("R2C2_Consensus.fasta", "R2C2_Subreads.fastq", "R2C2_Consensus.fastq"))
     if raw:
         return open(out + "Splint1/R2C2_Consensus.fasta", "rb").read(), open(out + "Splint1/R2C2_Subreads.fastq", "rb").read()
     return (sorted(fastx_read(out + "Splint1/R2C2_Consensus.fasta")), sorted(fastx_read(out + "Splint1/R2C2_Subreads.fastq")))
@@ -234,3 +245,104 @@ def test_pinned_result_buffers_keep_a_replaced_block_until_the_next_fit(monkeypa
     assert first in freed
     rb.close()
     assert len(freed) == len(blocks)
+
+
+def test_consensus_fastq_three_workers_equal_one_worker(tmp_path, monkeypatch):
+    """--consensus-fastq through the pipeline: the QV bytes travel with their batch (results_fetch_qv on the fetch thread, the
+    FASTQ writer beside the group writer), so 15 batches over 3 workers give the records of one worker in all three files"""
+    recs = list(synth.generate("cfg1", n_reads=60))
+    one = _run(tmp_path, "one", recs, 1, 4, monkeypatch, qv=True)
+    many = _run(tmp_path, "many", recs, 3, 4, monkeypatch, qv=True)
+    assert one == many
+    assert len(one[0]) == 60 and len(one[2]) == 60
+    cons = {r[0]: r[1] for r in one[0]}
+    for name, seq, qual in one[2]:                                    # the FASTA record's bases under the stand-in's quality byte
+        assert seq == cons[name] and qual == chr(FakeHandle.QV_BYTE) * len(seq)
+
+
+def _failing_run(tmp_path, monkeypatch, handle, n_dev, readers_per_gpu=1):
+    """stream.run over 40 cfg1 reads in batches of 4 with a stand-in that raises, inside the thread-plus-join(60) guard.
+    Returns (what run() raised, the readers it opened, those of them that were closed, its threads that are still alive)."""
+    import threading
+    recs = list(synth.generate("cfg1", n_reads=40))
+    fq = str(tmp_path / "reads.fastq")
+    with open(fq, "w") as fh:
+        for r in recs:
+            fh.write("@%s\n%s\n+\n%s\n" % (r[0], r[1], r[2]))
+    out = str(tmp_path / "out") + "/"
+    os.makedirs(out)
+    monkeypatch.setattr(_lib, "Handle", handle)
+    monkeypatch.setenv("C3_GPU_BATCH_READS", "4")
+    monkeypatch.setenv("C3_READERS_PER_GPU", str(readers_per_gpu))
+    monkeypatch.setenv("C3_MIN_RANGE_BYTES", "1")
+    opened, closed = [], []
+    init, close = _lib.Reader.__init__, _lib.Reader.close
+
+    def spy_init(self, *a, **kw):
+        opened.append(self)
+        init(self, *a, **kw)
+
+    def spy_close(self):
+        closed.append(self)
+        close(self)
+    monkeypatch.setattr(_lib.Reader, "__init__", spy_init)
+    monkeypatch.setattr(_lib.Reader, "close", spy_close)
+    args = types.SimpleNamespace(out_path=out, reads=fq, groupSize=1000, lencutoff=1000, mdistcutoff=500, zero=True, compress_output=False)
+    sd = {"Splint1": [synth.SPLINT1, revcomp(synth.SPLINT1)]}
+    box = {}
+
+    def go():
+        try:
+            stream.run(args, sd, {r[0]: ["Splint1", r[3]] for r in recs}, {"Splint1"}, n_dev)
+        except BaseException as e:                   # noqa: BLE001
+            box["err"] = e
+    before = set(threading.enumerate())
+    th = threading.Thread(target=go, daemon=True)
+    th.start()
+    th.join(60)
+    assert not th.is_alive(), "stream.run hangs after an error in a stage"
+    left = [t.name for t in threading.enumerate() if t.is_alive() and (t.name.startswith("c3-") or t not in before)]
+    return box.get("err"), opened, [r for r in opened if any(r is c for c in closed)], left
+
+
+def _second_call_raises(fn, boom):
+    import itertools
+    calls = itertools.count(1)
+
+    def wrapped(*a, **kw):
+        if next(calls) == 2:
+            raise boom
+        return fn(*a, **kw)
+    return wrapped
+
+
+def _assert_cleaned_up(err, boom, opened, closed, left, n_readers):
+    assert err is boom                                                 # the first error, that very object
+    assert len(opened) == n_readers and len(closed) == len(opened), "%d of %d readers closed" % (len(closed), len(opened))
+    assert left == [], "threads of the run still alive: %s" % left
+
+
+def test_error_in_run_of_the_second_batch_cleans_up(tmp_path, monkeypatch):
+    """2 workers x 2 ranges; the handles' second run() (whichever worker makes it) raises"""
+    boom = RuntimeError("run failed")
+
+    class H(FakeHandle):
+        run = _second_call_raises(FakeHandle.run, boom)
+    err, opened, closed, left = _failing_run(tmp_path, monkeypatch, H, 2, readers_per_gpu=2)
+    _assert_cleaned_up(err, boom, opened, closed, left, 4)
+
+
+def test_error_in_results_fetch_of_the_second_batch_cleans_up(tmp_path, monkeypatch):
+    boom = RuntimeError("fetch failed")
+
+    class H(FakeHandle):
+        results_fetch = _second_call_raises(FakeHandle.results_fetch, boom)
+    err, opened, closed, left = _failing_run(tmp_path, monkeypatch, H, 1)
+    _assert_cleaned_up(err, boom, opened, closed, left, 1)
+
+
+def test_error_in_write_group_of_the_second_batch_cleans_up(tmp_path, monkeypatch):
+    boom = OSError("write failed")
+    monkeypatch.setattr(_lib, "write_group", _second_call_raises(_lib.write_group, boom))
+    err, opened, closed, left = _failing_run(tmp_path, monkeypatch, FakeHandle, 1)
+    _assert_cleaned_up(err, boom, opened, closed, left, 1)

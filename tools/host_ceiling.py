@@ -27,7 +27,8 @@ from c3poa_amd.seqio import revcomp  # noqa: E402
 
 
 class InstantHandle:
-    """stand-in for _lib.Handle: the methods stream.run calls, no device; results are fabricated with numpy in ~1 ms per batch"""
+    """stand-in for _lib.Handle: the methods stream.run calls (the handle protocol in the docstring of stream.Pipeline), no device;
+    results are fabricated with numpy in ~1 ms per batch"""
 
     def __init__(self, **cfg):
         self.cfg = types.SimpleNamespace(conk_match=5)
