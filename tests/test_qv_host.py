@@ -17,8 +17,10 @@ def code(c):
     return CODE.get(c, 0)
 
 
-def spec_align(C, P, Q, mode, S):
-    """mode 0 / 1 in the frame given (mode 2 is handled by the caller)"""
+def spec_align(C, P, Q, mode, S, info=None):
+    """mode 0 / 1 in the frame given (mode 2 is handled by the caller).  info: a dict that receives what the edge tests assert
+    on -- "end" (the end cell), "maxima" (the band cells of largest H, in scan order), "d" (the set of band steps
+    lo(i) - lo(i-1)), "edge0" / "edge127" (the path touched band offset 0 with j > 0 / offset 127 with j < n)"""
     n, m = len(C), len(P)
     lo = [((i * n + m // 2) // m if mode == 0 else i) - 64 for i in range(m + 1)]
     H = {}
@@ -58,6 +60,10 @@ def spec_align(C, P, Q, mode, S):
             path.append(("X", i, j)); j -= 1
         else:
             path.append(("I", i, j)); i -= 1
+    if info is not None:
+        top = max(H.values())
+        info.update(end=(ei, ej), maxima=sorted(k for k, h in H.items() if h == top), d={lo[i] - lo[i - 1] for i in range(1, m + 1)},
+                    edge0=any(j - lo[i] == 0 and j > 0 for _k, i, j in path), edge127=any(j - lo[i] == 127 and j < n for _k, i, j in path))
     path.reverse()
     J = n if mode == 0 else ej
     if J == 0:
@@ -77,7 +83,15 @@ def spec_align(C, P, Q, mode, S):
         S[min(run[1], J - 1)] -= run[0]
 
 
-def spec_qv(cons, pieces):
+def _info(infos):
+    if infos is None:
+        return None
+    infos.append({})
+    return infos[-1]
+
+
+def spec_qv(cons, pieces, infos=None):
+    """infos: a list that receives one spec_align info dict per piece (mode 2: in the reversed frame)"""
     n = len(cons)
     C = [code(c) for c in cons]
     S = [0] * n
@@ -86,11 +100,11 @@ def spec_qv(cons, pieces):
         Q = [min(93, max(0, ord(c) - 33)) for c in qual]
         if mode == 2:
             Sr = [0] * n
-            spec_align(C[::-1], P[::-1], Q[::-1], 1, Sr)
+            spec_align(C[::-1], P[::-1], Q[::-1], 1, Sr, _info(infos))
             for j in range(n):
                 S[j] += Sr[n - 1 - j]
         else:
-            spec_align(C, P, Q, mode, S)
+            spec_align(C, P, Q, mode, S, _info(infos))
     return "".join(chr(33 + min(60, max(0, s))) for s in S)
 
 
