@@ -1478,7 +1478,7 @@ __global__ __launch_bounds__(64, C3_WIN_WAVES) void k_window(WinArgs a) {
           ++n_fallback; cb = (cb < 4 && a.band_mode == 0) ? cb + 1 : 0;
         }
         if (fail) break;
-        cells += (long long)(R + 1) * (Q + 1);
+        if (vpass == 0) cells += (long long)(R + 1) * (Q + 1);                // (the verify pass computes the layer again; it is still one layer)
         PH_MARK(4)
         // ---- traceback.  rq[q] = DP row aligned to query base q, 0 = insertion.
         // 64 ROWS AT A TIME: lane k owns row rt-k, loads its descriptor and a 16-byte window of its direction cells around

@@ -27,7 +27,13 @@ int c3o_poa_last_scores(int32_t* out, int cap) { int n = g_nscores < cap ? g_nsc
 #define SNK 1
 
 /* diagnostic row statistics (tools/poa_row_stats.py; single-threaded use only): what kinds of DP rows the alignments of a
- * batch consist of, as the HIP kernel classifies them, and how far real cell values sit below their row's maximum */
+ * batch consist of, as the HIP kernel classifies them, and how far real cell values sit below their row's maximum.
+ * How much of an input the tie rules decide (tests/low_complexity_cases.py):
+ *   [55] rows (of [0], the source row is not counted) whose maximum sits in more than one column (left != right): the band
+ *        hint of their successors spans the tie
+ *   [62] cells whose winning value is reached by more than one of its candidates: M / E1 / E2 in the vertical part or
+ *        ht / F1 / F2 in the horizontal part; a winning value at the C3O_NEG / C3O_NEG2 sentinels is no tie.  A cell counts once
+ *   [63] all cells looked at for [62]: every cell of the rows of [0] (equals [1]) */
 int64_t c3o_poa_rowstats[64];
 int c3o_poa_rowstats_on = 0;
 
@@ -104,6 +110,7 @@ static int poa_align(const c3o_graph* g, const uint8_t* q, int Q, const c3o_para
   m.rend = (int*)malloc(sizeof(int) * (size_t)n);
   m.roff = (int64_t*)malloc(sizeof(int64_t) * (size_t)n);
   int32_t* ht = (int32_t*)malloc(sizeof(int32_t) * (size_t)(Q + 2));
+  uint8_t* tie = c3o_poa_rowstats_on ? (uint8_t*)malloc((size_t)(Q + 2)) : NULL;      /* row statistics [62] only */
 
   for (int idx = 0; idx < n; ++idx) {
     int v = g->order[idx];
@@ -159,6 +166,7 @@ static int poa_align(const c3o_graph* g, const uint8_t* q, int Q, const c3o_para
       else if (e1b >= e2b) { hts = 1; t = e1b; }
       else { hts = 2; t = e2b; }
       ht[c] = t; E1[c] = e1b; E2[c] = e2b;
+      if (tie) tie[c] = t > C3O_NEG / 2 && (M == t) + (e1b == t) + (e2b == t) > 1;
       d = (uint32_t)mp | ((uint32_t)e1p << 8) | ((uint32_t)e2p << 16) | ((uint32_t)hts << 24)
           | ((uint32_t)e1x << 28) | ((uint32_t)e2x << 29);
       D[c] = d;
@@ -180,6 +188,7 @@ static int poa_align(const c3o_graph* g, const uint8_t* q, int Q, const c3o_para
       else if (f1 >= f2) { hs = 1; h = f1; }
       else { hs = 2; h = f2; }
       H[c] = h;
+      if (tie && v != SRC && h > C3O_NEG / 2 && (ht[c] == h) + (f1 == h) + (f2 == h) > 1) tie[c] = 1;
       D[c] |= ((uint32_t)hs << 26) | ((uint32_t)f1x << 30) | ((uint32_t)f2x << 31);
       if (h > best) { best = h; left = right = beg + c; }
       else if (h == best) right = beg + c;
@@ -195,6 +204,8 @@ static int poa_align(const c3o_graph* g, const uint8_t* q, int Q, const c3o_para
       }
       int pwd = m.rend[idx - 1] - m.rbeg[idx - 1] + 1, sh = beg - m.rbeg[idx - 1];
       S[0]++; S[1] += wd;
+      if (left != right) S[55]++;
+      if (tie) { for (int c = 0; c < wd; ++c) S[62] += tie[c]; S[63] += wd; }
       { int f6 = 0, f4 = 0;
         for (int k = 0; k < g->n_out[v]; ++k) { int t = g->out_to[v * K + k]; int dd = (t == SNK) ? 99 : g->index[t] - idx; if (dd > 5) f6 = 1; if (dd > 3) f4 = 1; }
         if (f6) S[56] += wd;
@@ -268,7 +279,7 @@ static int poa_align(const c3o_graph* g, const uint8_t* q, int Q, const c3o_para
     for (int k = r.n - 1; k >= 0; --k) op_push(ops, r.node[k], r.q[k]);
     free(r.node); free(r.q);
   }
-  free(rem); free(mpl); free(mpr); free(ht);
+  free(rem); free(mpl); free(mpr); free(ht); free(tie);
   free(m.H); free(m.E1); free(m.E2); free(m.D); free(m.rbeg); free(m.rend); free(m.roff);
   return rc;
 }

@@ -238,10 +238,9 @@ def test_the_largest_admitted_window_length():
 @pytest.mark.parametrize("mode", ["off", "verify"])
 def test_band_modes(wl, mode):
     """off: the unbanded descriptor builder and rows for every layer; verify: band and full matrix of every accepted layer compared
-    on the device (it counts their cells twice: the polish cells are compared with the default run's counters only where no
-    layer is banded)"""
+    on the device (the second alignment of a layer is computed, not counted: cells_polish stays the oracle's)"""
     _oracle(wl)
-    t = _check(wl, env={"C3_DEBUG_BAND": mode}, oracle_cells=mode == "off" or wl == 100)[2]
+    t = _check(wl, env={"C3_DEBUG_BAND": mode})[2]
     assert t["n_band_mismatch"] == 0
     if mode == "off" or wl == 100:
         assert t["n_band_layers"] == 0 and t["n_band_fallback"] == 0

@@ -30,3 +30,5 @@ print("  rows wider than 128: <=160 %.1f%% <=192 %.1f%% <=256 %.1f%% >256 %.1f%%
 print("  lowest real cell below its row maximum: %d; rows by that depth >-200 %.2f%% >-400 %.2f%% >-800 %.2f%% >-1600 %.3f%% below %.4f%%"
       % ((s[40],) + tuple(100 * x / rows for x in s[41:46])))
 print("  largest step of the row maximum between consecutive rows: %d" % s[47])
+print("  ties: rows whose maximum sits in more than one column %.2f%%; cells whose winning value has more than one source %.1f%% (of %d)"
+      % (100 * s[55] / max(rows, 1), 100 * s[62] / max(s[63], 1), s[63]))
