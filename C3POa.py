@@ -57,6 +57,10 @@ def parse_args(argv=None):
                         help="Where a BGZF .gz or a .bam input is inflated: zlib threads on the host (default), or the GPU (the "
                              "inflater threads' cores go back to the parser and the writers). Any other gzip file is read "
                              "as before.")
+    parser.add_argument("--gunzip", choices=["host", "gpu"], default="host",
+                        help="Where a plain gzip input (one deflate stream, as MinKNOW, guppy and gzip write it) is inflated: one zlib "
+                             "stream on the host (default), or in parallel on the GPU (needs --inflate gpu). BGZF, .bam and plain text are "
+                             "read as without it.")
     parser.add_argument("--parse", choices=["host", "gpu"], default="host",
                         help="Where the records of a BGZF .gz or a .bam input are found: the reader's parser thread on the host "
                              "(default), or the GPU, where --inflate gpu has left the text (needs --inflate gpu; strict "
@@ -77,6 +81,8 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.bgzf:
         args.compress_output = True
+    if args.gunzip == "gpu" and args.inflate != "gpu":
+        parser.error("--gunzip gpu needs --inflate gpu: it says how a plain gzip input is inflated on the GPU")
     if args.parse == "gpu" and args.inflate != "gpu":
         parser.error("--parse gpu needs --inflate gpu: records are parsed on the GPU only where the text was inflated there")
     return args

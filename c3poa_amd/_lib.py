@@ -244,7 +244,12 @@ def _prototypes():
         "c3_bgzf_scan": (i, [vp, i64, pi64, pi64]),
         "c3_bgzf_decompress": (i, [vp] + zz),
         "c3_bgzf_decompress_host": (i, zz),
+        "c3_gunzip": (i, [vp] + zz),
+        "c3_gunzip_host": (i, zz + [i64]),
+        "c3_gunzip_stats": (i, [pi64, i]),
         "c3_reader_open_inflate": (i, [cp, i, i, pvp]),
+        "c3_reader_gunzip_on_device": (i, [vp, i]),
+        "c3_reader_gunzip_stats": (i, [vp, pi64, i]),
         "c3_reader_inflate_wait": (dbl, [vp]),
         "c3_write_group_bgzf": (i, [vp] + wg),
         "c3_write_consensus_fastq_bgzf": (i, [vp] + wq),
@@ -1007,13 +1012,16 @@ class Reader(_Owned):
     a ValueError of next naming the record, its inflated byte offset and the reason)"""
     _owns = ("r", "c3_reader_close")
 
-    def __init__(self, path, n_sets=3, names_only=False, byte_range=None, inflate_device=None, parse_device=False, stage_device=False):
+    def __init__(self, path, n_sets=3, names_only=False, byte_range=None, inflate_device=None, parse_device=False, stage_device=False,
+                 gunzip_device=False):
         """byte_range = (beg, end): only the records that START inside [beg, end) (plain files; c3_reader_open_range)
         inflate_device = d: a BGZF file is inflated by k_inflate on device d (c3_reader_open_inflate; whole-file readers)
         parse_device: ... and its records are parsed there too (k_fastq, k_bam for a .bam; c3_reader_parse_on_device).  C3Error with code
         E_STATE when the reader is not one of a BGZF file with inflate_device
         stage_device: ... and the bases and qualities of its groups stay there (c3_reader_stage_on_device): a device group has
-        hb.dev (c3_device_batch) and no seqs / quals; after a departure the groups are host groups (hb.dev is None)"""
+        hb.dev (c3_device_batch) and no seqs / quals; after a departure the groups are host groups (hb.dev is None)
+        gunzip_device: a plain gzip file (not BGZF) is inflated by the k_gunzip kernels on inflate_device instead of gzread
+        (c3_reader_gunzip_on_device); C3Error with code E_STATE on any other reader"""
         self.lib = load()
         self.r = C.c_void_p()
         self.n_sets, self._cur, self.parse_device = max(1, int(n_sets)), -1, bool(parse_device)
@@ -1032,7 +1040,8 @@ class Reader(_Owned):
         if names_only:
             self.lib.c3_reader_names_only(self.r, 1)
         self.stage_device = False
-        for want, call in ((parse_device, "c3_reader_parse_on_device"), (stage_device, "c3_reader_stage_on_device")):
+        for want, call in ((gunzip_device, "c3_reader_gunzip_on_device"), (parse_device, "c3_reader_parse_on_device"),
+                           (stage_device, "c3_reader_stage_on_device")):
             rc = getattr(self.lib, call)(self.r, 1) if want else 0
             if rc != 0:
                 e = _c3_error(rc, self._err, call)
@@ -1082,6 +1091,12 @@ class Reader(_Owned):
     def inflate_wait(self):
         """seconds the parser waited for inflated bytes of a BGZF file (either inflater); 0 for other files"""
         return float(self.lib.c3_reader_inflate_wait(self.r))
+
+    def gunzip_stats(self):
+        """the counters of gunzip_stats() summed over the stretches a gunzip_device reader has inflated so far"""
+        v = (C.c_int64 * len(GUNZIP_STATS))()
+        self.lib.c3_reader_gunzip_stats(self.r, v, len(GUNZIP_STATS))
+        return dict(zip(GUNZIP_STATS, (int(x) for x in v)))
 
     def _stats(self, fn):
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
@@ -1275,6 +1290,42 @@ def bgzf_decompress_host(data):
     return _bgzf_call(load().c3_bgzf_decompress_host, (), data, _bgzf_inflated)
 
 
+# ---- gzip input (include/c3poa.h "gzip input") ----
+GUNZIP_STATS = ("pieces", "candidates", "accepted", "rejected", "relaunches", "full_slabs", "fallback_bytes", "stretches")
+
+
+def gunzip_stats():
+    """c3_gunzip_stats: the counters of this thread's last gunzip call, by name"""
+    v = (C.c_int64 * len(GUNZIP_STATS))()
+    rc = load().c3_gunzip_stats(v, len(GUNZIP_STATS))
+    if rc != 0:
+        raise _c3_error(rc)
+    return dict(zip(GUNZIP_STATS, (int(x) for x in v)))
+
+
+def _gunzip_call(fn, first, data, last):
+    """fn(*first, src, n, dst, cap, &out_len, *last): the text of the gzip file `data`.  A gzip file does not say how long its
+    text is (ISIZE is the last member's, modulo 2^32), so cap grows while the call answers E_ARG, up to deflate's 1032 : 1"""
+    src = _b(data)
+    top = 1032 * len(src) + 65536
+    cap = min(top, max(1 << 16, 6 * len(src)))
+    while True:
+        out = C.create_string_buffer(cap)
+        olen = C.c_int64(0)
+        rc = fn(*first, src, len(src), out, cap, C.byref(olen), *last)
+        if rc == 0:
+            return out.raw[:olen.value]
+        if rc != E_ARG or cap >= top or not len(src):
+            raise _c3_error(rc)
+        cap = min(top, 4 * cap)
+
+
+def gunzip_host(data, piece=0):
+    """c3_gunzip_host: the text of the gzip file `data` (any RFC 1952 file); the host statement of Bgzf.gunzip (no zlib).
+    piece > 0: the piece size in compressed bytes instead of C3_GUNZIP_PIECE / the default"""
+    return _gunzip_call(load().c3_gunzip_host, (), data, (int(piece),))
+
+
 class Bgzf(_Owned):
     """c3_bgzf: k_bgzf on one device (device buffers and a stream of its own; one per thread)"""
     _owns = ("z", "c3_bgzf_destroy")
@@ -1292,6 +1343,10 @@ class Bgzf(_Owned):
     def decompress(self, data):
         """c3_bgzf_decompress: the text of the BGZF members `data` (k_inflate); C3Error with code E_DATA on a damaged member"""
         return _bgzf_call(self.lib.c3_bgzf_decompress, (self.z,), data, _bgzf_inflated)
+
+    def gunzip(self, data):
+        """c3_gunzip: the text of the gzip file `data` inflated by the k_gunzip kernels; C3Error with code E_DATA on damage"""
+        return _gunzip_call(self.lib.c3_gunzip, (self.z,), data, ())
 
     def fastq_parse(self, text, at_eof=False, min_len=0, text_offset=0, caps=None):
         """c3_fastq_parse: the strict FASTQ records of `text` found and gathered by k_fastq (a FastqParse); text_offset

@@ -2,6 +2,7 @@
 // text, the argument checks that a device call and its host statement both apply, and the reader's private calls into the
 // stream unit.  No hip_runtime.h here.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/c3poa.h"
 
@@ -49,3 +50,13 @@ extern "C" int c3_bgzf_stretch_stage(c3_bgzf* z, int slot, int64_t r0, int64_t r
 extern "C" int c3_bgzf_set_get(const c3_bgzf* z, int set, const char** d_seqs, const char** d_quals, int* device);
 // the --bgzf writers' private call (c3_stream.hip, called by c3_writer.cpp): pieces p[0..np) compressed as one text
 extern "C" int c3_bgzf_compress_pieces(c3_bgzf* z, const char* const* p, const int64_t* len, int np, char* dst, int64_t cap, int64_t* out_len);
+// the reader's gzip stream (c3_gunzip_dev.hip, called by c3_reader_bgzf.cpp): a plain gzip file read and inflated stretch by
+// stretch by the k_gunzip kernels on z's device.  _next: the stretch's bytes on the host; _next_parse: the stretch left on the
+// device behind the carry in the slot's text and parsed there (c3_bgzf_stretch_parse's rule and tables).  *eof: the file ends
+// behind this stretch.  Damage: C3_E_DATA, text in c3_last_error(NULL).  _stats: the counters of c3_gunzip_stats summed so far
+struct c3_gunzip_stream;
+extern "C" int c3_gunzip_stream_open(c3_bgzf* z, const char* path, c3_gunzip_stream** out);
+extern "C" int c3_gunzip_stream_next(c3_gunzip_stream* s, const char** text, int64_t* bytes, int* eof);
+extern "C" int c3_gunzip_stream_next_parse(c3_gunzip_stream* s, int slot, int64_t carry_from, int64_t carry_len, int* eof, int64_t* bytes, c3_fq_stretch* fq);
+extern "C" void c3_gunzip_stream_stats(const c3_gunzip_stream* s, int64_t* v, int n);
+extern "C" void c3_gunzip_stream_close(c3_gunzip_stream* s);

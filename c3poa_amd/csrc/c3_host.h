@@ -34,6 +34,9 @@ int post_sizes(c3_handle* h, const c3_post_args* a, PostArgs& p, std::vector<int
 int post_write(c3_handle* h, PostArgs& p, int64_t need);
 int adapters_device(c3_handle* h, const C3Batch& b, int64_t max_len, int32_t* d_out);
 int bgzf_inflate_to_device(c3_bgzf* z, const char* src, int64_t n, int64_t nm, uint8_t* d_dst, int64_t* out_len);    // c3_stream.hip
+// a reader's device stretch in two halves around its inflater (c3_stream.hip; the gzip stream of c3_gunzip_dev.hip uses them)
+int stretch_text_begin(c3_bgzf* z, int slot, int64_t carry_from, int64_t carry_len, int64_t bytes, bool bam, uint8_t** d_at);
+int stretch_text_parse(c3_bgzf* z, int slot, int64_t total, bool bam, int at_start, int at_eof, c3_fq_stretch* out);
 // k_fasta on a text that lies on the device, the gather of its records, the index sets of a search (c3_scans.hip)
 namespace fa { enum { FA_TEXT, FA_CNT, FA_NL, FA_LSE, FA_LDST, FA_BSUM, FA_HDR, FA_OFF, FA_NOFF, FA_RECL, FA_HASH, FA_NAMES, FA_SEQS, FA_KREC, FA_ROFF,
                       FA_OUT, FA_ANAMES, FA_ANO, FA_BNAMES, FA_BNO, FA_N }; }      // the slots of c3_handle::d_fa
@@ -286,4 +289,6 @@ struct c3_bgzf {
   // the reader's device buffer sets (c3_reader_stage_on_device): the home of a device group, filled from the slots on copy_stream
   struct DevSet { DBuf seqs, quals; };
   std::vector<DevSet> dsets;
+  // k_gunzip (first use): the file, the symbol arena, candidates, jobs / results, segments / chunks / chunk results, windows, bytes
+  DBuf gz_comp, gz_arena, gz_cand, gz_jobs, gz_res, gz_segs, gz_chunks, gz_cres, gz_wins, gz_out;
 };

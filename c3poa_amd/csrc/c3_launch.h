@@ -1,6 +1,6 @@
 // c3_launch.h -- the one declaration of every kernel launcher and kernel query.  The host units call through it, and every k_*.hip
 // that defines a launcher includes it too, so a prototype that drifts from its definition fails to compile in the kernel's own
-// translation unit.  Declarations only: the argument blocks are named, not defined (c3_args.h, c3_post.h, c3_inflate.h, c3_fastq.h, c3_bam.h, c3_fasta.h, c3_emit.h, c3_fastx.h, c3_dsplit.h).
+// translation unit.  Declarations only: the argument blocks are named, not defined (c3_args.h, c3_post.h, c3_inflate.h, c3_fastq.h, c3_bam.h, c3_fasta.h, c3_emit.h, c3_fastx.h, c3_dsplit.h, c3_gunzip.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -8,6 +8,7 @@
 
 struct ConkArgs; struct AdapterArgs; struct PostArgs; struct PeaksArgs; struct PoaArgs; struct PoaPairArgs; struct PrepArgs; struct WinArgs; struct StitchArgs;
 struct ZeroArgs; struct QvArgs; struct C3BgzfMember; struct C3FqHdr; struct C3BamHdr; struct C3BamTile; struct FaArgs; struct EmitArgs; struct FxArgs; struct DsArgs;
+struct C3GzJob; struct C3GzRes; struct C3GzSeg; struct C3GzChunk;
 
 extern "C" {
 void c3k_launch_conk(const ConkArgs*, int, int, int, hipStream_t);                                                          // k_conk.hip
@@ -33,6 +34,11 @@ void c3k_launch_qv(const QvArgs*, int, hipStream_t);                            
 int c3k_qv_lds_max(void);
 void c3k_launch_bgzf(const uint8_t*, long long, int, uint8_t*, int*, uint8_t*, hipStream_t);                                // k_bgzf.hip
 void c3k_launch_inflate(const uint8_t*, const C3BgzfMember*, int, uint8_t*, int2*, hipStream_t);                            // k_inflate.hip
+void c3k_launch_gunzip_find(const uint8_t*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t*, hipStream_t);                  // k_gunzip.hip
+void c3k_launch_gunzip_decode(const uint8_t*, int64_t, const C3GzJob*, int, uint16_t*, C3GzRes*, hipStream_t);
+void c3k_launch_gunzip_window(const uint16_t*, const C3GzSeg*, int, uint8_t*, hipStream_t);
+void c3k_launch_gunzip_resolve(const uint16_t*, const C3GzSeg*, const C3GzChunk*, int, const uint8_t*, uint8_t*, uint2*, hipStream_t);
+int c3k_gunzip_chunk(void);
 void c3k_launch_fastq_count(const uint8_t*, uint32_t, uint32_t, int32_t*, int, C3FqHdr*, hipStream_t);                      // k_fastq.hip
 void c3k_launch_fastq_lines(const uint8_t*, uint32_t, uint32_t, const int32_t*, int32_t*, hipStream_t);
 void c3k_launch_fastq_records(const uint8_t*, uint32_t, uint32_t, const int32_t*, int, int, int, int, int32_t*, int32_t*, long long*,

@@ -34,6 +34,8 @@ struct BatchSet {
 
 struct c3_reader {
   FILE* fp = nullptr; gzFile gz = nullptr; Bgzf* bz = nullptr;
+  // c3_reader_open_inflate on plain gzip: the device it was given (c3_reader_gunzip_on_device hands it to bz) and the path
+  c3_bgzf* gz_dev = nullptr; std::string path;
   std::vector<char> buf; size_t beg = 0, end = 0; bool eof = false;
   std::vector<BatchSet> sets; int cur = -1;
   std::string err;
@@ -59,7 +61,7 @@ bool refill(c3_reader* r) {
   long got = r->bz ? bgzf_read(r->bz, r->buf.data() + r->end, room)
            : r->gz ? (long)gzread(r->gz, r->buf.data() + r->end, (unsigned)std::min<size_t>(room, 1u << 30))
                    : (long)fread(r->buf.data() + r->end, 1, room, r->fp);
-  if (got < 0 && r->bz) r->err = "BGZF input: a member is damaged (size, inflate or CRC)" + (r->bz->why.empty() ? std::string() : ": " + r->bz->why);
+  if (got < 0 && r->bz) r->err = r->bz->gs ? r->bz->why : "BGZF input: a member is damaged (size, inflate or CRC)" + (r->bz->why.empty() ? std::string() : ": " + r->bz->why);
   if (got <= 0) { r->eof = true; return false; }
   r->end += (size_t)got;
   return true;
@@ -120,6 +122,7 @@ extern "C" void c3_host_free(void* p) {
 extern "C" int c3_reader_open(const char* path, int n_sets, c3_reader** out) {
   if (!path || !out) return C3_E_ARG;
   c3_reader* r = new c3_reader();
+  r->path = path;
   size_t n = strlen(path);
   r->bam = n > 4 && strcmp(path + n - 4, ".bam") == 0;
   if (r->bam || (n > 3 && strcmp(path + n - 3, ".gz") == 0)) {
@@ -160,7 +163,8 @@ extern "C" int c3_reader_open_inflate(const char* path, int n_sets, int device, 
   if (r->bz) {
     r->bz->dev = z;
     if (const char* e = getenv("C3_INFLATE_STRETCH_MEMBERS")) { const int v = atoi(e); if (v >= 1 && v <= 4096) r->bz->stretch_members = (size_t)v; }
-  } else c3_bgzf_destroy(z);                                    // plain gzip / plain text: read as c3_reader_open reads it
+  } else if (r->gz) r->gz_dev = z;                              // plain gzip: read as c3_reader_open reads it unless c3_reader_gunzip_on_device follows
+  else c3_bgzf_destroy(z);                                      // plain text
   *out = r;
   return C3_E_OK;
 }
@@ -242,9 +246,10 @@ extern "C" int c3_reader_open_range(const char* path, int n_sets, int64_t beg, i
 
 extern "C" void c3_reader_close(c3_reader* r) {
   if (!r) return;
+  if (r->gz_dev) c3_bgzf_destroy(r->gz_dev);
   if (r->gz) gzclose(r->gz);
   if (r->fp) fclose(r->fp);
-  if (r->bz) { if (r->bz->pre_on) r->bz->pre.join(); if (r->bz->fp) fclose(r->bz->fp); if (r->bz->dev) c3_bgzf_destroy(r->bz->dev); delete r->bz; }
+  if (r->bz) { if (r->bz->pre_on) r->bz->pre.join(); if (r->bz->fp) fclose(r->bz->fp); if (r->bz->gs) c3_gunzip_stream_close(r->bz->gs); if (r->bz->dev) c3_bgzf_destroy(r->bz->dev); delete r->bz; }
   delete r;
 }
 
@@ -254,9 +259,35 @@ extern "C" void c3_reader_names_only(c3_reader* r, int names_only) { if (r) r->n
 
 extern "C" int c3_reader_parse_on_device(c3_reader* r, int on) {
   if (!r) return C3_E_ARG;
-  if (!r->bz || !r->bz->dev) { r->err = "c3_reader_parse_on_device: not a BGZF file opened by c3_reader_open_inflate"; return C3_E_STATE; }
+  if (!r->bz || !r->bz->dev) { r->err = "c3_reader_parse_on_device: not a BGZF file opened by c3_reader_open_inflate, nor a plain gzip file with c3_reader_gunzip_on_device"; return C3_E_STATE; }
   if (r->started) { r->err = "c3_reader_parse_on_device: after the first c3_reader_next"; return C3_E_STATE; }
   r->bz->parse_req = r->bz->parse_on = r->bz->dev_active = on != 0;
+  return C3_E_OK;
+}
+
+// a plain gzip file opened by c3_reader_open_inflate is inflated by the k_gunzip kernels on that device instead of gzread: the
+// reader becomes one of the BGZF kind (stretch loop, prefetch thread, device parser and device groups) whose stretches are what
+// the gzip stream inflates next
+extern "C" int c3_reader_gunzip_on_device(c3_reader* r, int on) {
+  if (!r) return C3_E_ARG;
+  if (r->bz && r->bz->gs) {
+    if (on) return C3_E_OK;
+    r->err = "c3_reader_gunzip_on_device: cannot be taken back"; return C3_E_STATE;
+  }
+  if (!r->gz || !r->gz_dev) { r->err = "c3_reader_gunzip_on_device: not a plain gzip file opened by c3_reader_open_inflate"; return C3_E_STATE; }
+  if (r->started) { r->err = "c3_reader_gunzip_on_device: after the first c3_reader_next"; return C3_E_STATE; }
+  if (!on) return C3_E_OK;
+  c3_gunzip_stream* gs = nullptr;
+  const int rc = c3_gunzip_stream_open(r->gz_dev, r->path.c_str(), &gs);
+  if (rc != C3_E_OK) { r->err = c3_last_error(nullptr); return rc; }
+  gzclose(r->gz); r->gz = nullptr;
+  r->bz = new Bgzf(); r->bz->gs = gs; r->bz->dev = r->gz_dev; r->gz_dev = nullptr;
+  return C3_E_OK;
+}
+
+extern "C" int c3_reader_gunzip_stats(const c3_reader* r, int64_t* v, int n) {
+  if (!r || !v || n < 0) return C3_E_ARG;
+  c3_gunzip_stream_stats(r->bz ? r->bz->gs : nullptr, v, n);
   return C3_E_OK;
 }
 
@@ -596,6 +627,7 @@ extern "C" int c3_reader_next_set(c3_reader* r, int set, int max_reads, int64_t 
     rc = r->bam ? fill_from_bam(g) : fill_from_text(g);
   }
   if (rc != C3_E_OK) return rc;
+  if (r->bz && r->bz->bad && r->bz->gs) { r->err = r->bz->why; return C3_E_DATA; }      // (c3_gunzip's text: member, offset, reason)
   if (r->bz && r->bz->bad) return fail(r, "BGZF input: a member is damaged (header, size, inflate or CRC)");      // never a silently short file
   g.finish(out);
   return C3_E_OK;

@@ -41,8 +41,34 @@ bool bgzf_inflate(const unsigned char* m, size_t msz, char* out, size_t osz) {
   return crc32(crc32(0L, Z_NULL, 0), (const unsigned char*)out, (unsigned)osz) == crc;
 }
 
+// a plain gzip file (c3_reader_gunzip_on_device): the next stretch of its stream, parsed on the device or brought to dec
+bool gunzip_next_stretch(Bgzf* bz, BgzfStretch* b) {
+  b->dend = 0; b->on_dev = false;
+  if (bz->eof) return false;
+  int eof = 0; int64_t bytes = 0;
+  if (bz->parse_on) {
+    const int rc = c3_gunzip_stream_next_parse(bz->gs, (int)(b - bz->st), bz->carry_from, bz->carry_len, &eof, &bytes, &b->fq);
+    if (rc != C3_E_OK) { bz->why = c3_last_error(nullptr); bz->bad = true; return false; }
+    if (eof) bz->eof = true;
+    if (bytes == 0 && bz->carry_len == 0) return false;          // (an empty file, or nothing behind the last stretch)
+    b->on_dev = true; b->next_rec = 0;
+    ++bz->n_dev;
+    return true;
+  }
+  if (bz->parse_req) ++bz->n_host;
+  const char* text = nullptr;
+  const int rc = c3_gunzip_stream_next(bz->gs, &text, &bytes, &eof);
+  if (rc != C3_E_OK) { bz->why = c3_last_error(nullptr); bz->bad = true; return false; }
+  if (eof) bz->eof = true;
+  if (bytes == 0) return false;
+  b->dec.assign(text, text + bytes);
+  b->dend = (size_t)bytes;
+  return true;
+}
+
 // next stretch of the file: up to `max_members` members read, located by their headers, inflated by b->threads threads
 bool bgzf_next_stretch(Bgzf* bz, BgzfStretch* b, size_t max_members = 512) {
+  if (bz->gs) return gunzip_next_stretch(bz, b);
   if (bz->dev) max_members = bz->stretch_members;               // one k_inflate launch: a wave per member
   b->comp.clear(); b->coff.clear(); b->csz.clear(); b->doff.clear();
   b->dend = 0;

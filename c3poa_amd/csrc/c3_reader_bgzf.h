@@ -31,6 +31,9 @@ struct BgzfStretch {
 };
 struct Bgzf {
   FILE* fp = nullptr;
+  // c3_reader_gunzip_on_device: not BGZF at all but a plain gzip file -- a stretch is what the gzip stream inflates next on dev
+  // (k_gunzip), brought to dec or left on the device for the parser; everything else here stays as it is
+  c3_gunzip_stream* gs = nullptr;
   int threads = 1;
   BgzfStretch st[2];                        // the stretch being parsed and the one being read + inflated beside it
   int cur = 0;

@@ -361,15 +361,13 @@ extern "C" int c3_bam_parse(c3_bgzf* z, const char* data, int64_t n, int at_star
 // members of comp; it stays on the device, is parsed there with min_len 0 (the group rule, min_len included, is the
 // reader's), and the record tables come back (c3_fq_stretch, c3_checks.h).  On return the slot holds the finished records
 // until it is loaded again.
-static int stretch_parse(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, int64_t carry_from, int64_t carry_len,
-                         bool bam, int at_start, int at_eof, c3_fq_stretch* out) {
-  if (!z || !out || slot < 0 || slot > 1 || ncomp < 0 || (ncomp > 0 && !comp) || carry_len < 0) return host_fail(C3_E_ARG, "c3_bgzf_stretch_parse: bad arguments");
-  memset(out, 0, sizeof *out);
-  int64_t nm = 0, ob = 0;
-  int rc = c3_bgzf_scan(comp, ncomp, &nm, &ob);
-  if (rc) return rc;
-  const int64_t total = carry_len + ob;
+// the two halves around the inflater (k_inflate here, the k_gunzip kernels in c3_gunzip_dev.hip): _begin sizes the slot's text for
+// the carry plus `bytes`, copies the carry and says where the inflated bytes go; _parse takes the finished text of `total` bytes
+int c3h::stretch_text_begin(c3_bgzf* z, int slot, int64_t carry_from, int64_t carry_len, int64_t bytes, bool bam, uint8_t** d_at) {
+  if (!z || slot < 0 || slot > 1 || carry_len < 0 || bytes < 0) return host_fail(C3_E_ARG, "c3_bgzf_stretch_parse: bad arguments");
+  const int64_t total = carry_len + bytes;
   if (total > C3_FASTQ_MAX_TEXT) return host_fail(C3_E_LIMIT, "c3_bgzf_stretch_parse: stretch longer than C3_FASTQ_MAX_TEXT");
+  int rc;
   if ((rc = bam ? bam_prepare(z) : fq_prepare(z)) != C3_E_OK) return rc;
   c3_bgzf::FqSlot& sl = z->fq[slot];
   const c3_bgzf::FqSlot& other = z->fq[slot ^ 1];
@@ -377,12 +375,13 @@ static int stretch_parse(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, 
   ZCHK(sl.text.ensure((size_t)total + 256), "stretch text");
   sl.text_n = 0;
   if (carry_len > 0) ZCHK(hipMemcpyAsync(sl.text.p, other.text.as<char>() + carry_from, (size_t)carry_len, hipMemcpyDeviceToDevice, z->stream), "carry");
-  if (nm > 0) {
-    int64_t got = 0;
-    rc = bgzf_inflate_members(z, comp, ncomp, nm, sl.text.as<uint8_t>() + carry_len, nullptr, &got);
-    if (rc) return rc;
-    if (got != ob) return host_fail(C3_E_DATA, "c3_bgzf_stretch_parse: inflated size differs from the headers");
-  }
+  *d_at = sl.text.as<uint8_t>() + carry_len;
+  return C3_E_OK;
+}
+
+int c3h::stretch_text_parse(c3_bgzf* z, int slot, int64_t total, bool bam, int at_start, int at_eof, c3_fq_stretch* out) {
+  int rc;
+  c3_bgzf::FqSlot& sl = z->fq[slot];
   sl.text_n = total;
   out->text_bytes = total;
   if (bam) {
@@ -412,6 +411,24 @@ static int stretch_parse(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, 
     out->off = sl.h_off; out->name_off = sl.h_name_off;
   }
   return C3_E_OK;
+}
+
+static int stretch_parse(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, int64_t carry_from, int64_t carry_len,
+                         bool bam, int at_start, int at_eof, c3_fq_stretch* out) {
+  if (!z || !out || slot < 0 || slot > 1 || ncomp < 0 || (ncomp > 0 && !comp) || carry_len < 0) return host_fail(C3_E_ARG, "c3_bgzf_stretch_parse: bad arguments");
+  memset(out, 0, sizeof *out);
+  int64_t nm = 0, ob = 0;
+  int rc = c3_bgzf_scan(comp, ncomp, &nm, &ob);
+  if (rc) return rc;
+  uint8_t* d_at = nullptr;
+  if ((rc = c3h::stretch_text_begin(z, slot, carry_from, carry_len, ob, bam, &d_at)) != C3_E_OK) return rc;
+  if (nm > 0) {
+    int64_t got = 0;
+    rc = bgzf_inflate_members(z, comp, ncomp, nm, d_at, nullptr, &got);
+    if (rc) return rc;
+    if (got != ob) return host_fail(C3_E_DATA, "c3_bgzf_stretch_parse: inflated size differs from the headers");
+  }
+  return c3h::stretch_text_parse(z, slot, carry_len + ob, bam, at_start, at_eof, out);
 }
 
 extern "C" int c3_bgzf_stretch_parse(c3_bgzf* z, int slot, const char* comp, int64_t ncomp, int64_t carry_from, int64_t carry_len,

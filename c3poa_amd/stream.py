@@ -82,7 +82,7 @@ N_SETS = 5                                          # (a sixth set would cover e
 class Options:
     """every switch of a run, read ONCE from args and the environment: nothing below looks at either again"""
     reads: str; out_path: str; lencutoff: int; mdistcutoff: int; zero: bool; zero_max_cells: int
-    compress: bool; bgzf: bool; qv: bool; emit_gpu: bool; inflate_gpu: bool; parse_gpu: bool
+    compress: bool; bgzf: bool; qv: bool; emit_gpu: bool; inflate_gpu: bool; parse_gpu: bool; gunzip_gpu: bool
     batch_reads: int; batch_fixed: bool; n_work: int; readers_per_gpu: int; min_range: int
     devices: tuple                                  # worker -> physical device
 
@@ -107,6 +107,8 @@ class Options:
             # as well) and the writer only appends the finished streams
             emit_gpu=getattr(args, "emit", "host") == "gpu",
             inflate_gpu=getattr(args, "inflate", "host") == "gpu", parse_gpu=getattr(args, "parse", "host") == "gpu",
+            # --gunzip gpu: a plain gzip input is inflated by the k_gunzip kernels instead of one zlib stream (needs --inflate gpu)
+            gunzip_gpu=getattr(args, "gunzip", "host") == "gpu",
             batch_reads=gpu_batch if gpu_batch > 0 else max(int(args.groupSize), GPU_BATCH_READS), batch_fixed=gpu_batch > 0, n_work=n_work,
             readers_per_gpu=max(1, int(env.get("C3_READERS_PER_GPU", READERS_PER_GPU))), min_range=int(env.get("C3_MIN_RANGE_BYTES", MIN_RANGE_BYTES)),
             devices=tuple(devices))
@@ -184,16 +186,20 @@ def open_readers(opt):
     n_ranges = max(1, min(opt.n_work * opt.readers_per_gpu, size // max(opt.min_range, 1))) if splittable else 1
     # --inflate gpu: the (single, whole-file) reader of a .gz or .bam input inflates its BGZF stretches with k_inflate on worker
     # 0's device instead of zlib threads; any other gzip file has no member sizes to split on and is read as before
-    inflate_dev, parse_dev = None, False
+    inflate_dev, parse_dev, gunzip_dev = None, False, False
     if opt.inflate_gpu and zipped:
-        if _is_bgzf(opt.reads):
+        if opt.gunzip_gpu and str(opt.reads).endswith(".gz") and not _is_bgzf(opt.reads):
+            # --gunzip gpu: plain gzip inflated in parallel on worker 0's device (k_gunzip); with --parse gpu its text stays there
+            # for k_fastq, as a BGZF file's does
+            inflate_dev, parse_dev, gunzip_dev = opt.devices[0], opt.parse_gpu, True
+        elif _is_bgzf(opt.reads):
             # --parse gpu: ... and its records are found there too (k_fastq; k_bam for a .bam); only the finished arrays come to the host
             inflate_dev, parse_dev = opt.devices[0], opt.parse_gpu
         else:
             print("C3POa: --inflate gpu: %s is gzip but not BGZF (no member size in front); only BGZF can be inflated on the GPU, the file is read as before" % opt.reads, file=sys.stderr)
 
     def whole_file():
-        return [_lib.Reader(opt.reads, n_sets=N_SETS, inflate_device=inflate_dev, parse_device=parse_dev)], 1
+        return [_lib.Reader(opt.reads, n_sets=N_SETS, inflate_device=inflate_dev, parse_device=parse_dev, gunzip_device=gunzip_dev)], 1
     if n_ranges == 1:
         return whole_file()
     cuts = [size * k // n_ranges for k in range(n_ranges)] + [-1]
@@ -529,6 +535,12 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
         timers.put(inflate_wait=sum(r.inflate_wait() for r in readers))         # BGZF input: the parser waiting for inflated bytes
         if readers[0].parse_device:                 # --parse gpu: stretches parsed on the device / host, records from the device
             timers.put(**dict(zip(("parse_stretches_device", "parse_stretches_host", "parse_records_device"), (sum(x) for x in zip(*(r.parse_stats() for r in readers))))))
+        if opt.gunzip_gpu:                          # --gunzip gpu: what went through the serial fallback instead of the kernels
+            gz = readers[0].gunzip_stats()
+            if gz["fallback_bytes"]:
+                print("C3POa: --gunzip gpu: %d bytes of the input (%d stretches, %d block starts found) were inflated serially on the host: "
+                      "streams of fixed or stored blocks, or of very many members, are read faster with --gunzip host"
+                      % (gz["fallback_bytes"], gz["stretches"], gz["candidates"]), file=sys.stderr)
         if keep_pinned:                             # one-shot process (the CLI): process teardown releases the page-locked buffers
             kept = readers + pipe.emit_bufs         # ... and the page-locked arenas of --emit gpu likewise
             _KEPT.extend(kept)

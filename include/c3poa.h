@@ -449,10 +449,43 @@ int c3_bgzf_compress_host(const char* src, int64_t n, char* dst, int64_t cap, in
 int c3_bgzf_scan(const char* src, int64_t n, int64_t* n_members, int64_t* out_bytes);
 int c3_bgzf_decompress(c3_bgzf* z, const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len);
 int c3_bgzf_decompress_host(const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len);
+/* ---- gzip input ----
+ * A plain gzip file (RFC 1952: any header fields, members back to back, stored, fixed and dynamic blocks; no BC size field
+ * needed) inflated in parallel: the compressed bytes are cut into pieces of C3_GUNZIP_PIECE bytes (environment, read at
+ * every call; default 4 096, at least 64), every piece but the first looks for the first bit at which a dynamic-Huffman
+ * block header parses and decodes from there into 16-bit symbols (a byte, or 0x8000 | p = byte p of the unknown 32 KiB in
+ * front of it), a piece is accepted exactly when the accepted piece before it stopped at its first bit, the 32 KiB windows
+ * go down the chain, and the symbols become bytes.  A wrong guess costs time, never a byte: where the chain breaks one
+ * piece is decoded again from the true position (at most 16 times per stretch of 32 MiB; past that, and in a stretch
+ * without any candidate, the rest of the stretch is decoded serially on the host; both are counted).  The output is what
+ * zlib delivers, member after member; CRC-32 and ISIZE of every member are compared.  Damage is C3_E_DATA with a
+ * c3_last_error(NULL) text naming the member, its file offset and the reason; never a short or altered result.
+ * c3_gunzip runs the k_gunzip kernels on the device of a c3_bgzf with the whole file in memory; c3_gunzip_host is its host
+ * statement (the same procedure and decoder by plain loops on one CPU thread, no zlib; piece > 0 overrides the
+ * environment).  Null arguments, a null handle and a cap below the inflated size return C3_E_ARG -- before anything is
+ * launched where the last member's ISIZE already shows it, otherwise when the stretch that would cross cap is reached;
+ * n == 0 is success with out_len = 0.  (The early answer trusts the file's last four bytes: a file whose only damage is an
+ * ISIZE above cap gets C3_E_ARG, and C3_E_DATA once cap has grown past it.)
+ * c3_gunzip_stats: the first n of the calling thread's counters of its last c3_gunzip / c3_gunzip_host call, in this
+ * order: pieces, pieces with a candidate, candidates accepted, candidates rejected (accepted + rejected = candidates),
+ * relaunches, full slabs, bytes inflated by the serial fallback, stretches. */
+int c3_gunzip(c3_bgzf* z, const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len);
+int c3_gunzip_host(const char* src, int64_t n, char* dst, int64_t cap, int64_t* out_len, int64_t piece);
+int c3_gunzip_stats(int64_t* v, int n);
 /* c3_reader_open, but a BGZF file's stretches are inflated by k_inflate on `device` (a c3_bgzf owned by the reader)
  * instead of zlib threads; a file that is not BGZF (plain gzip, plain text) is read exactly as c3_reader_open reads it.
  * C3_E_NO_DEVICE without a usable GPU: asking for the device never falls back to zlib. */
 int c3_reader_open_inflate(const char* path, int n_sets, int device, c3_reader** out);
+/* c3_reader_gunzip_on_device(r, 1): a plain gzip file (not BGZF) opened by c3_reader_open_inflate is inflated by the k_gunzip
+ * kernels on that device instead of gzread: the file is read and inflated stretch by stretch (C3_GUNZIP_PIECE and the other
+ * variables are read here), the next stretch on a thread of its own while the parser works, and the groups are the ones the
+ * plain reader delivers.  With it c3_reader_parse_on_device and c3_reader_stage_on_device are valid on such a reader too: the
+ * inflated text stays on the device for k_fastq, departures as on BGZF.  c3_reader_inflate_wait counts for it.  Damage fails
+ * c3_reader_next with C3_E_DATA and c3_gunzip's text.  Before the first group, and not taken back; anything else is
+ * C3_E_STATE with a text.  Without the call every reader is as before.  c3_reader_gunzip_stats: the counters of
+ * c3_gunzip_stats summed over the stretches inflated so far. */
+int c3_reader_gunzip_on_device(c3_reader* r, int on);
+int c3_reader_gunzip_stats(const c3_reader* r, int64_t* v, int n);
 /* seconds the parser has waited for inflated bytes of a BGZF file so far, with either inflater (C3_STREAM_STATS); 0 for other files */
 double c3_reader_inflate_wait(const c3_reader* r);
 /* c3_write_group / c3_write_consensus_fastq with each file's text of the call (all records, in record order) compressed

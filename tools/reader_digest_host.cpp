@@ -34,6 +34,12 @@ int c3_bgzf_sets_create(c3_bgzf*, int) { return C3_E_NO_DEVICE; }
 int c3_bgzf_set_reserve(c3_bgzf*, int, int64_t, int64_t) { return C3_E_NO_DEVICE; }
 int c3_bgzf_stretch_stage(c3_bgzf*, int, int64_t, int64_t, char*, int, int64_t) { return C3_E_NO_DEVICE; }
 int c3_bgzf_set_get(const c3_bgzf*, int, const char**, const char**, int*) { return C3_E_NO_DEVICE; }
+struct c3_gunzip_stream;
+int c3_gunzip_stream_open(c3_bgzf*, const char*, c3_gunzip_stream**) { return C3_E_NO_DEVICE; }
+int c3_gunzip_stream_next(c3_gunzip_stream*, const char**, int64_t*, int*) { return C3_E_NO_DEVICE; }
+int c3_gunzip_stream_next_parse(c3_gunzip_stream*, int, int64_t, int64_t, int*, int64_t*, c3_fq_stretch*) { return C3_E_NO_DEVICE; }
+void c3_gunzip_stream_stats(const c3_gunzip_stream*, int64_t*, int) {}
+void c3_gunzip_stream_close(c3_gunzip_stream*) {}
 }
 
 static uint64_t fnv(uint64_t h, const void* p, size_t n) {
