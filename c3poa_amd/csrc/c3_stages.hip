@@ -269,12 +269,17 @@ static int run_poa(c3_handle* h) {
   for (int i : h->work) { max_sum = std::max(max_sum, h->sum[i].sum_sub); max_ns = std::max(max_ns, h->sum[i].n_sub); max_q = std::max(max_q, h->sum[i].max_sub); }
   const int Ncap_full = max_sum + 8, K = max_ns + 1, Pcap = max_sum + 8;
   const int w = h->cfg.poa_band_b + (int)(h->cfg.poa_band_f * max_q);
-  long long cells_full = (long long)(2 * max_q + 2) * (2 * w + 1 + max_q / 5);
-  if (max_ns < 2) cells_full = 64;
-  if (cells_full > 0x7fffff00LL) cells_full = 0x7fffff00LL;
   // typical need: every further subread adds ~12 % nodes (mismatch siblings + insertions) to a graph of max_q nodes; a row
   // holds 2w+1 cells plus the drift between the row's nominal column and the argmax of its predecessors
   const double nodes_typ = (double)max_q * (1.0 + 0.15 * std::max(0, max_ns - 1));
+  // rows of the full-size arena: one per node.  Twice the longest subread holds the graph of a few subreads; a deep read's graph
+  // grows with every subread (250 subreads of 240 bases at 12 % errors: 845 rows per alignment on average), so 1.3 x the typical
+  // node count where that is more (from five subreads per read on), within the node capacity of the pass.  At 2 * max_q + 2
+  // alone, reads of 200 and more subreads overflowed every pass and ended as C3_ST_LIMIT: DESIGN.md 3, tests/test_gpu_deep_reads.py
+  const long long rows_full = std::max<long long>(2LL * max_q + 2, std::min<long long>(Ncap_full, (long long)(1.3 * nodes_typ)));
+  long long cells_full = rows_full * (2 * w + 1 + max_q / 5);
+  if (max_ns < 2) cells_full = 64;
+  if (cells_full > 0x7fffff00LL) cells_full = 0x7fffff00LL;
   int Ncap = (int)std::min<double>(Ncap_full, 1.3 * nodes_typ + 256);
   long long cells = std::min<long long>(cells_full, (long long)(1.5 * nodes_typ * (2 * w + 12)) + 4096);
   if (const char* e_ = getenv("C3_DEBUG_POA_SMALL")) { Ncap = std::min(Ncap_full, std::max(64, atoi(e_))); cells = std::min<long long>(cells_full, 16LL * Ncap); }   // test hook: forces the second pass

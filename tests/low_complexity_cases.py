@@ -37,6 +37,8 @@ import numpy as np
 from c3poa_amd import synth
 from c3poa_amd.seqio import revcomp
 
+from deep_read_cases import concatemer
+
 Case = collections.namedtuple("Case", "name subs quals front tail cfg group tract")
 
 QMAX = 1792                     # longest subread k_poa_pair takes
@@ -211,11 +213,7 @@ CASES = _build()
 GROUPS = tuple(collections.OrderedDict((c.group, None) for c in CASES))
 
 
-def _concatemer(rng, splint, ins, n, k0, k1, err=0.1):
-    """tests/test_gpu_edge_cases._concatemer over a given insert"""
-    clean = ins[len(ins) - k0:] + (splint + ins) * n + splint + ins[:k1]
-    s, q = synth._mutate(rng, np.frombuffer(clean.encode(), dtype=np.uint8), sub=err * 0.4, ins=err * 0.25, dele=err * 0.35)
-    return s.decode(), q.decode()
+_concatemer = concatemer            # over a given insert (tests/deep_read_cases.py)
 
 
 def _build_batch():

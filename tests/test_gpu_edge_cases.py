@@ -6,6 +6,8 @@ import pytest
 from c3poa_amd import synth
 from c3poa_amd.seqio import revcomp
 
+from deep_read_cases import concatemer
+
 pytestmark = pytest.mark.gpu
 
 
@@ -23,11 +25,7 @@ def _qual(rng, L, lo=2, hi=41):
     return "".join(chr(33 + int(v)) for v in rng.integers(lo, hi, L))
 
 
-def _concatemer(rng, splint, insert_len, n, k0, k1, err=0.1):
-    ins = _rand(rng, insert_len)
-    clean = ins[len(ins) - k0:] + (splint + ins) * n + splint + ins[:k1]
-    s, q = synth._mutate(rng, np.frombuffer(clean.encode(), dtype=np.uint8), sub=err * 0.4, ins=err * 0.25, dele=err * 0.35)
-    return s.decode(), q.decode()
+_concatemer = concatemer            # (rng, splint, insert length, repeats, k0, k1, err=0.1): tests/deep_read_cases.py
 
 
 def _compare(O, splints, reads, strands, sids, **cfg):
