@@ -74,6 +74,11 @@ def parse_args(argv=None):
                              "(default), or the GPU, while the batch is still resident (with --bgzf they are compressed there "
                              "as well). The files are the same byte for byte; measured at 1 M reads the run is slower "
                              "without --bgzf and faster with it (DESIGN.md 5.8).")
+    parser.add_argument("--bam", action="store_true", default=False,
+                        help="Write <splint>/R2C2_Consensus.bam and R2C2_Subreads.bam, unaligned BAM made and compressed on the GPU, "
+                             "instead of the FASTA and FASTQ files (needs --emit gpu). A consensus record carries np, rl and aq "
+                             "tags and, with --consensus-fastq, its QVs as qualities; --bgzf and -co change nothing for .bam "
+                             "files. Read names of more than 219 bytes are refused. No index, no @RG (DESIGN.md 5.15).")
     parser.add_argument("--version", "-v", action="version", version=VERSION, help="Prints the C3POa version.")
     if argv is None and len(sys.argv) == 1:
         parser.print_help()
@@ -83,6 +88,8 @@ def parse_args(argv=None):
         args.compress_output = True
     if args.gunzip == "gpu" and args.inflate != "gpu":
         parser.error("--gunzip gpu needs --inflate gpu: it says how a plain gzip input is inflated on the GPU")
+    if args.bam and args.emit != "gpu":
+        parser.error("--bam needs --emit gpu: BAM records are packed on the GPU while the batch is resident")
     if args.parse == "gpu" and args.inflate != "gpu":
         parser.error("--parse gpu needs --inflate gpu: records are parsed on the GPU only where the text was inflated there")
     return args

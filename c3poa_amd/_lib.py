@@ -273,6 +273,9 @@ def _prototypes():
         "c3_batch_emit_fetch": (i, [vp, vp, i64, vp]),
         "c3_emit_timing_get": (i, [vp, P(EmitTiming)]),
         "c3_append_streams": (i, [pcp, vp, vp, i]),
+        "c3_emit_group_bam": (i, [vp] + em),
+        "c3_emit_group_bam_host": (i, em),
+        "c3_bam_out_header": (i, [vp, i64, pi64]),
         "c3_fastx_strict_parse_host": (i, [vp, i64, i, i, vp, i64, vp, vp, vp, i64, vp, vp, i64, P(FastxInfo)]),
         "c3_post_emit_text": (i, [vp, vp, i64, i, i, P(PostArgs), vp, i64, vp, vp, i64, P(PostTextInfo)]),
         "c3_post_text_reset": (i, [vp]),
@@ -782,12 +785,20 @@ class Handle(_Owned):
         return _emit_call(lambda *a: self.lib.c3_emit_group(self.h, *a), self._err,
                           hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, zero, cap, arena)
 
-    def emit_snapshot(self, hb, zero=True, bgzf=False, qv=False):
+    def emit_group_bam(self, hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, zero=True, cap=None, arena=None):
+        """c3_emit_group_bam (k_bamout): the records of emit_group as uncompressed BAM records, two streams per splint
+        (consensus, subreads).  Same arguments as emit_group_bam_host."""
+        return _emit_call(lambda *a: self.lib.c3_emit_group_bam(self.h, *a), self._err,
+                          hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, zero, cap, arena, bam=True)
+
+    def emit_snapshot(self, hb, zero=True, bgzf=False, qv=False, bam=False):
         """c3_batch_emit_snapshot: formats the records of the resident batch (whose names are hb's) on the device and freezes
-        the streams; the handle may then commit and run the next batch.  Returns the number of streams emit_fetch delivers."""
+        the streams; the handle may then commit and run the next batch.  bam: BAM records (two streams per splint, the QVs as
+        consensus qualities) instead of text.  Returns the number of streams emit_fetch delivers."""
         no = np.ascontiguousarray(hb.name_off, dtype=np.int64)
-        self._chk(self.lib.c3_batch_emit_snapshot(self.h, hb.c.names, no.ctypes.data, 1 if zero else 0, EMIT_BGZF if bgzf else 0))
-        return self.n_splints * (3 if qv else 2)
+        self._chk(self.lib.c3_batch_emit_snapshot(self.h, hb.c.names, no.ctypes.data, 1 if zero else 0,
+                                                  (EMIT_BGZF if bgzf else 0) | (EMIT_BAM if bam else 0)))
+        return self.n_splints * (3 if qv and not bam else 2)
 
     def emit_fetch(self, into, n_streams):
         """c3_batch_emit_fetch: (arena bytes, stream_off[n_streams + 1]) of the emit snapshot in `into` (an EmitBuffers); may run
@@ -1603,6 +1614,7 @@ def demux_emit_host(text, sets, at_eof=True, cap=None, max_records=None):
 
 # ---- records formatted on the GPU (--emit gpu; include/c3poa.h "Records formatted on the GPU") ----
 EMIT_BGZF = 1
+EMIT_BAM = 2                     # c3_batch_emit_snapshot: BAM records (include/c3poa.h "Records written as unaligned BAM")
 EMIT_KINDS = ("consensus_fasta", "subread_fastq", "consensus_fastq")
 
 
@@ -1619,10 +1631,10 @@ class EmitStreams:
         return [self.stream(x) for x in range(len(self.stream_off) - 1)]
 
 
-def _emit_call(fn, err, hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, zero, cap=None, arena=None):
+def _emit_call(fn, err, hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, zero, cap=None, arena=None, bam=False):
     """cap None: the arena is sized by a first call with no arena (C3_E_LIMIT reports the need).  An explicit cap / arena is
-    handed through as it is; a C3Error then carries .code and .stream_off."""
-    K = 3 if qv_buf is not None else 2
+    handed through as it is; a C3Error then carries .code and .stream_off.  bam: the BAM form of the call (K = 2)."""
+    K = 3 if qv_buf is not None and not bam else 2
     S = n_splints * K
     sid = np.ascontiguousarray(splint_ids, dtype=np.int16)
     res = np.ascontiguousarray(res)
@@ -1645,7 +1657,7 @@ def _emit_call(fn, err, hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splin
     else:
         rc = call(arena, cap)
     if rc != 0:
-        raise _c3_error(rc, err, "c3_emit_group", stream_off=so[:max(S, 0) + 1].copy())
+        raise _c3_error(rc, err, "c3_emit_group_bam" if bam else "c3_emit_group", stream_off=so[:max(S, 0) + 1].copy())
     return EmitStreams(arena, so[:S + 1].copy(), int(nrec.value), K)
 
 
@@ -1653,6 +1665,21 @@ def emit_group_host(hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, 
     """c3_emit_group_host: the host statement of Handle.emit_group (same arguments and results).  hb: a HostBatch; res: RESULT_DTYPE
     records; cons_buf / cons_off / qv_buf as results_raw / results_fetch_qv return them (cons_buf and qv_buf may be None)"""
     return _emit_call(load().c3_emit_group_host, None, hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, zero, cap, arena)
+
+
+def emit_group_bam_host(hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, zero=True, cap=None, arena=None):
+    """c3_emit_group_bam_host: the host statement of Handle.emit_group_bam (same arguments and results): uncompressed BAM
+    records, stream splint * 2 + kind with kind 0 = consensus and 1 = subreads"""
+    return _emit_call(load().c3_emit_group_bam_host, None, hb, res, cons_buf, cons_off, qv_buf, splint_ids, n_splints, zero, cap, arena, bam=True)
+
+
+def bam_out_header():
+    """c3_bam_out_header: the uncompressed header of a --bam file (magic, @HD and @PG text, no references)"""
+    buf, n = C.create_string_buffer(512), C.c_int64(0)
+    rc = load().c3_bam_out_header(buf, len(buf), C.byref(n))
+    if rc != 0:
+        raise _c3_error(rc, None, "c3_bam_out_header")
+    return buf.raw[:n.value]
 
 
 class EmitBuffers:

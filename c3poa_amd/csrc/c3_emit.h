@@ -114,6 +114,7 @@ struct EmitArgs {
   int64_t* stream_off;                  // [S * K + 2]: stream starts, total, records
   int64_t* roff;                        // [n][C3_EMIT_KINDS] arena offset of the read's bytes of each kind
   uint8_t* arena;
+  int bam;                              // 1: BAM records (k_bamout.hip, c3_bamout.h; K = 2), 0: text
 };
 
 // argument and record rules shared by c3_emit_group and c3_emit_group_host (c3_emit.cpp); C3_E_OK = go on

@@ -494,7 +494,7 @@ extern "C" int c3_batch_results(c3_handle* h, c3_read_result* res, char* cons, i
 //   c3_batch_emit_fetch     copies the streams out on the download stream; with C3_EMIT_BGZF each stream goes through k_bgzf
 //                           first (c3h::bgzf_chunks, c3_stream.hip; the packed members of the last chunks land at the wait that ends the call).
 extern "C" int c3_batch_emit_snapshot(c3_handle* h, const char* names, const int64_t* name_off, int zero, int flags) {
-  if (!h || h->n <= 0 || !names || !name_off || (flags & ~C3_EMIT_BGZF)) return C3_E_ARG;
+  if (!h || h->n <= 0 || !names || !name_off || (flags & ~(C3_EMIT_BGZF | C3_EMIT_BAM))) return C3_E_ARG;
   if (h->emit_pending.load(std::memory_order_acquire)) return c3_fail(h, C3_E_STATE, "c3_batch_emit_snapshot: the previous emit snapshot has not been fetched");
   if (h->n_spl > C3_EMIT_MAX_SPLINTS) return c3_fail(h, C3_E_LIMIT, "c3_batch_emit_snapshot: more than 64 splints");
   const double t_call = dbg_now_ms();
@@ -502,6 +502,8 @@ extern "C" int c3_batch_emit_snapshot(c3_handle* h, const char* names, const int
   if (name_off[0] != 0) return c3_fail(h, C3_E_ARG, "c3_batch_emit_snapshot: name_off must start at 0");
   for (int i = 0; i < n; ++i) if (name_off[i + 1] < name_off[i]) return c3_fail(h, C3_E_ARG, "c3_batch_emit_snapshot: name_off not ascending");
   for (int i = 0; i < n; ++i) if (name_off[i + 1] - name_off[i] >= (1ll << 31)) return c3_fail(h, C3_E_LIMIT, "c3_batch_emit_snapshot: a name of 2^31 bytes or more");
+  const int bam = (flags & C3_EMIT_BAM) != 0;
+  if (bam) { const int nrc = c3_bamout_check_names("c3_batch_emit_snapshot", names, name_off, n); if (nrc != C3_E_OK) return c3_fail(h, nrc, c3_last_error(nullptr)); }
   HIPCHK(hipSetDevice(h->cfg.device));
   if (!h->ev_emit_dn) HIPCHK(hipEventCreateWithFlags(&h->ev_emit_dn, hipEventDisableTiming));
   const size_t nmb = (size_t)name_off[n];
@@ -509,7 +511,7 @@ extern "C" int c3_batch_emit_snapshot(c3_handle* h, const char* names, const int
   HIPCHK(h->d_emit_noff.put(name_off, sizeof(int64_t) * (size_t)(n + 1), h->stream));
   const bool have_cons = (h->stages_done & C3_STAGE_POLISH) != 0, have_qv = have_cons && (h->stages_done & C3_STAGE_QV) != 0;
   EmitArgs p; memset(&p, 0, sizeof(p));
-  p.n = n; p.n_splints = h->n_spl; p.K = have_qv ? 3 : 2; p.zero = zero;
+  p.n = n; p.n_splints = h->n_spl; p.K = have_qv && !bam ? 3 : 2; p.zero = zero; p.bam = bam;
   p.names = h->d_emit_names.as<uint8_t>(); p.name_off = h->d_emit_noff.as<int64_t>();
   p.seqs = h->d_ascii.as<uint8_t>(); p.quals = h->d_qual.as<uint8_t>(); p.off = h->d_off.as<int64_t>();
   p.info = h->d_info.as<C3Info>(); p.sid = h->d_sid.as<int16_t>();

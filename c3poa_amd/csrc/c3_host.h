@@ -7,6 +7,7 @@
 #include "c3_launch.h"
 #include "c3_checks.h"
 #include "c3_emit.h"
+#include "c3_bamout.h"
 #include "c3_post.h"
 #include "c3_fastx.h"
 #include "c3_dsplit.h"

@@ -57,6 +57,8 @@ void c3k_launch_demux_emit(const FaArgs*, hipStream_t);
 void c3k_launch_emit_len(const EmitArgs*, hipStream_t);                                                                    // k_emit.hip
 void c3k_launch_emit_scan(const EmitArgs*, hipStream_t);
 void c3k_launch_emit_write(const EmitArgs*, hipStream_t);
+void c3k_launch_bamout_len(const EmitArgs*, hipStream_t);                                                                  // k_bamout.hip
+void c3k_launch_bamout_write(const EmitArgs*, hipStream_t);
 void c3k_launch_fastx_high(const FxArgs*, hipStream_t);                                                                    // k_fastx.hip
 void c3k_launch_fastx_records(const FxArgs*, hipStream_t);
 void c3k_launch_fastx_gather(const FxArgs*, hipStream_t);

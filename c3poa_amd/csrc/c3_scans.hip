@@ -445,7 +445,7 @@ int c3h::emit_run(c3_handle* h, EmitArgs& p, EmitBufs& eb, hipStream_t s, std::v
   p.head = (EmitHead*)w; p.len = (int64_t*)(w + w_len); p.roff = (int64_t*)(w + w_roff); p.bsum = (long long*)(w + w_bsum);
   p.stream_off = eb.offs.as<int64_t>(); p.arena = nullptr;
   HIPCHK(hipEventRecord(eb.ev[0], s));
-  c3k_launch_emit_len(&p, s);
+  if (p.bam) c3k_launch_bamout_len(&p, s); else c3k_launch_emit_len(&p, s);
   HIPCHK(hipEventRecord(eb.ev[1], s));
   c3k_launch_emit_scan(&p, s);
   HIPCHK(hipEventRecord(eb.ev[2], s));
@@ -460,22 +460,24 @@ int c3h::emit_run(c3_handle* h, EmitArgs& p, EmitBufs& eb, hipStream_t s, std::v
   HIPCHK(eb.arena.ensure((size_t)need + 256));                  // (256: what k_bgzf may read behind a chunk, c3_batch_emit_fetch)
   p.arena = eb.arena.as<uint8_t>();
   HIPCHK(hipEventRecord(eb.ev[3], s));
-  c3k_launch_emit_write(&p, s);
+  if (p.bam) c3k_launch_bamout_write(&p, s); else c3k_launch_emit_write(&p, s);
   HIPCHK(hipEventRecord(eb.ev[4], s));
   HIPCHK(hipGetLastError());
   return C3_E_OK;
 }
 
 // the stand-alone call: three steps on the handle's stream: upload + lengths + scans, the stream sizes read back, write + download
-extern "C" int c3_emit_group(c3_handle* h, const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
-                             const char* qv, const int16_t* splint_id, int n_splints, int zero, char* arena, int64_t cap,
-                             int64_t* stream_off, int64_t* n_records) {
+// (bam: the records of c3_emit_group_bam, K = 2 whatever qv is; who: the call's name in its error texts)
+static int emit_group(c3_handle* h, const char* who, int bam, const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
+                      const char* qv, const int16_t* splint_id, int n_splints, int zero, char* arena, int64_t cap,
+                      int64_t* stream_off, int64_t* n_records) {
   if (!h) return C3_E_ARG;
   const double t_call = dbg_now_ms();
-  const int rc = c3_emit_check_args("c3_emit_group", b, res, cons, cons_off, qv, splint_id, n_splints, zero, arena, cap, stream_off, n_records);
+  int rc = c3_emit_check_args(who, b, res, cons, cons_off, qv, splint_id, n_splints, zero, arena, cap, stream_off, n_records);
+  if (rc == C3_E_OK && bam) rc = c3_bamout_check_names(who, b->names, b->name_off, b->n);
   if (rc != C3_E_OK) return c3_fail(h, rc, c3_last_error(nullptr));
   HIPCHK(hipSetDevice(h->cfg.device));
-  const int n = b->n, K = qv ? 3 : 2, SK = n_splints * K;
+  const int n = b->n, K = qv && !bam ? 3 : 2, SK = n_splints * K;
   h->etm = c3_emit_timing{};
   if (n == 0) { for (int x = 0; x <= SK; ++x) stream_off[x] = 0; *n_records = 0; return C3_E_OK; }
   const size_t sb = (size_t)b->off[n], nmb = (size_t)b->name_off[n], cb = cons ? (size_t)cons_off[n] : 0, ob = sizeof(int64_t) * (size_t)(n + 1);
@@ -489,7 +491,7 @@ extern "C" int c3_emit_group(c3_handle* h, const c3_host_batch* b, const c3_read
     if (up[k].bytes) HIPCHK(hipMemcpyAsync(d[k].p, up[k].src, up[k].bytes, hipMemcpyHostToDevice, h->stream));
   }
   EmitArgs p; memset(&p, 0, sizeof(p));
-  p.n = n; p.n_splints = n_splints; p.K = K; p.zero = zero;
+  p.n = n; p.n_splints = n_splints; p.K = K; p.zero = zero; p.bam = bam;
   p.names = d[0].as<uint8_t>(); p.name_off = d[1].as<int64_t>(); p.seqs = d[2].as<uint8_t>(); p.quals = d[3].as<uint8_t>(); p.off = d[4].as<int64_t>();
   p.info = d[5].as<c3_read_result>(); p.sid = d[6].as<int16_t>();
   p.cons = cons ? d[7].as<uint8_t>() : nullptr; p.qv = qv ? d[8].as<uint8_t>() : nullptr;
@@ -500,7 +502,7 @@ extern "C" int c3_emit_group(c3_handle* h, const c3_host_batch* b, const c3_read
   if (rr != C3_E_OK && rr != C3_E_LIMIT) return rr;
   memcpy(stream_off, so.data(), sizeof(int64_t) * (SK + 1));
   *n_records = so[SK + 1];
-  if (rr == C3_E_LIMIT) return c3_fail(h, C3_E_LIMIT, "c3_emit_group: arena too small (bytes needed in stream_off[S])");
+  if (rr == C3_E_LIMIT) return c3_fail(h, C3_E_LIMIT, (std::string(who) + ": arena too small (bytes needed in stream_off[S])").c_str());
   const int64_t need = so[SK];
   if (need) HIPCHK(hipMemcpyAsync(arena, eb.arena.p, (size_t)need, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -510,6 +512,17 @@ extern "C" int c3_emit_group(c3_handle* h, const c3_host_batch* b, const c3_read
   h->etm.n_reads = n; h->etm.n_records = so[SK + 1]; h->etm.in_bytes = (int64_t)(nmb + 2 * sb + cb * (qv ? 2 : 1)); h->etm.out_bytes = need;
   h->etm.ms_call = (float)(dbg_now_ms() - t_call);
   return C3_E_OK;
+}
+extern "C" int c3_emit_group(c3_handle* h, const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
+                             const char* qv, const int16_t* splint_id, int n_splints, int zero, char* arena, int64_t cap,
+                             int64_t* stream_off, int64_t* n_records) {
+  return emit_group(h, "c3_emit_group", 0, b, res, cons, cons_off, qv, splint_id, n_splints, zero, arena, cap, stream_off, n_records);
+}
+// the same group as unaligned BAM records (k_bamout.hip; host statement: c3_bamout.cpp)
+extern "C" int c3_emit_group_bam(c3_handle* h, const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
+                                 const char* qv, const int16_t* splint_id, int n_splints, int zero, char* arena, int64_t cap,
+                                 int64_t* stream_off, int64_t* n_records) {
+  return emit_group(h, "c3_emit_group_bam", 1, b, res, cons, cons_off, qv, splint_id, n_splints, zero, arena, cap, stream_off, n_records);
 }
 extern "C" int c3_emit_timing_get(c3_handle* h, c3_emit_timing* t) {
   if (!h || !t) return C3_E_ARG;

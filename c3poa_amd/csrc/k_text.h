@@ -1,4 +1,4 @@
-// k_text.h -- the one home of what the text kernels share (k_fastq, k_bam, k_fastx, k_fasta, k_dsplit, k_post, k_emit): the workgroup
+// k_text.h -- the one home of what the text kernels share (k_fastq, k_bam, k_fastx, k_fasta, k_dsplit, k_post, k_emit, k_bamout): the workgroup
 // shape of their record passes (TX_WAVES, TX_LONG), the wave and workgroup scans, the wave copy between any two byte addresses,
 // the cutter that shares a long record among the waves of a workgroup, and the one-column exclusive scan over a functor (three
 // kernels and their launcher).  Device code, but for that launcher.

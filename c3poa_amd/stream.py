@@ -83,6 +83,7 @@ class Options:
     """every switch of a run, read ONCE from args and the environment: nothing below looks at either again"""
     reads: str; out_path: str; lencutoff: int; mdistcutoff: int; zero: bool; zero_max_cells: int
     compress: bool; bgzf: bool; qv: bool; emit_gpu: bool; inflate_gpu: bool; parse_gpu: bool; gunzip_gpu: bool
+    bam: bool
     batch_reads: int; batch_fixed: bool; n_work: int; readers_per_gpu: int; min_range: int
     devices: tuple                                  # worker -> physical device
 
@@ -106,6 +107,9 @@ class Options:
             # --emit gpu: the records of every batch are formatted on the GPU while it is resident (k_emit; with --bgzf compressed there
             # as well) and the writer only appends the finished streams
             emit_gpu=getattr(args, "emit", "host") == "gpu",
+            # --bam (needs --emit gpu): the records leave the device as unaligned BAM, always BGZF (k_bamout, k_bgzf), into
+            # R2C2_Consensus.bam and R2C2_Subreads.bam; QVs, when computed, are the consensus qualities
+            bam=bool(getattr(args, "bam", False)),
             inflate_gpu=getattr(args, "inflate", "host") == "gpu", parse_gpu=getattr(args, "parse", "host") == "gpu",
             # --gunzip gpu: a plain gzip input is inflated by the k_gunzip kernels instead of one zlib stream (needs --inflate gpu)
             gunzip_gpu=getattr(args, "gunzip", "host") == "gpu",
@@ -119,18 +123,23 @@ class OutputTree:
     as X, or as X.gz with --bgzf: which exist, what a run does to them before and after.  No thread, no handle.  finder_psl: the
     fused mode's PSL, collected in finder_psl + ".part" while the run lasts."""
 
-    def __init__(self, out_path, splint_names, bgzf=False, compress=False, qv=False, finder_psl=None):
+    def __init__(self, out_path, splint_names, bgzf=False, compress=False, qv=False, finder_psl=None, bam=False):
         self.out_path, self.names, self.bgzf, self.compress, self.qv, self.finder_psl = out_path, list(splint_names), bgzf, compress, qv, finder_psl
+        self.bam_head = None                        # --bam: the header member every .bam begins with
+        self.bam = bam                              # --bam: R2C2_Consensus.bam and R2C2_Subreads.bam and nothing else (bgzf, compress and qv name no file)
         self.cons_paths = [out_path + n + "/R2C2_Consensus.fasta" for n in self.names]
         self.sub_paths = [out_path + n + "/R2C2_Subreads.fastq" for n in self.names]
         self.fq_paths = [out_path + n + "/R2C2_Consensus.fastq" for n in self.names] if qv else []
         gz = ".gz" if bgzf else ""
         self.cons_w, self.sub_w, self.fq_w = ([p + gz for p in ps] for ps in (self.cons_paths, self.sub_paths, self.fq_paths))
         # stream s * K + kind of c3_batch_emit_fetch -> its file
+        self.bam_w = [(out_path + n + "/R2C2_Consensus.bam", out_path + n + "/R2C2_Subreads.bam") for n in self.names] if bam else []
         self.emit_paths = [p for k in range(len(self.names)) for p in self.written(k)]
         self.gz_made = []                           # --bgzf: the .gz files of this run (each gets the EOF member at the end)
 
     def written(self, k):                           # the files the writers append to for splint k
+        if self.bam:
+            return self.bam_w[k]
         return (self.cons_w[k], self.sub_w[k]) + ((self.fq_w[k],) if self.qv else ())
 
     def prepare(self, used):
@@ -141,6 +150,9 @@ class OutputTree:
         for k, n in enumerate(self.names):
             if n in used:
                 os.makedirs(self.out_path + n, exist_ok=True)
+                if self.bam:
+                    self.prepare_bam(k)
+                    continue
                 for p in self.written(k):           # "w+" semantics of cat_files (C3POa.py:88-92)
                     open(p, "w").close()
                     stale = p[:-3] if self.bgzf else p + ".gz"
@@ -149,18 +161,34 @@ class OutputTree:
                     if self.bgzf:
                         self.gz_made.append(p)
 
+    def prepare_bam(self, k):
+        """--bam: each file of splint k starts with the BAM header as one BGZF member (host code: no worker runs yet); no text
+        counterpart, plain or .gz, stays beside them"""
+        if self.bam_head is None:
+            self.bam_head = _lib.bgzf_compress_host(_lib.bam_out_header())
+        for p in self.bam_w[k]:
+            with open(p, "wb") as fh:
+                fh.write(self.bam_head)
+            self.gz_made.append(p)
+        d = self.out_path + self.names[k] + "/"
+        for stale in ("R2C2_Consensus.fasta", "R2C2_Subreads.fastq", "R2C2_Consensus.fastq"):
+            for q in (d + stale, d + stale + ".gz"):
+                if os.path.exists(q):
+                    os.remove(q)
+
     def finish(self, seen=None):
         """after the last writer.  seen: the splints that were hit (fused mode), else None"""
+        unused = len(self.bam_head or b"")                          # --bam: an unused file holds only its header member
         if seen is not None:
             os.replace(self.finder_psl + ".part", self.finder_psl)  # a rerun finds the PSL and takes the two-pass route
             for k, n in enumerate(self.names):
                 if n not in seen:                                   # adapter_set of bin/preprocess.py:34,43 = splints that were hit
                     for p in self.written(k):                       # (before the EOF members: an unused .gz is still empty)
-                        if os.path.exists(p) and os.stat(p).st_size == 0:
+                        if os.path.exists(p) and os.stat(p).st_size == unused:
                             os.remove(p)
                     with contextlib.suppress(OSError):
                         os.rmdir(self.out_path + n)
-        if self.bgzf:                                               # every writer is done: the EOF member ends each file
+        if self.bgzf or self.bam:                                   # every writer is done: the EOF member ends each file
             for p in self.gz_made:
                 if os.path.exists(p):
                     with open(p, "ab") as fh:
@@ -263,7 +291,7 @@ class Pipeline:
       last_timing: a dict with ms_pack and ms_total; ms_wall and ms_alloc are optional
       results_snapshot() -> shape; one snapshot per handle, the next waits for the fetch of this one (fetched[w])
       results_fetch(rb, shape[, with_cons=False]) -> (res, buf, coff) | results_fetch_qv(rb, shape) -> (res, buf, coff, qv)
-      --emit gpu: emit_snapshot(hb, zero, bgzf, qv) -> n_streams; emit_fetch(eb, n_streams) -> (eb, stream_off); emit_timing() -> dict
+      --emit gpu: emit_snapshot(hb, zero, bgzf, qv) -> n_streams (--bam: emit_snapshot(hb, zero, True, qv, bam=True)); emit_fetch(eb, n_streams) -> (eb, stream_off); emit_timing() -> dict
       fused finder: scan_splints() -> (table, splint_ids, strands); assign(splint_ids, strands); cfg.conk_match"""
 
     def __init__(self, opt, tree, readers, splints, assigner, timers):
@@ -376,7 +404,10 @@ class Pipeline:
             return False
         self.fetched[w].clear()
         b.shape = h.results_snapshot()
-        b.n_streams = h.emit_snapshot(b.hb, opt.zero, opt.bgzf, opt.qv) if opt.emit_gpu else 0
+        if opt.bam:                                 # BAM records, always as BGZF members
+            b.n_streams = h.emit_snapshot(b.hb, opt.zero, True, opt.qv, bam=True)
+        else:
+            b.n_streams = h.emit_snapshot(b.hb, opt.zero, opt.bgzf, opt.qv) if opt.emit_gpu else 0
         self.timers.add(run=t2 - t1, snapshot=time.perf_counter() - t2, **dev)
         with self.timers("wait_out"):
             self.to_fetch[w].put(b)
@@ -518,7 +549,9 @@ def run(args, splint_dict, assigner, adapter_set=None, n_dev=1, stats=None, find
         assigner = DictAssigner(assigner, splint_names)
     fused = assigner is None
     opt = Options.read(args, n_dev)
-    tree = OutputTree(opt.out_path, splint_names, opt.bgzf, opt.compress, opt.qv, finder_psl if fused else None)
+    if opt.bam and not opt.emit_gpu:
+        raise ValueError("--bam needs --emit gpu: BAM records are made on the GPU only")
+    tree = OutputTree(opt.out_path, splint_names, opt.bgzf, opt.compress, opt.qv, finder_psl if fused else None, bam=opt.bam)
     used = set(adapter_set or ())                   # cat_files runs per adapter_set entry (C3POa.py:259)
     if isinstance(assigner, DictAssigner):
         used |= set(v[0] for v in assigner.d.values())

@@ -712,6 +712,43 @@ int c3_emit_timing_get(c3_handle* h, c3_emit_timing* t);
  * text naming the path and the system's reason.  Host code. */
 int c3_append_streams(const char* const* paths, const char* arena, const int64_t* stream_off, int n_streams);
 
+/* ---- Records written as unaligned BAM (C3POa.py --emit gpu --bam) ----
+ * The records of "Records formatted on the GPU" as BAM records instead of text.  Which reads write which records, in which
+ * order and from which slice is the same rule (c3poa_amd/csrc/c3_emit.h); what a record is made of is
+ * c3poa_amd/csrc/c3_bamout.h.  K = 2 kinds per splint whatever qv is: stream s * 2 + kind, kind 0 = consensus records, kind 1 =
+ * subread records, records within a stream in read order.  One record, every field little-endian and none aligned:
+ *   block_size (bytes behind it), refID -1, pos -1, l_read_name (name bytes + the NUL), mapq 0, bin 4680, n_cigar_op 0, flag 4,
+ *   l_seq, next_refID -1, next_pos -1, tlen 0, read_name NUL, seq ((l_seq + 1) / 2 bytes, high nibble first, an unused low
+ *   nibble 0), qual (l_seq bytes), tags (consensus records only).
+ * A subread record is named <name>_<idx> (the FASTQ record's text between '@' and the newline), holds the bases and qualities of
+ * its piece and no tags; a piece of 0 bases is a record with l_seq = 0.  A consensus record is named
+ * <name>_<avgQ>_<L>_<ns>_<clen> (the FASTA header's text), holds the consensus, the QV bytes as qualities when qv is given and
+ * l_seq bytes of 0xFF when not, and three tags in this order: np:i = ns as the name prints it, rl:i = L, aq:f =
+ * (float)((double)tot / (double)L) with the tot the name's avgQ is made from.  A base is stored as its index in
+ * "=ACMGRSVTWYHKDBN", a lower-case letter as its upper-case form, every other byte as 15; a quality byte b as
+ * min(max(b - 33, 0), 93).
+ * Limits, checked on the host before any launch, beside those of c3_emit_group: a read name of more than 219 bytes is
+ * C3_E_LIMIT (254 name bytes fit a record; the longest suffix takes 35 of them; decided from the names alone, for every read of
+ * the group), a name that holds a NUL is C3_E_ARG; both texts name the read.  Unaligned records only, no index, no @RG.
+ * c3_emit_group_bam / c3_emit_group_bam_host deliver the UNCOMPRESSED record bytes per stream; arena, cap,
+ * stream_off[n_splints * 2 + 1], n_records and C3_E_LIMIT with the bytes needed work as in c3_emit_group.  The host call is the
+ * statement of the device call, byte for byte (errors through c3_last_error(NULL)).
+ * c3_batch_emit_snapshot takes C3_EMIT_BAM in its flags: the streams of the fetch are then the two BAM kinds (K = 2), with the
+ * QVs as consensus qualities when the batch ran C3_STAGE_QV; with C3_EMIT_BGZF beside it every non-empty stream is compressed by
+ * k_bgzf as for text (a record may straddle two members).  The name limits are checked there as well.
+ * c3_bam_out_header writes the file header: "BAM\1", l_text, the text
+ * "@HD\tVN:1.6\tSO:unknown\n@PG\tID:c3poa_amd\tPN:c3poa_amd\tVN:<c3_version()>\n", n_ref = 0; *len = its bytes, C3_E_LIMIT with
+ * *len set when cap is smaller.  A file is that header as BGZF member(s), the members of the record streams in any order of
+ * arrival, and the BGZF EOF member.  Host code. */
+#define C3_EMIT_BAM 2             /* c3_batch_emit_snapshot: BAM records instead of text; K = 2 */
+int c3_emit_group_bam(c3_handle* h, const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
+                      const char* qv, const int16_t* splint_id, int n_splints, int zero, char* arena, int64_t cap,
+                      int64_t* stream_off, int64_t* n_records);
+int c3_emit_group_bam_host(const c3_host_batch* b, const c3_read_result* res, const char* cons, const int64_t* cons_off,
+                           const char* qv, const int16_t* splint_id, int n_splints, int zero, char* arena, int64_t cap,
+                           int64_t* stream_off, int64_t* n_records);
+int c3_bam_out_header(char* dst, int64_t cap, int64_t* len);
+
 /* ---- Strict FASTA / FASTQ records (the input of C3POa_postprocessing.py) ----
  * A text is STRICT of kind 4 (the four-line FASTQ rule of "FASTQ records on the GPU") or of kind 2, the two-line FASTA that
  * C3POa.py writes: line 0 begins with '>'; line 1 is not empty and does not begin with '>', '@' or '+'.  The kind of a file is
