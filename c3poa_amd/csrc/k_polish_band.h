@@ -22,7 +22,8 @@
 // filling.  A layer whose certificate fails is simply redone by the unbanded rows.
 //
 // Row loop.  hcur = row r-1 in ITS band coordinates.  The fast row (one predecessor = the row above, band shift 0 or 1,
-// nothing to keep) is straight-line code, one variant per shift: neighbours from registers with one DPP move, substitution
+// nothing to keep) is straight-line code, one variant per shift, and a run of fast rows of one shift is a loop of its own that
+// updates its state in place: neighbours from registers with one DPP move, substitution
 // bytes of its columns prefetched from an LDS table during the row before, 2 bits of direction per cell appended to a
 // per-lane accumulator that goes to memory once per RPW rows (ONE vector store per 4-8 rows: the row loop is bound by
 // instruction issue, and a store costs the memory pipeline as much as sixteen ALU instructions cost the SIMD).  Every other
@@ -166,6 +167,7 @@ __device__ int win_build_desc_band(WCtx& c, int R, int Q, int begin, int end, in
         const unsigned wr = other | (next & (fastn ^ 1u));
         uint4 d; d.x = vb[u] * 8u | ((unsigned)min(np, 255) << 8) | (ovf << 16) | (far << 17) | ((has ^ 1u) << 18) | ((unsigned)two << 19) | (fast << 20)
                        | ((unsigned)(fast ? dl : 0) << 22) | (wr << 23) | (virt << 24);
+        // (bit 22 on fast rows only, and fast implies dl <= 1: the fast-run loops of win_rows_band test the bit alone)
         d.y = p[0] | (p[1] << 16); d.z = p[2] | (p[3] << 16); d.w = (unsigned)lo | ((unsigned)min(dist, 255) << 10) | ((unsigned)bidx << 18);
         c.rdesc[r] = d;
       }
@@ -215,6 +217,7 @@ __device__ __attribute__((noinline)) int win_chain_desc_band(uint4* crdesc, cons
       typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
       u32x4 d;
       d.x = vb * 8u | (1u << 8) | ((has ^ 1u) << 18) | (1u << 19) | (fast << 20) | ((fast ? (unsigned)dl : 0u) << 22) | (wr << 23) | ((unsigned)(r == 1) << 24);
+      // (bit 22 on fast rows only, as in win_build_desc_band)
       d.y = (unsigned)(r - 1); d.z = 0; d.w = (unsigned)lo | (has << 10) | ((unsigned)r << 18);
       GP(u32x4, rdesc)[r] = d;
     }
@@ -240,6 +243,26 @@ __device__ __forceinline__ void wb_park_edge(unsigned eaddr, const int (&h)[CB])
   else
     asm volatile("s_mov_b64 exec, %0\n\tds_write_b16 %1, %2\n\tds_write_b16 %1, %3 offset:2\n\tds_write_b16 %1, %4 offset:4\n\tds_write_b16 %1, %5 offset:6\n\ts_mov_b64 exec, -1"
                  :: "s"(emask), "v"(eaddr), "v"(h[0]), "v"(h[CB > 1 ? 1 : 0]), "v"(h[CB > 2 ? 2 : 0]), "v"(h[CB > 3 ? 3 : 0]) : "memory");
+}
+
+// Exclusive max-scan of the LOW halves over the wave: lane l gets max(run[0 .. l-1]), lane 0 W_NEG16.  The six steps are
+// 16-bit maxima with the DPP shift on the operand, so `run` needs no sign extension first (max16 zero-extends; v_bfe_i32 is a
+// slow-class instruction).  The upper half of the result is whatever the steps left there, and it cannot reach a stored value:
+// every consumer is a 16-bit max (reads the low halves only), an `& ~3`, or an add -- and an add carries upward only, so its
+// low half depends on the low halves alone.  What is stored (H cells, direction tags) is cut from results of max16.
+// One block: the compiler cannot see the DPP hazard (two wait states after a VALU write of the source) inside inline assembly.
+__device__ __forceinline__ int wb_scan16_excl(int run) {
+  int ex = W_NEG16;
+  asm("s_nop 1\n\t"
+      "v_max_i16_dpp %1, %1, %1 row_shr:1 row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
+      "v_max_i16_dpp %1, %1, %1 row_shr:2 row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
+      "v_max_i16_dpp %1, %1, %1 row_shr:4 row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
+      "v_max_i16_dpp %1, %1, %1 row_shr:8 row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
+      "v_max_i16_dpp %1, %1, %1 row_bcast:15 row_mask:0xa bank_mask:0xf\n\ts_nop 1\n\t"
+      "v_max_i16_dpp %1, %1, %1 row_bcast:31 row_mask:0xc bank_mask:0xf\n\ts_nop 1\n\t"
+      "v_mov_b32_dpp %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf"
+      : "+v"(ex), "+v"(run));
+  return ex;
 }
 
 // All banded rows of one layer.  Returns 0, 1 (a predecessor's band lies too far left: not banded) or -1 (scratch too small).
@@ -314,18 +337,18 @@ __device__ __attribute__((noinline)) int win_rows_band(int* cI, int* cE, int32_t
     {                                                                                                            \
       int run = W_NEG16;                                                                                         \
       _Pragma("unroll") for (int cc = 0; cc < CB; ++cc) run = max16(run, key[cc] - g41[cc]);                    \
-      int ex = wave_shr1(wave_scan_max(__builtin_amdgcn_sbfe(run, 0, 16)), W_NEG16);                             \
-      unsigned w2 = 0, pidx = 0;                                                                                 \
+      int ex = wb_scan16_excl(run);                                                                              \
+      unsigned pidx = 0;                                                                                         \
       _Pragma("unroll") for (int cc = 0; cc < CB; ++cc) {                                                       \
         const int k2 = max16(key[cc], (ex & ~3) + g41[cc]);                                                      \
         ex = max16(ex, key[cc] - g41[cc]);                                                                       \
         hcur[cc] = k2 & ~3;                                                                                      \
-        w2 |= ((unsigned)k2 & 3u) << (32 - BPR + 2 * cc);                                                        \
+        dacc = __builtin_amdgcn_alignbit((unsigned)k2, dacc, 2);     /* 2 tag bits in at the top, the word moves down */ \
         if (PIDX) pidx |= (((unsigned)key[cc] >> 16) & 63u) << (8 * cc);                                         \
       }                                                                                                          \
-      dacc = (dacc >> BPR) | w2;                                                                                 \
       if (PIDX) GP(unsigned, PX)[(unsigned)r * 64u + (unsigned)lane] = pidx;                                     \
-      wb_park_edge<CB>(ebase + (unsigned)(li & (WB_EROWS - 1)) * (2u * WB_EROW), hcur);                                             \
+      wb_park_edge<CB>(eoff, hcur);                                                                              \
+      eoff += 2u * WB_EROW;                                                                                      \
     }
 #define WB_RING_WRITE()                                                                                          \
     {                                                                                                            \
@@ -334,52 +357,77 @@ __device__ __attribute__((noinline)) int win_rows_band(int* cI, int* cE, int32_t
       _Pragma("unroll") for (int cc = 0; cc < CB; ++cc) sp_[WB_PADL + CB * lane + cc] = (unsigned short)hcur[cc]; \
     }
 
-  for (int rb = 1; rb <= R; rb += 64) {
+  // a fast row hands over: its ring slot if a later row reads it, then the descriptor word of the next row -- 0 past the end of
+  // the direction word, so that one test ends a run at the word's end as at a row of another kind
+#ifdef C3_PHASE_PROF
+#define WB_PF_FAST ++pf_fast;
+#else
+#define WB_PF_FAST
+#endif
+#define WB_FAST_NEXT()                                                                                           \
+          if (dx & (1u << 23)) WB_RING_WRITE()                                                                   \
+          WB_PF_FAST                                                                                             \
+          ++li;                                                                                                  \
+          { const unsigned nx_ = (unsigned)__builtin_amdgcn_readlane((int)dblk.x, min(li, 63)); dx = li < wend ? nx_ : 0u; }
+  // Row loop.  The rows of a 64-row descriptor block go word by word (RPW rows = one direction word per lane).  Inside a word
+  // the innermost loops are the two fast-run loops, one per band shift: each is one block that updates hcur[], tn[], dacc and
+  // eoff in place (lo is scalar) and has ONE exit test, on the descriptor word dx of the next row.  dx is 0 past the word's
+  // end, so the end of the word, of the WB_EROWS group, of the descriptor block and of the layer all hang off that test: there
+  // the direction word goes to memory, every WB_EROWS rows (or at the block's end) the certificate is evaluated and the
+  // edge-park offset wraps.  The general row stands between the runs and is part of neither loop (joined into one loop body,
+  // the three kinds of row met in phi values: eight register copies per fast row).  A row with more than 64 predecessors ends
+  // all three loops through their own conditions (li, cnt, Rl are numbers), not through a `return` of its own.
+  // The fast-run loops rely on bit 22 (shift) being set on fast rows only: both descriptor builders write fast ? dl : 0 there.
+  int ret = 0, Rl = R;
+  unsigned eoff = ebase;                                                     // LDS byte address of this lane's edge cells of the current row
+  for (int rb = 1; rb <= Rl; rb += 64) {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     const u32x4 dv = GP(const u32x4, c.rdesc)[min(rb + lane, R)];
     uint4 dblk = make_uint4(dv.x, dv.y, dv.z, dv.w);
     asm volatile("" : "+v"(dblk.x), "+v"(dblk.y), "+v"(dblk.z), "+v"(dblk.w));
-    const int cnt = min(64, R - rb + 1);
-    for (int half_ = 0; half_ < 64 && half_ < cnt; half_ += WB_EROWS) {
-    const int hend_ = min(half_ + WB_EROWS, cnt);
-    for (int li = half_; li < hend_; ++li) {
-      const int r = rb + li;
-      const unsigned dx = (unsigned)__builtin_amdgcn_readlane((int)dblk.x, li);
-      int key[CB];
-      if (dx & (1u << 20)) {
-        // FAST ROW: the row above, band shift 0 or 1
-        const int vb8 = (int)(dx & 24u);
-#ifdef C3_PHASE_PROF
-        ++pf_fast;
-#endif
-        if (dx & (1u << 22)) {
-          int tv[CB];
+    int cnt = min(64, R - rb + 1);
+    int li = 0;
+    while (li < cnt) {
+      const int wend = min((li | (RPW - 1)) + 1, cnt);
+      for (;;) {
+        unsigned dx = (unsigned)__builtin_amdgcn_readlane((int)dblk.x, li);
+        // a run of fast rows (the row above, band shift 0 or 1)
+        while (dx & (1u << 20)) {
+          while (dx & (1u << 22)) {                                         // band shift 1
+            const int r = rb + li, vb8 = (int)(dx & 24u);
+            int key[CB], tv[CB];
 #pragma unroll
-          for (int cc = 0; cc < CB; ++cc) tv[cc] = __builtin_amdgcn_sbfe((int)tn[cc + 1], vb8, 8);
-          lo += 1;
+            for (int cc = 0; cc < CB; ++cc) tv[cc] = __builtin_amdgcn_sbfe((int)tn[cc + 1], vb8, 8);
+            lo += 1;
 #pragma unroll
-          for (int k = 0; k <= CB; ++k) tn[k] = tp[lo + k];
-          const int hnext = wave_shl1(hcur[0], W_NEG16);                    // offset CB*lane + CB of the row above
+            for (int k = 0; k <= CB; ++k) tn[k] = tp[lo + k];
+            const int hnext = wave_shl1(hcur[0], W_NEG16);                  // offset CB*lane + CB of the row above
 #pragma unroll
-          for (int cc = 0; cc < CB; ++cc) {
-            const int hv = cc + 1 < CB ? hcur[cc + 1 < CB ? cc + 1 : cc] : hnext;
-            key[cc] = max16(hcur[cc] + tv[cc], hv + cV);
+            for (int cc = 0; cc < CB; ++cc) {
+              const int hv = cc + 1 < CB ? hcur[cc + 1 < CB ? cc + 1 : cc] : hnext;
+              key[cc] = max16(hcur[cc] + tv[cc], hv + cV);
+            }
+            WB_ROW_TAIL(false)
+            WB_FAST_NEXT()
           }
-          WB_ROW_TAIL(false)
-        } else {
-          int tv[CB];
+          while ((dx & (5u << 20)) == (1u << 20)) {                         // band shift 0
+            const int r = rb + li, vb8 = (int)(dx & 24u);
+            int key[CB], tv[CB];
 #pragma unroll
-          for (int cc = 0; cc < CB; ++cc) tv[cc] = __builtin_amdgcn_sbfe((int)tn[cc], vb8, 8);
-          const int hleft = wave_shr1(hcur[CB - 1], W_NEG16);
+            for (int cc = 0; cc < CB; ++cc) tv[cc] = __builtin_amdgcn_sbfe((int)tn[cc], vb8, 8);
+            const int hleft = wave_shr1(hcur[CB - 1], W_NEG16);
 #pragma unroll
-          for (int cc = 0; cc < CB; ++cc) {
-            const int hd = cc == 0 ? hleft : hcur[cc > 0 ? cc - 1 : 0];
-            key[cc] = max16(hd + tv[cc], hcur[cc] + cV);
+            for (int cc = 0; cc < CB; ++cc) {
+              const int hd = cc == 0 ? hleft : hcur[cc > 0 ? cc - 1 : 0];
+              key[cc] = max16(hd + tv[cc], hcur[cc] + cV);
+            }
+            WB_ROW_TAIL(false)
+            WB_FAST_NEXT()
           }
-          WB_ROW_TAIL(false)
         }
-        if (dx & (1u << 23)) WB_RING_WRITE()
-      } else {
+        if (li >= wend) break;
+        const int r = rb + li;
+        int key[CB];
 #ifdef C3_PHASE_PROF
         const unsigned long long gen_t0 = __builtin_readcyclecounter();
 #endif
@@ -390,106 +438,114 @@ __device__ __attribute__((noinline)) int win_rows_band(int* cI, int* cE, int32_t
         de.w = __builtin_amdgcn_readlane(dblk.w, li);
         const int np = (de.x >> 8) & 0xff;
         const bool ovf = (de.x >> 16) & 1, two = (de.x >> 19) & 1;
-        if (np > 64) return -1;
-        lo = WB_W_LO(de.w);
-        const int vb8 = (int)(dx & 24u);
-        int tv[CB];
+        if (np > 64) { ret = -1; Rl = 0; cnt = 0; li = 64; }             // more predecessors than the rows take: all three loops end at their own tests
+        else {
+          lo = WB_W_LO(de.w);
+          const int vb8 = (int)(dx & 24u);
+          int tv[CB];
 #pragma unroll
-        for (int cc = 0; cc < CB; ++cc) tv[cc] = __builtin_amdgcn_sbfe((int)tp[lo + cc], vb8, 8);
+          for (int cc = 0; cc < CB; ++cc) tv[cc] = __builtin_amdgcn_sbfe((int)tp[lo + cc], vb8, 8);
 #pragma unroll
-        for (int k = 0; k <= CB; ++k) tn[k] = tp[lo + k];                   // for the row below
-        int kedge = 0;
-        for (int t = 0; t < np; ++t) {
-          int prow;
-          if ((de.x >> 24) & 1) prow = 0;
-          else if (!ovf) prow = (t == 0) ? (de.y & 0xffff) : (t == 1) ? (de.y >> 16) : (t == 2) ? (de.z & 0xffff) : (de.z >> 16);
-          else {
-            const int v = GP(const int, c.rows().ptr())[r];
-            prow = -1;
-            while (kedge < GP(const int, c.n_in().ptr())[v]) { int pr = GP(const int, c.rowof().ptr())[GP(const int, c.in_from().ptr())[EI(v, kedge)]]; ++kedge; if (pr >= 0) { prow = pr; break; } }
-            if (prow < 0) break;
+          for (int k = 0; k <= CB; ++k) tn[k] = tp[lo + k];                   // for the row below
+          int kedge = 0;
+          for (int t = 0; t < np; ++t) {
+            int prow;
+            if ((de.x >> 24) & 1) prow = 0;
+            else if (!ovf) prow = (t == 0) ? (de.y & 0xffff) : (t == 1) ? (de.y >> 16) : (t == 2) ? (de.z & 0xffff) : (de.z >> 16);
+            else {
+              const int v = GP(const int, c.rows().ptr())[r];
+              prow = -1;
+              while (kedge < GP(const int, c.n_in().ptr())[v]) { int pr = GP(const int, c.rowof().ptr())[GP(const int, c.in_from().ptr())[EI(v, kedge)]]; ++kedge; if (pr >= 0) { prow = pr; break; } }
+              if (prow < 0) break;
+            }
+            int hpv[CB + 1];                                                   // H[prow][lo + CB*lane - 1 + k]
+            if (prow == 0) {                                                   // the virtual start row: H[0][j] = j * gap
+              const int b0 = (lo + CB * lane - 1) * g4;
+#pragma unroll
+              for (int k = 0; k <= CB; ++k) hpv[k] = b0 + k * g4;
+              if (lo + CB * lane == 0) hpv[0] = W_NEG16;
+            } else if (r - prow <= WB_RING) {
+              const unsigned short* sp_ = ring + (prow & (WB_RING - 1)) * SLOT;
+              const int sh = lo - *(const int*)sp_;
+              if (sh > WB_MAXSHIFT) bandbad = 1;
+              const unsigned short* cp = sp_ + (WB_PADL - 1) + CB * lane + min(sh, WB_MAXSHIFT);
+#pragma unroll
+              for (int k = 0; k <= CB; ++k) hpv[k] = (int)cp[k];
+            } else {
+              const auto* hp_ = GP(const unsigned short, H16) + (size_t)prow * HS;
+              const int sh = lo - (int)((unsigned)hp_[0] | ((unsigned)hp_[1] << 16));
+              if (sh > WB_MAXSHIFT) bandbad = 1;
+#pragma unroll
+              for (int k = 0; k <= CB; ++k) { const int ix = CB * lane + sh - 1 + k; hpv[k] = (ix >= 0 && ix < BW) ? (int)hp_[WB_PADL + ix] : W_NEG16; }
+            }
+            if (t == 0) {
+#pragma unroll
+              for (int cc = 0; cc < CB; ++cc) key[cc] = max16(hpv[cc] + tv[cc], hpv[cc + 1] + cV);
+            } else {
+              const int tmark = t << 16;
+#pragma unroll
+              for (int cc = 0; cc < CB; ++cc) {
+                const int nk = max16(key[cc], max16(hpv[cc] + tv[cc], hpv[cc + 1] + cV));
+                key[cc] = nk != (key[cc] & 0xffff) ? (nk | tmark) : key[cc];
+              }
+            }
           }
-          int hpv[CB + 1];                                                   // H[prow][lo + CB*lane - 1 + k]
-          if (prow == 0) {                                                   // the virtual start row: H[0][j] = j * gap
-            const int b0 = (lo + CB * lane - 1) * g4;
+          if (two) WB_ROW_TAIL(false) else WB_ROW_TAIL(true)
+          if (de.x & (1u << 23)) WB_RING_WRITE()
+          if ((de.x >> 17) & 1) {
+            auto* hrow = GP(unsigned short, H16) + (size_t)r * HS;
+            hrow[0] = (unsigned short)lo; hrow[1] = (unsigned short)((unsigned)lo >> 16);
 #pragma unroll
-            for (int k = 0; k <= CB; ++k) hpv[k] = b0 + k * g4;
-            if (lo + CB * lane == 0) hpv[0] = W_NEG16;
-          } else if (r - prow <= WB_RING) {
-            const unsigned short* sp_ = ring + (prow & (WB_RING - 1)) * SLOT;
-            const int sh = lo - *(const int*)sp_;
-            if (sh > WB_MAXSHIFT) bandbad = 1;
-            const unsigned short* cp = sp_ + (WB_PADL - 1) + CB * lane + min(sh, WB_MAXSHIFT);
-#pragma unroll
-            for (int k = 0; k <= CB; ++k) hpv[k] = (int)cp[k];
-          } else {
-            const auto* hp_ = GP(const unsigned short, H16) + (size_t)prow * HS;
-            const int sh = lo - (int)((unsigned)hp_[0] | ((unsigned)hp_[1] << 16));
-            if (sh > WB_MAXSHIFT) bandbad = 1;
-#pragma unroll
-            for (int k = 0; k <= CB; ++k) { const int ix = CB * lane + sh - 1 + k; hpv[k] = (ix >= 0 && ix < BW) ? (int)hp_[WB_PADL + ix] : W_NEG16; }
+            for (int cc = 0; cc < CB; ++cc) hrow[WB_PADL + CB * lane + cc] = (unsigned short)hcur[cc];
           }
-          if (t == 0) {
+          if ((de.x >> 18) & 1) {                                             // an end row: H[r][Q] is a candidate end of the alignment (first maximum in row order)
 #pragma unroll
-            for (int cc = 0; cc < CB; ++cc) key[cc] = max16(hpv[cc] + tv[cc], hpv[cc + 1] + cV);
-          } else {
-            const int tmark = t << 16;
-#pragma unroll
-            for (int cc = 0; cc < CB; ++cc) {
-              const int nk = max16(key[cc], max16(hpv[cc] + tv[cc], hpv[cc + 1] + cV));
-              key[cc] = nk != (key[cc] & 0xffff) ? (nk | tmark) : key[cc];
+            for (int cc = 0; cc < CB; ++cc) { const int sc = __builtin_amdgcn_sbfe(hcur[cc], 2, 14); if (lo + lane * CB + cc == Q && sc > ebs) { ebs = sc; ebr = r; } }
+          }
+#ifdef C3_PHASE_PROF
+          { const bool pm1 = (de.y & 0xffff) == (unsigned)(r - 1); pf_d0 += (1ull << 32) + (two && pm1); pf_d1 += 1 + ((unsigned long long)!two << 32);
+            const unsigned long long dt_ = __builtin_readcyclecounter() - gen_t0; if (!two) pf_c2 += dt_; else if (pm1) pf_c4 += dt_; else pf_c3 += dt_; }
+#endif
+        }
+        if (++li >= wend) break;
+      }
+      if (li <= 64) {
+        // the word is complete, or the layer ends inside it (the last, partial word)
+        const int miss = li & (RPW - 1) ? RPW - (li & (RPW - 1)) : 0;
+        GP(unsigned, DW)[dwoff] = dacc >> (BPR * miss); dwoff += 64; dacc = 0;
+        if ((li & (WB_EROWS - 1)) == 0 || li == cnt) {
+          eoff = ebase;
+          // certificate bound of these rows: lane li holds the descriptor of row rb + li, the edge cells sit in ebuf[li & 31]
+          if (lane >= ((li - 1) & ~(WB_EROWS - 1)) && lane < li) {
+            const unsigned short* e = ebuf + (lane & (WB_EROWS - 1)) * WB_EROW;
+            const int r = rb + lane;
+            const int lo_r = WB_W_LO(dblk.w), dist = WB_W_DIST(dblk.w), nb = NB - WB_W_BIDX(dblk.w);
+            const int hi = lo_r + BW - 1;
+            if (hi < Q) best = max(best, ((int)(short)e[8 + CB - 1] >> 2) + ups * (Q - hi));
+            if (((dblk.x >> 24) & 1) && lo_r > 0) best = max(best, ups * min(Q, nb + 1) + gap * max(0, Q - nb - 1));      // entered from (0, j), j < lo
+            if (dist > 0) {
+              // leftspan = lo(r + dist) - lo(r): shift bits of rows r+1 .. r+dist = bit indices r .. r+dist-1
+              const int w0 = r >> 6, off = r & 63;
+              unsigned long long a0 = d0bits[w0] >> off, a1 = d1bits[w0] >> off;
+              if (off) { a0 |= d0bits[w0 + 1] << (64 - off); a1 |= d1bits[w0 + 1] << (64 - off); }
+              const unsigned long long dm = dist >= 64 ? ~0ull : ((1ull << dist) - 1ull);
+              const int ls = __popcll(a0 & dm) + 2 * __popcll(a1 & dm);
+              if (ls > 2 * CB) bandbad = 1;                                        // only the first 2*CB cells of a row are parked
+              for (int b = 0; b < min(ls, 2 * CB); ++b) {
+                const int rem = Q - lo_r - b;
+                best = max(best, ((int)(short)e[b] >> 2) + ups * min(rem, nb) + gap * max(0, rem - nb));
+              }
             }
           }
         }
-        if (two) WB_ROW_TAIL(false) else WB_ROW_TAIL(true)
-        if (de.x & (1u << 23)) WB_RING_WRITE()
-        if ((de.x >> 17) & 1) {
-          auto* hrow = GP(unsigned short, H16) + (size_t)r * HS;
-          hrow[0] = (unsigned short)lo; hrow[1] = (unsigned short)((unsigned)lo >> 16);
-#pragma unroll
-          for (int cc = 0; cc < CB; ++cc) hrow[WB_PADL + CB * lane + cc] = (unsigned short)hcur[cc];
-        }
-        if ((de.x >> 18) & 1) {                                             // an end row: H[r][Q] is a candidate end of the alignment (first maximum in row order)
-#pragma unroll
-          for (int cc = 0; cc < CB; ++cc) { const int sc = __builtin_amdgcn_sbfe(hcur[cc], 2, 14); if (lo + lane * CB + cc == Q && sc > ebs) { ebs = sc; ebr = r; } }
-        }
-#ifdef C3_PHASE_PROF
-        { const bool pm1 = (de.y & 0xffff) == (unsigned)(r - 1); pf_d0 += (1ull << 32) + (two && pm1); pf_d1 += 1 + ((unsigned long long)!two << 32);
-          const unsigned long long dt_ = __builtin_readcyclecounter() - gen_t0; if (!two) pf_c2 += dt_; else if (pm1) pf_c4 += dt_; else pf_c3 += dt_; }
-#endif
       }
-      if ((li & (RPW - 1)) == RPW - 1) { GP(unsigned, DW)[dwoff] = dacc; dwoff += 64; dacc = 0; }
-    }
-    if (hend_ == cnt && (cnt & (RPW - 1))) {                                 // the last, partial word of the layer
-      const int miss = RPW - (cnt & (RPW - 1));
-      GP(unsigned, DW)[dwoff] = dacc >> (BPR * miss); dwoff += 64; dacc = 0;
-    }
-    // certificate bound of these rows: lane li holds the descriptor of row rb + li, the edge cells sit in ebuf[li & 31]
-    if (lane >= half_ && lane < hend_) {
-      const unsigned short* e = ebuf + (lane & (WB_EROWS - 1)) * WB_EROW;
-      const int r = rb + lane;
-      const int lo_r = WB_W_LO(dblk.w), dist = WB_W_DIST(dblk.w), nb = NB - WB_W_BIDX(dblk.w);
-      const int hi = lo_r + BW - 1;
-      if (hi < Q) best = max(best, ((int)(short)e[8 + CB - 1] >> 2) + ups * (Q - hi));
-      if (((dblk.x >> 24) & 1) && lo_r > 0) best = max(best, ups * min(Q, nb + 1) + gap * max(0, Q - nb - 1));      // entered from (0, j), j < lo
-      if (dist > 0) {
-        // leftspan = lo(r + dist) - lo(r): shift bits of rows r+1 .. r+dist = bit indices r .. r+dist-1
-        const int w0 = r >> 6, off = r & 63;
-        unsigned long long a0 = d0bits[w0] >> off, a1 = d1bits[w0] >> off;
-        if (off) { a0 |= d0bits[w0 + 1] << (64 - off); a1 |= d1bits[w0 + 1] << (64 - off); }
-        const unsigned long long dm = dist >= 64 ? ~0ull : ((1ull << dist) - 1ull);
-        const int ls = __popcll(a0 & dm) + 2 * __popcll(a1 & dm);
-        if (ls > 2 * CB) bandbad = 1;                                        // only the first 2*CB cells of a row are parked
-        for (int b = 0; b < min(ls, 2 * CB); ++b) {
-          const int rem = Q - lo_r - b;
-          best = max(best, ((int)(short)e[b] >> 2) + ups * min(rem, nb) + gap * max(0, rem - nb));
-        }
-      }
-    }
     }
   }
 #undef WB_ROW_TAIL
 #undef WB_RING_WRITE
+#undef WB_FAST_NEXT
+#undef WB_PF_FAST
+  if (ret < 0) return -1;
   best = wave_max(best);
   const int gbs = wave_max(ebs);
   const int gbr = wave_min(ebs == gbs ? ebr : INT32_MAX / 2);
